@@ -47,6 +47,7 @@ FWD_FLOP_PER_ROW_EXECUTED = {"fp32": 1186816, "h16": 1186816 - 2 * 65536}
 TRAFFIC_FILE = "r06_traffic.json"   # refreshed per round by tools/pmc_traffic.sh
 PSNR_FILE = "r06_psnr_plain_modes.jsonl"      # tools/psnr_plain_modes.py on the round's kernels (the throughput mode's dB figure)
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8 TB/s HBM3E
+DUMP_BUDGET_BYTES = 64 << 20    # --dump-outputs: the files' total size
 # training forward, algorithmic bytes per row: saved state written + xyz read (12) + raw written (16)
 FWD_TRAIN_BYTES_PER_ROW = {"fp32": 2596 * 4 + 28, "h16": 2272 * 2 + 272 + 28}   # fp32 planes | half planes + relu masks
 PEAK_TFLOPS = {"fp32": 157.3, "bf16x3": 2500.0, "bf16": 2500.0, "f16x3": 2500.0, "f16": 2500.0}   # MI355X_MICROARCH.md, dense
@@ -111,7 +112,14 @@ def parse(argv=None):
                     help="launcher self-test: this rank raises before the first step (the launcher must stop the others "
                          "and exit non-zero)")
     ap.add_argument("--launch-timeout", type=float, default=1800.0, help="seconds the self-spawned ranks may run")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step handed its caller (its return "
+                         "values, both networks' weights after the step and the gradients left in .grad) as DIR/<name>.npy, "
+                         f"float32 (float64 and integers: float64), at most {DUMP_BUDGET_BYTES >> 20} MB in all")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def make_args(a, ckpt_dir, precision):
@@ -256,9 +264,12 @@ def build_step(P, a, precision, scene, dev, rank, world, force_dist):
                                                    scene.near, scene.far, seed=0, step=i, ray_id0=rank * a.rays,
                                                    want_pixels=True)
             target_h = scene.hyp[v][:, pix[:, 0].long(), pix[:, 1].long()].unsqueeze(-1)
-            loss, _, _, _ = ts(cols, target, target_h)
+            loss, img_loss, sc, out = ts(cols, target, target_h)
+            # (detached: the render outputs kept until the next step must not keep this step's autograd graph alive)
+            step.last = (loss, img_loss, sc, {k: v.detach() for k, v in out.items() if torch.is_tensor(v)})
             return loss
         step.trainer = ts
+        step.names = ("loss", "img_loss", "space_carving_loss", "render")
         return step, nets
     args = make_args(a, ck, precision)
     _stdout = sys.stdout
@@ -275,10 +286,11 @@ def build_step(P, a, precision, scene, dev, rank, world, force_dist):
 
     def step(i):
         v = i % len(scene.poses)
-        loss, _ = ts.step_view(scene.H, scene.W, scene.K, scene.poses[v], scene.images[v], near=scene.near,
-                               far=scene.far, n_rand=a.rays)
-        return loss
+        step.last = ts.step_view(scene.H, scene.W, scene.K, scene.poses[v], scene.images[v], near=scene.near,
+                                 far=scene.far, n_rand=a.rays)
+        return step.last[0]
     step.trainer = ts
+    step.names = ("loss", "psnr")
     return step, nets
 
 
@@ -426,8 +438,10 @@ def build_stub_step(rank, world):
         t0 = time.perf_counter()
         bucket.allreduce_mean()
         step.allreduce_s.append(time.perf_counter() - t0)
+        step.last = (loss.detach(),)
         return loss
     step.allreduce_s = []
+    step.names = ("loss",)
     return step, nets
 
 
@@ -509,6 +523,48 @@ def peak_of(precision):
 
 def stats_ms(v):
     return {"min": min(v), "median": statistics.median(v), "max": max(v)} if v else None
+
+
+def dump_outputs(out_dir, step, nets):
+    """--dump-outputs: what the last timed step handed its caller -- its return values (step.names; a dict such as the depth
+    step's render outputs as <name>.<key>), then per network (network_fn, network_fine) every parameter after the step and
+    the gradient the step left in its .grad -- as out_dir/<name>.npy.  float64 stays float64, integers become float64,
+    everything else float32.  Should the files exceed DUMP_BUDGET_BYTES, every array of more than 4096 elements is cut to
+    a fixed sample of its flattened elements (sorted indices from a generator seeded by the name), the same on every run
+    with the same arguments.  Returns a summary for the JSON line."""
+    import zlib
+    import numpy as np
+    arrays = {}
+
+    def put(name, t):
+        if torch.is_tensor(t):
+            t = t.detach().cpu()
+            arrays[name] = t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()
+    for name, v in zip(step.names, step.last):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                put(f"{name}.{k}", v[k])
+        else:
+            put(name, v)
+    for tag, net in zip(("network_fn", "network_fine"), nets):
+        for pname, prm in net.named_parameters():
+            put(f"{tag}.{pname}", prm)
+            put(f"{tag}.{pname}.grad", prm.grad)
+    budget = DUMP_BUDGET_BYTES - 256 * len(arrays)      # (room for the .npy headers)
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    if total > budget:
+        big = sum(t.numel() * t.element_size() for t in arrays.values() if t.numel() > 4096)
+        keep = (budget - (total - big)) / big
+        for k, t in arrays.items():
+            if t.numel() > 4096:
+                n = max(1, int(t.numel() * keep))
+                idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(t.numel(), n, replace=False))
+                arrays[k] = t.reshape(-1)[torch.from_numpy(idx)]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, t in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), t.numpy())
+    written = sum(t.numel() * t.element_size() for t in arrays.values())
+    return {"dir": os.path.abspath(out_dir), "files": len(arrays), "bytes": written, "sampled": total > budget}
 
 
 def main(argv=None):
@@ -597,6 +653,9 @@ def main(argv=None):
     dt, final_loss, per_rank_s, per_step_ms = timed(step, a.warmup, a.steps, timer)
     host_per_rank_s = list(timed.host_per_rank)
     merged_steps = getattr(getattr(step, "trainer", None), "merged_steps", None)
+    dumped = None
+    if a.dump_outputs and rank == 0:     # (the timed steps are over: the other legs below build networks of their own)
+        dumped = dict(dump_outputs(a.dump_outputs, step, nets), step=a.warmup + a.steps - 1)
 
     strict = None
     if a.precision != "fp32" and not a.no_strict_fp32 and world == 1 and not cpu:
@@ -691,7 +750,8 @@ def main(argv=None):
             "ranks": {"ms_per_step": stats_ms([1e3 * x / a.steps for x in per_rank_s]),
                       "host_ms_per_step": stats_ms([1e3 * x / a.steps for x in host_per_rank_s]),
                       "omp_num_threads": pinned["omp_num_threads"], "numa_node_rank0": pinned["numa_node"],
-                      "allreduce_exposed_ms_max_over_ranks": float(ex_mean.item())}}), flush=True)
+                      "allreduce_exposed_ms_max_over_ranks": float(ex_mean.item())},
+            **({"dump_outputs": dumped} if dumped else {})}), flush=True)
     elif rank == 0:
         ms = 1e3 * dt / a.steps
         fwd_ms = timer.mean_ms(f"mlp_fwd[{rows_fine}]")
@@ -782,6 +842,8 @@ def main(argv=None):
                 "step_tflops": (R * (2 * a.n_samples + a.n_importance) * TRAIN_FLOP_PER_ROW / (ms * 1e-3) / 1e12),
             },
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if strict is not None:
             out["strict_fp32"] = strict
         out.update(extra)

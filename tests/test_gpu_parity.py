@@ -1337,7 +1337,7 @@ def test_full_image_render_c2w(P):
     assert_close(extras["rgb0"].reshape(-1, 3), ref["rgb0"], what="full-image rgb0")
 
 
-def test_render_path(P):
+def test_render_path(P, tmp_path):
     """render_path (run_plnerf.py:178-216): one render() per pose, numpy stacks, render_factor downsampling;
     image writing is outside the path and refuses loudly."""
     H, W, f = 8, 12, 14.0
@@ -1358,4 +1358,4 @@ def test_render_path(P):
     half = P.render_path(poses[:1], (H, W, f), K, 64, kw, render_factor=2)[0]
     assert half.shape == (1, H // 2, W // 2, 3)
     with pytest.raises(NotImplementedError):
-        P.render_path(poses[:1], (H, W, f), K, 64, kw, savedir="/tmp/x")
+        P.render_path(poses[:1], (H, W, f), K, 64, kw, savedir=str(tmp_path))

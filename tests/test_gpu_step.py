@@ -405,7 +405,7 @@ HW, N_RAND, STEPS = int(sys.argv[2]), int(sys.argv[3]), 3      # view size, rays
 rank, world, _ = dp.init_from_env(backend="gloo")          # every rank on cuda:0; gloo moves CUDA tensors through the host
 dev = torch.device("cuda:0")
 torch.cuda.set_device(0)
-FLAGGED = [r for r in (1, 5) if r < world]                  # ranks whose fine forward "leaves the half range" below
+FLAGGED = [r for r in (1, 3) if r < world]                  # ranks whose fine forward "leaves the half range" below
 
 
 def make(distributed):
@@ -537,13 +537,14 @@ def test_data_parallel_training_step_two_ranks_on_one_gpu(P, tmp_path):
     _run_dp_ranks(tmp_path, 2, 64, 128, 600)
 
 
-def test_baseline_config2_eight_shards_equal_one_global_batch(P, tmp_path):
-    """BASELINE configs[2] in its real shape, minus the other seven GPUs: EIGHT ranks x 4096 rays of an 800 x 800 view
-    (global batch 32,768; global ray ids up to 32,767 through the counter-based pixel choice and draws; 1 / world = 1 / 8
-    inside the Adam kernel; status tails summed over eight ranks), time-sharing one MI355X over gloo, against ONE rank
-    stepping the whole 32,768-ray batch: parameters after three steps equal to fp32 summation-order tolerance.  What
-    this leaves untested of configs[2] is the RCCL wire itself."""
-    _run_dp_ranks(tmp_path, 8, 800, 4096, 1500)
+def test_baseline_config2_global_batch_four_shards_equal_one_rank(P, tmp_path):
+    """BASELINE configs[2]'s global batch on one GPU: FOUR ranks x 8192 rays of an 800 x 800 view (global batch 32,768;
+    global ray ids up to 32,767 through the counter-based pixel choice and draws; 1 / world = 1 / 4 inside the Adam kernel;
+    status tails summed over four ranks, two of them set), time-sharing one MI355X over gloo, against ONE rank stepping the
+    whole 32,768-ray batch: parameters after three steps equal to fp32 summation-order tolerance.  Four ranks, not
+    configs[2]'s eight: the ranks and this test's own process must stay within six processes holding a shared GPU open at
+    once.  What this leaves untested of configs[2] is the eight-way split and the RCCL wire itself."""
+    _run_dp_ranks(tmp_path, 4, 800, 8192, 1500)
 
 
 # ----------------------------------------------------------------------------- the depth-supervised step, data parallel
@@ -694,12 +695,13 @@ def test_depth_supervised_step_data_parallel_two_ranks_on_one_gpu(P, tmp_path, j
     _run_dp_depth_ranks(tmp_path, 2, 64, 128, joint, 600)
 
 
-def test_baseline_config4_eight_shards_equal_one_global_batch(P, tmp_path):
-    """BASELINE configs[4] in its real shape, minus the other seven GPUs: the depth-supervised step at N_samples 128 /
-    N_importance 64, EIGHT ranks x 4096 rays of an 800 x 800 view time-sharing one MI355X over gloo, against ONE rank stepping
-    the 32,768-ray batch (clip on the averaged gradient, tails summed over eight ranks, one exchange per step).  What this leaves
-    untested of configs[4] is the RCCL wire."""
-    _run_dp_depth_ranks(tmp_path, 8, 800, 4096, False, 1500)
+def test_baseline_config4_global_batch_four_shards_equal_one_rank(P, tmp_path):
+    """BASELINE configs[4]'s global batch on one GPU: the depth-supervised step at N_samples 128 / N_importance 64, FOUR ranks
+    x 8192 rays of an 800 x 800 view time-sharing one MI355X over gloo, against ONE rank stepping the 32,768-ray batch (clip on
+    the averaged gradient, tails summed over four ranks, one exchange per step).  Four ranks, not configs[4]'s eight: the ranks
+    and this test's own process must stay within six processes holding a shared GPU open at once.  What this leaves untested
+    of configs[4] is the eight-way split and the RCCL wire."""
+    _run_dp_depth_ranks(tmp_path, 4, 800, 8192, False, 1500)
 
 
 @pytest.mark.parametrize("precision,n_rows", [("f16x3", 131072), ("f16x3", 262144), ("f16x3", 1000), ("fp32", 8200),

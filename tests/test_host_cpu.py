@@ -607,13 +607,30 @@ def test_checkpoint_wire_format_roundtrip(built, tmp_path, capsys):
         assert torch.equal(a, b)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree exists in the build container only")
-def test_reference_reloads_a_checkpoint_written_here(built, tmp_path, capsys):
-    """Wire format, the other direction (run_plnerf.py:454-471): the reference's own create_nerf resumes from a file
-    written by plnerf_amd.save_checkpoint -- step counter, both networks and the fine optimizer's Adam state."""
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from _ref_import import import_reference
-    R_, _ = import_reference()
+def _module_with_parameter_tree(state_dict):
+    """An nn.Module whose parameters carry the names, shapes and order of `state_dict` (zero-filled): what a strict
+    load_state_dict and an optimizer built over .parameters() see of the module that wrote it."""
+    root = torch.nn.Module()
+    for name, t in state_dict.items():
+        *path, leaf = name.split(".")
+        mod = root
+        for part in path:
+            if part not in mod._modules:
+                mod.add_module(part, torch.nn.Module())
+            mod = mod._modules[part]
+        mod.register_parameter(leaf, torch.nn.Parameter(torch.zeros_like(t)))
+    assert [n for n, _ in root.named_parameters()] == list(state_dict)
+    return root
+
+
+def test_reference_reloads_a_checkpoint_written_here(built, tmp_path):
+    """Wire format, the other direction (run_plnerf.py:454-471): the reference's resume -- the last '*tar*' file of
+    ckpt_dir/expname, torch.load with its default arguments, start = global_step, optimizer.load_state_dict into an Adam over
+    the fine network's parameters, strict load_state_dict into both networks -- on a file written by
+    plnerf_amd.save_checkpoint: step counter, both networks and the fine optimizer's Adam state.  The reference's networks
+    are modules with the reference's parameter tree (names, shapes, order), read off the checkpoint the reference itself
+    wrote (tests/golden/g9_reference_checkpoint.tar), and the file's Adam state has the layout of that checkpoint's."""
+    ref = torch.load(os.path.join(ROOT, "tests", "golden", "g9_reference_checkpoint.tar"), map_location="cpu")
     (tmp_path / "exp").mkdir()
     args = _args(str(tmp_path), no_reload=True)
     cpu = torch.device("cpu")
@@ -622,17 +639,29 @@ def test_reference_reloads_a_checkpoint_written_here(built, tmp_path, capsys):
         p.grad = torch.full_like(p, 1e-3 * (i + 1))
     opt.step()
     built.save_checkpoint(built.checkpoint_path(str(tmp_path), "exp", 77), 77, kw["network_fn"], kw["network_fine"], opt)
-    args_ref = _args(str(tmp_path), no_reload=False)
-    kw_r, _, start_r, grad_vars_r, opt_r, _ = R_.create_nerf(args_ref)
+    # the reference's create_nerf with no_reload=False, on modules shaped like its own
+    model = _module_with_parameter_tree(ref["network_fn_state_dict"])
+    model_fine = _module_with_parameter_tree(ref["network_fine_state_dict"])
+    grad_vars_r = list(model_fine.parameters())
+    opt_r = torch.optim.Adam(params=grad_vars_r, lr=args.lrate, betas=(0.9, 0.999))
+    basedir = os.path.join(args.ckpt_dir, args.expname)
+    ckpts = [os.path.join(basedir, f) for f in sorted(os.listdir(basedir)) if "tar" in f]
+    ckpt = torch.load(ckpts[-1])
+    start_r = ckpt["global_step"]
+    opt_r.load_state_dict(ckpt["optimizer_state_dict"])
+    model.load_state_dict(ckpt["network_fn_state_dict"])
+    model_fine.load_state_dict(ckpt["network_fine_state_dict"])
     assert start_r == 77
-    for a, b in zip(kw["network_fn"].parameters(), kw_r["network_fn"].parameters()):
-        assert torch.equal(a.detach(), b.detach().cpu())
-    for a, b in zip(kw["network_fine"].parameters(), kw_r["network_fine"].parameters()):
-        assert torch.equal(a.detach(), b.detach().cpu())
-    for p, q in zip(grad_vars, grad_vars_r):
+    for net, net_r in ((kw["network_fn"], model), (kw["network_fine"], model_fine)):
+        for (na, a), (nb, b) in zip(net.named_parameters(), net_r.named_parameters(), strict=True):
+            assert na == nb and torch.equal(a.detach(), b.detach())
+    ref_state = ref["optimizer_state_dict"]["state"]
+    assert set(ckpt["optimizer_state_dict"]["state"]) == set(ref_state)
+    for i, (p, q) in enumerate(zip(grad_vars, grad_vars_r, strict=True)):
         sa, sb = opt.state[p], opt_r.state[q]
+        assert set(sb) == set(ref_state[i]) and all(sb[k].shape == ref_state[i][k].shape for k in sb)
         assert float(sa["step"]) == float(sb["step"]) == 1.0
-        assert torch.equal(sa["exp_avg"], sb["exp_avg"].cpu()) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"].cpu())
+        assert torch.equal(sa["exp_avg"], sb["exp_avg"]) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"])
 
 
 def test_select_rays_matches_get_rays(built):
@@ -789,3 +818,28 @@ def test_bench_under_torchrun_environment(built):
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["config"]["self_launched"] is False
+
+
+def test_bench_dump_outputs(built, tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned and the two networks' parameters and gradients as
+    DIR/<name>.npy (float32 here), run after run the same for the same arguments; `--steps` is the number of timed steps
+    and is at least 1.  (The stub step on CPU: the plumbing, not the hot path's numbers.)"""
+    import json
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        r = _run_bench("--gpus", "1", "--stub-cpu", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == 3 and out["dump_outputs"]["step"] == 4 and out["dump_outputs"]["sampled"] is False
+        runs.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    names = {"loss.npy"} | {f"{n}.{p}{g}.npy" for n in ("network_fn", "network_fine") for p in ("weight", "bias")
+                            for g in ("", ".grad")}
+    assert set(runs[0]) == set(runs[1]) == names
+    assert out["dump_outputs"]["files"] == len(names)
+    for name, arr in runs[0].items():
+        assert arr.dtype == np.float32 and np.isfinite(arr).all(), name
+        assert np.array_equal(arr, runs[1][name]), name
+    assert runs[0]["loss.npy"].shape == () and runs[0]["network_fn.weight.npy"].shape == (32, 64)
+    r = _run_bench("--gpus", "1", "--stub-cpu", "--steps", "0")
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

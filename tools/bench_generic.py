@@ -1,5 +1,5 @@
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import plnerf_amd as P
 dev = torch.device("cuda:0")
 emb, ic = P.get_embedder(10, 0); embd, icv = P.get_embedder(4, 0)

@@ -2,7 +2,7 @@
 # (Re)compile csrc/mlp_rr.hip with extra flags and link a library variant.
 #   bash tools/build_rr.sh                      -> resource report of all six instantiations (single translation unit)
 #   bash tools/build_rr.sh <name> -DRR_...      -> tools/_head/librr_<name>.so (git-ignored A/B variant)
-R=/root/repo; C=$R/pl-nerf_amd/csrc
+R=$(cd "$(dirname "$0")/.." && pwd); C=$R/pl-nerf_amd/csrc
 name=$1; shift
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -mllvm -amdgpu-mfma-vgpr-form"
 if [ -z "$name" ]; then

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel, per-grid stats of one bench.py run under rocprofv3 (first N lines of the CSV).
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 out=$R/gpurun_out/kstats; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $out/prof -o x -- python $R/bench.py --no-cpu-baseline ${BENCH_ARGS} > $out/bench.json 2> $out/err.log

@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ / LDS / TCP counters per kernel of one bench.py run: three separate rocprofv3 --pmc passes (counters only; no trace
 # domains), per kernel and grid (tools/pmc_summary.py) -> gpurun_out/pmc_sq/summary.txt
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 out=$R/gpurun_out/pmc_sq; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py --no-cpu-baseline --no-strict-fp32 --no-extra-legs --steps 3 --warmup 1 ${BENCH_ARGS}"

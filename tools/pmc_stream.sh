@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ / LDS / TCP counters of the per-ray (HBM / VALU bound) kernels at a chip-filling size (262,144 rays): separate
 # rocprofv3 --pmc passes, counters only (no trace domains) -> gpurun_out/pmc_stream/summary.txt
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 out=$R/gpurun_out/pmc_stream; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 B="python $R/tools/bench_stream_kernels.py --rays 262144 --reps 2"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # HBM traffic per kernel from two separate rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE cannot share a pass) of a
 # short bench.py run; prints the per-kernel means (KiB) and writes gpurun_out/pmc_traffic/{summary.txt,traffic.json}.
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 out=$R/gpurun_out/pmc_traffic; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do

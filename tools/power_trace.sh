@@ -2,7 +2,7 @@
 # Socket power and shader clock (rocm-smi, 5 samples/s) while bench.py runs a long timed region.
 #   gpurun -- 'bash tools/power_trace.sh f16x3 600'
 prec=${1:-f16x3}; steps=${2:-600}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R
 ( for i in $(seq 1 60); do rocm-smi --showpower --showclocks --json 2>/dev/null | python -c "
 import sys, json, time

@@ -2,7 +2,7 @@
 # One gpurun call that regenerates a round's evidence from the working tree:
 #   gpurun --timeout 3000 -- 'ROUND=r06 COMMIT=<git rev-parse --short HEAD> bash tools/refresh_profiles.sh'
 # then, in the build container:  for f in gpurun_out/r06p/*; do cp $f profiles/r06_$(basename $f); done
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 out=$R/gpurun_out/${ROUND:-r06}p
 mkdir -p $out
 cd $R

@@ -4,7 +4,7 @@
 # (BWD=1: of the dgrad kernel).  Works on the GPU box (hipcc is in the image) or here (then ship tools/_head/).
 export PLNERF_ALLOW_TOOLS_BUILD=1      # variant libraries carry ablation / trace switches (pl-nerf_amd/_lib.py refuses them otherwise)
 set -e
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R/pl-nerf_amd/csrc
 out=/tmp/libplnerf_trace.so
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -w -DPLNERF_TRACE=${TRACE_BLOCK:-3000} ${EXTRA_DEFS} -c mlp_bf16.hip -o /tmp/mlp_bf16_trace.o
