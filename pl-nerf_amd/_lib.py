@@ -18,7 +18,7 @@ COLOR = {"midpoint": 0, "left": 1}
 PRECISION = {"fp32": 0, "bf16x3": 1, "bf16": 2, "f16x3": 3, "f16": 4}
 GUARDED_PRECISIONS = ("f16x3", "f16", "bf16x3", "bf16")      # modes whose kernels can set a bit of the range status word
 N_PARAM_TENSORS = 24
-ABI_VERSION = 600                      # PLNERF_VERSION of include/plnerf_hip.h this binding was written against
+ABI_VERSION = 601                      # PLNERF_VERSION of include/plnerf_hip.h this binding was written against
 QUAD_RAYS_PER_GROUP = 4                # PLNERF_QUAD_RAYS_PER_GROUP: rays per workgroup of plnerf_quad_bwd (its absmax_out)
 DEPTH_LOSS_WORKSPACE_BYTES = 4096      # PLNERF_DEPTH_LOSS_WORKSPACE_BYTES
 IMAGE_LOSS_WORKSPACE_BYTES = 4096      # PLNERF_IMAGE_LOSS_WORKSPACE_BYTES
@@ -86,6 +86,12 @@ SIGNATURES = {
     "plnerf_mlp_status_offset": (ctypes.c_size_t, [c_i]),
 }
 
+# ... and include/plnerf_hip_batching.h (ABI 601): the use_batching ray source
+BATCHING_SIGNATURES = {
+    "plnerf_select_bank_rays": (c_i, [c_i, c_f, c_i, c_i] + [ctypes.c_float] * 4 + [c_f, c_f, ctypes.c_uint64, ctypes.c_uint32,
+                                c_i, c_i, ctypes.c_float, ctypes.c_float] + [c_f] * 7 + [c_s]),
+}
+
 _lib = None
 
 
@@ -100,7 +106,7 @@ def lib():
                 "plnerf_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

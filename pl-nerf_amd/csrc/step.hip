@@ -4,6 +4,8 @@
 //   plnerf_uniform         counter-based uniform draws (philox.h): the t_rand / u tensors, world-size invariant
 //   plnerf_normal          the same counters through Box-Muller: the density noise of raw2outputs (run_plnerf.py:568-570)
 //   plnerf_select_rays     run_plnerf.py:1259-1281: N_rand distinct random pixels of one view -> their rays
+//   plnerf_select_bank_rays run_plnerf.py:1199-1249 (use_batching): the next rays of a shuffled bank of every pixel of
+//                          every training view -> their rays, as plnerf_select_rays builds them
 //   plnerf_ndc_rays        run_nerf_helpers.py:184-201: the NDC warp of forward-facing rays
 //                          (get_rays, run_nerf_helpers.py:162-171), unit view directions (run_plnerf.py:148-150),
 //                          near / far columns and the target colours -- without building the H x W ray grid
@@ -23,6 +25,7 @@
 // reference's order.
 #include "common.h"
 #include "philox.h"
+#include "../../include/plnerf_hip_batching.h"
 
 using namespace plnerf;
 
@@ -100,6 +103,16 @@ __device__ __forceinline__ uint32_t perm_index(const PixelPerm& p, uint32_t x) {
     return x;
 }
 
+// pixel (row, col) -> camera ray direction d and |d| (run_nerf_helpers.py:166-169):
+// dirs = ((i - cx) / fx, -(j - cy) / fy, -1);  rays_d[k] = sum_j dirs[j] * c2w[k][j], summed left to right as torch does
+__device__ __forceinline__ float pixel_ray(const int row, const int col, const float fx, const float fy, const float cx,
+                                           const float cy, const float* c2w, float d[3]) {
+    const float d0 = ((float)col - cx) / fx, d1 = -((float)row - cy) / fy, d2 = -1.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = (d0 * c2w[4 * k + 0] + d1 * c2w[4 * k + 1]) + d2 * c2w[4 * k + 2];
+    return sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+}
+
 struct SelectArgs {
     int H, W;
     float fx, fy, cx, cy;
@@ -123,12 +136,8 @@ __global__ __launch_bounds__(256) void select_rays_kernel(const SelectArgs a) {
     if (i >= a.R) return;
     const uint32_t pick = perm_index(a.perm, (uint32_t)(a.ray_id0 + i));
     const int row = a.r0 + (int)(pick / (uint32_t)a.nc), col = a.c0 + (int)(pick % (uint32_t)a.nc);
-    // dirs = ((i - cx) / fx, -(j - cy) / fy, -1);  rays_d[k] = sum_j dirs[j] * c2w[k][j]   (run_nerf_helpers.py:166-169)
-    const float d0 = ((float)col - a.cx) / a.fx, d1 = -((float)row - a.cy) / a.fy, d2 = -1.0f;
     float d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d[k] = (d0 * a.c2w[4 * k + 0] + d1 * a.c2w[4 * k + 1]) + d2 * a.c2w[4 * k + 2];
-    const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    const float nrm = pixel_ray(row, col, a.fx, a.fy, a.cx, a.cy, a.c2w, d);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         a.rays_o[3 * (size_t)i + k] = a.c2w[4 * k + 3];
@@ -144,6 +153,59 @@ __global__ __launch_bounds__(256) void select_rays_kernel(const SelectArgs a) {
         a.target[3 * (size_t)i + 2] = px[2];
     }
     if (a.pixels) { a.pixels[2 * (size_t)i] = row; a.pixels[2 * (size_t)i + 1] = col; }
+}
+
+// ---- training rays from every pixel of every training view (run_plnerf.py:1199-1249, use_batching): bank index
+// b = t * H * W + row * W + col names pixel (row, col) of view views[t] -- the row order of the reference's rays_rgb before
+// its shuffle.  Ray i is bank entry perm_e(pos0 + i), perm_e the epoch's keyed bijection of [0, M); nothing of the bank is
+// materialised: the pose and the target are read from the views' arrays, the ray is pixel_ray's arithmetic.
+struct BankArgs {
+    const int* views;       // [n_views] indices into c2w / images
+    int H, W;
+    float fx, fy, cx, cy;
+    const float* c2w;       // [N_all, 12] rows of the 3x4 camera-to-world matrices
+    const float* images;    // [N_all, H, W, 3] or null
+    PixelPerm perm;         // over M = n_views * H * W
+    int pos0, R;
+    float near, far;
+    float* rays_o;
+    float* rays_d;
+    float* viewdirs;
+    float* near_out;
+    float* far_out;
+    float* target;
+    int* bank_index;        // [R] or null
+};
+
+__global__ __launch_bounds__(256) void select_bank_rays_kernel(const BankArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.R) return;
+    const uint32_t b = perm_index(a.perm, (uint32_t)(a.pos0 + i));
+    const uint32_t hw = (uint32_t)a.H * (uint32_t)a.W;
+    const uint32_t t = b / hw, pix = b - t * hw;
+    const int row = (int)(pix / (uint32_t)a.W), col = (int)(pix % (uint32_t)a.W);
+    const int v = a.views[t];
+    const float* c2w = a.c2w + 12 * (size_t)v;
+    float c[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) c[k] = c2w[k];
+    float d[3];
+    const float nrm = pixel_ray(row, col, a.fx, a.fy, a.cx, a.cy, c, d);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.rays_o[3 * (size_t)i + k] = c[4 * k + 3];
+        a.rays_d[3 * (size_t)i + k] = d[k];
+        if (a.viewdirs) a.viewdirs[3 * (size_t)i + k] = d[k] / nrm;
+    }
+    a.near_out[i] = a.near;
+    a.far_out[i] = a.far;
+    if (a.target && a.images) {
+        const float* px = a.images + ((size_t)v * hw + pix) * 3;
+        a.target[3 * (size_t)i + 0] = px[0];
+        a.target[3 * (size_t)i + 1] = px[1];
+        a.target[3 * (size_t)i + 2] = px[2];
+    }
+    if (a.bank_index) a.bank_index[i] = (int)b;
 }
 
 // ---- normalised device coordinates of forward-facing rays (run_nerf_helpers.py:184-201), one thread per ray ----
@@ -540,6 +602,21 @@ extern "C" int plnerf_normal(uint64_t seed, uint32_t stream_id, uint32_t step, i
     return PLNERF_OK;
 }
 
+// the keyed bijection of [0, M) (M <= 2^30): 2 hb >= log2 M bits, round keys from one Philox block on (seed, ctr)
+// under a per-use domain constant
+static PixelPerm make_perm(uint64_t M, uint32_t domain, uint64_t seed, uint32_t ctr) {
+    PixelPerm p{};
+    int bits = 1;
+    while ((1ull << bits) < M) ++bits;
+    p.hb = (bits + 1) / 2;
+    if (p.hb < 1) p.hb = 1;
+    p.M = (uint32_t)M;
+    uint32_t c[4] = {domain, 0u, 0xffffffffu, ctr};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    for (int i = 0; i < 4; ++i) p.key[i] = c[i];
+    return p;
+}
+
 extern "C" int plnerf_select_rays(int H, int W, float fx, float fy, float cx, float cy, const float* c2w_host,
                                   const float* image, int crop_r0, int crop_c0, int crop_rows, int crop_cols,
                                   uint64_t seed, uint32_t step, int ray_id0, int R, float near, float far,
@@ -556,18 +633,33 @@ extern "C" int plnerf_select_rays(int H, int W, float fx, float fy, float cx, fl
     a.H = H; a.W = W; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
     for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host[i];
     a.image = image; a.r0 = crop_r0; a.c0 = crop_c0; a.nr = crop_rows; a.nc = crop_cols;
-    int bits = 1;
-    while ((1ull << bits) < M) ++bits;
-    a.perm.hb = (bits + 1) / 2;
-    if (a.perm.hb < 1) a.perm.hb = 1;
-    a.perm.M = (uint32_t)M;
-    uint32_t c[4] = {0x5e1ec7u, 0u, 0xffffffffu, step};     // round keys: one Philox block per (seed, step)
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    for (int i = 0; i < 4; ++i) a.perm.key[i] = c[i];
+    a.perm = make_perm(M, 0x5e1ec7u, seed, step);     // round keys: one Philox block per (seed, step)
     a.ray_id0 = ray_id0; a.R = R; a.near = near; a.far = far;
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.near_out = near_out; a.far_out = far_out;
     a.target = target; a.pixels = pixels;
     hipLaunchKernelGGL(select_rays_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    PLNERF_CHECK_LAUNCH();
+    return PLNERF_OK;
+}
+
+extern "C" int plnerf_select_bank_rays(int n_views, const int* views, int H, int W, float fx, float fy, float cx, float cy,
+                                       const float* c2w, const float* images, uint64_t seed, uint32_t epoch, int pos0, int R,
+                                       float near, float far, float* rays_o, float* rays_d, float* viewdirs,
+                                       float* near_out, float* far_out, float* target, int* bank_index,
+                                       plnerf_stream_t stream) {
+    if (n_views < 1 || H < 1 || W < 1 || R < 0 || pos0 < 0 || !views || !c2w) return PLNERF_EINVAL;
+    const uint64_t M = (uint64_t)n_views * (uint64_t)H * (uint64_t)W;
+    if (M > (1ull << 30) || (uint64_t)pos0 + (uint64_t)R > M) return PLNERF_ERANGE;     // one epoch's positions only
+    if (R == 0) return PLNERF_OK;
+    if (!rays_o || !rays_d || !near_out || !far_out) return PLNERF_EINVAL;
+    BankArgs a{};
+    a.views = views; a.H = H; a.W = W; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.c2w = c2w; a.images = images;
+    a.perm = make_perm(M, 0xba7c4e5u, seed, epoch);     // round keys: one Philox block per (seed, epoch), not select_rays' domain
+    a.pos0 = pos0; a.R = R; a.near = near; a.far = far;
+    a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.near_out = near_out; a.far_out = far_out;
+    a.target = target; a.bank_index = bank_index;
+    hipLaunchKernelGGL(select_bank_rays_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     PLNERF_CHECK_LAUNCH();
     return PLNERF_OK;
 }

@@ -46,6 +46,18 @@ def shard_rays(n_global, rank, world_size):
     return rank * per, (rank + 1) * per
 
 
+def shard_batch(n_global, rank, world_size):
+    """[begin, end) of this rank's contiguous, balanced share of a global batch of any size (the short last batch of an
+    epoch, train.RayBank): rank r takes n // world + (r < n % world) rays from r * (n // world) + min(r, n % world) on.
+    When world divides n this is shard_rays' split.  A rank may get none (n < world); the caller weights each rank's
+    mean by world * (end - begin) / n so that the averaged gradient is the global batch's (TrainStep.step_batch)."""
+    if n_global < 0 or world_size < 1 or not 0 <= rank < world_size:
+        raise ValueError(f"shard_batch: n {n_global}, rank {rank}, world {world_size}")
+    per, extra = divmod(n_global, world_size)
+    begin = rank * per + min(rank, extra)
+    return begin, begin + per + (rank < extra)
+
+
 class GradientBucket:
     """Gradient averaging across ranks, one collective per network, overlapped with the rest of the backward.
 

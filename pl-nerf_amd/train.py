@@ -7,7 +7,9 @@ optimisers from the FINE learning rate (the reference assigns `new_lrate` to the
 too, line 1315), `constant_init` warm-up (line 1284) -- and adds what the reference does not have:
 ray shards per rank with one bucketed gradient all-reduce (dp.py).  Ray selection happens on the
 device (only the N_rand selected pixels are turned into rays) instead of rebuilding the full
-H x W ray grid and choosing on the host every step (lines 1259, 1275).
+H x W ray grid and choosing on the host every step (lines 1259, 1275).  Both of the reference's ray sources are
+there: one view per step (`TrainStep.step_view`, its no_batching branch) and random rays of all training views
+(`RayBank` + `TrainStep.step_batch`, its default use_batching branch).
 """
 import ctypes
 import os
@@ -102,6 +104,88 @@ def select_view_rays(H, W, K, c2w, image, n_rand, near, far, seed=0, step=0, ray
     return RB.RayColumns(o, d, nr_col, fr_col, vd), target, pix
 
 
+def batch_schedule(step, M, B):
+    """The reference's use_batching walk through its shuffled rays_rgb (run_plnerf.py:1238-1249: take rows
+    i_batch .. i_batch + N_rand, `i_batch += N_rand`, reshuffle and restart at 0 once i_batch >= M) as a pure function of
+    the global step: an epoch has S = ceil(M / B) steps; step g is in epoch g // S and takes positions [p0, p0 + n) of that
+    epoch's order, p0 = (g % S) * B, n = min(B, M - p0) -- the last batch of an epoch is short.  Returns (epoch, p0, n)."""
+    step, M, B = int(step), int(M), int(B)
+    if step < 0 or M < 1 or B < 1:
+        raise ValueError(f"batch_schedule: step {step}, bank size {M}, batch {B}")
+    S = -(-M // B)
+    p0 = (step % S) * B
+    return step // S, p0, min(B, M - p0)
+
+
+class RayBank:
+    """The reference's default ray source (run_plnerf.py:1199-1249, `use_batching`): every pixel of every training view,
+    shuffled once per epoch, consumed N_rand rows per step -- without building rays_rgb.  Bank index
+    b = t * H * W + row * W + col names pixel (row, col) of view i_train[t] (the row order of rays_rgb before its shuffle);
+    epoch e visits the bank in the order of a bijection of [0, M) keyed by (seed, e), and a batch's rays, view directions,
+    near / far columns and targets are built on the device from the bank positions alone (plnerf_select_bank_rays).
+
+    images [N_all, H, W, 3], poses [N_all, 3 or 4, 4], K the intrinsics, i_train the training views, all of one H x W.
+    Converted once, here: images to contiguous fp32 and poses to [N_all, 12] on `device` (default: the current HIP
+    device), i_train to int32 there.  The reference's own shuffle stream (np.random.shuffle, torch.randperm) is not
+    reproduced; the order is a function of (seed, epoch) alone, so a run resumed at step g continues the same walk."""
+
+    def __init__(self, images, poses, K, i_train, near, far, seed=0, device=None):
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        images = torch.as_tensor(images)
+        poses = torch.as_tensor(poses)
+        if images.dim() != 4 or images.shape[-1] != 3 or poses.dim() != 3 or poses.shape[0] != images.shape[0] \
+                or poses.shape[1] < 3 or poses.shape[2] != 4:
+            raise ValueError(f"RayBank: images [N, H, W, 3] and poses [N, 3|4, 4], got {tuple(images.shape)} and "
+                             f"{tuple(poses.shape)}")
+        views = [int(v) for v in np.asarray(torch.as_tensor(i_train).cpu()).reshape(-1)]
+        if not views or min(views) < 0 or max(views) >= images.shape[0]:
+            raise ValueError(f"RayBank: i_train must name views in [0, {images.shape[0]}), got {views}")
+        self.N_all, self.H, self.W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+        self.K = [[float(v) for v in row] for row in K]
+        self.near, self.far, self.seed = float(near), float(far), int(seed)
+        self.device = dev
+        self.images = images.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.poses = poses[:, :3, :4].detach().to(device=dev, dtype=torch.float32).reshape(self.N_all, 12).contiguous()
+        self.i_train = views
+        self.views = torch.tensor(views, dtype=torch.int32, device=dev)
+        self.M = len(views) * self.H * self.W
+
+    def schedule(self, step, B):
+        """(epoch, p0, n) of global step `step` with global batch B (batch_schedule)."""
+        return batch_schedule(step, self.M, B)
+
+    def select(self, epoch, pos0, R, want_viewdirs=True, want_index=False):
+        """Rays of positions pos0 .. pos0 + R - 1 of epoch `epoch`'s order, one launch.
+        Returns (RayColumns, target [R, 3], bank_index [R] int32 or None)."""
+        dev = self.device
+        o, d = torch.empty(R, 3, device=dev), torch.empty(R, 3, device=dev)
+        vd = torch.empty(R, 3, device=dev) if want_viewdirs else None
+        nr_col, fr_col = torch.empty(R, device=dev), torch.empty(R, device=dev)
+        target = torch.empty(R, 3, device=dev)
+        idx = torch.empty(R, device=dev, dtype=torch.int32) if want_index else None
+        K = self.K
+        L.check(L.lib().plnerf_select_bank_rays(
+            len(self.i_train), L.dptr(self.views, "views", torch.int32), self.H, self.W, K[0][0], K[1][1], K[0][2], K[1][2],
+            L.dptr(self.poses, "poses"), L.dptr(self.images, "images"), self.seed, int(epoch), int(pos0), int(R),
+            self.near, self.far, L.dptr(o), L.dptr(d), L.dptr(vd), L.dptr(nr_col), L.dptr(fr_col), L.dptr(target),
+            L.dptr(idx, "bank_index", torch.int32), L.stream()), "plnerf_select_bank_rays")
+        return RB.RayColumns(o, d, nr_col, fr_col, vd), target, idx
+
+    def batch(self, step, n_rand, rank=0, world=1, want_index=False, want_viewdirs=True):
+        """This rank's share of global step `step`'s batch (global batch n_rand * world, split by dp.shard_batch).
+        Returns (RayColumns, target, bank_index or None, offset of the share in the global batch, global batch size n)."""
+        epoch, p0, n = self.schedule(step, int(n_rand) * int(world))
+        begin, end = dp.shard_batch(n, rank, world)
+        cols, target, idx = self.select(epoch, p0 + begin, end - begin, want_viewdirs, want_index)
+        return cols, target, idx, begin, n
+
+    @staticmethod
+    def decode(bank_index, H, W):
+        """bank index -> (t, row, col): t indexes i_train."""
+        b = bank_index.long()
+        return b // (H * W), (b % (H * W)) // W, b % W
+
+
 def merged_backward_ok(tape, nets):
     """Can this step's two network backwards run as one launch sequence (backward_merged)?  One MlpFn forward per
     network (the batch fitted one launch each), coarse first, both networks native (NeRF.is_native), in one 16-bit
@@ -187,6 +271,7 @@ class TrainStep:
         # the environment switches it off (A/B measurements).
         self.merged_backward = os.environ.get("PLNERF_MERGED_BWD", "1") != "0"
         self.merged_steps = 0      # steps that took the merged backward (the rest went through torch.autograd.backward)
+        self.last_batch = None     # step_batch: (epoch, first bank position, rays, offset in the global batch, global n)
         self.bucket = None
         if distributed and self.world > 1:
             # replicas must start from the same weights (create_nerf initialises from each process's own RNG, and a
@@ -212,6 +297,34 @@ class TrainStep:
                                            step=self.global_step, ray_id0=self.rank * n_rand, precrop=precrop,
                                            want_viewdirs=bool(self.kw.get("use_viewdirs", True)))
         return self._step(H, W, K, cols, target, near, far)
+
+    def step_batch(self, bank, n_rand=None, precrop=None):
+        """The loop body of the reference's use_batching branch (run_plnerf.py:1238-1316) for `bank` (a RayBank): this
+        rank's share of global step `global_step`'s batch of n_rand * world bank rays (batch_schedule; dp.shard_batch),
+        then the optimisation step.  Draws are keyed on the ray's position in the global batch, and each rank weights its
+        image-loss gradients by world * n_r / n: the averaged update is that of one process stepping the whole batch, the
+        short last batch of an epoch included.  A rank left without rays (a tail shorter than world) renders one stand-in
+        ray at weight 0 -- an exactly zero gradient through the same collective and guarded Adam step -- and returns NaN
+        loss and psnr.  The batching branch never crops: `precrop` is refused."""
+        if precrop is not None:
+            raise ValueError("step_batch: the batching branch has no precrop (run_plnerf.py:1199-1249); use step_view")
+        n_rand = int(n_rand if n_rand is not None else self.args.N_rand)
+        want_vd = bool(self.kw.get("use_viewdirs", True))
+        epoch, p0, n = bank.schedule(self.global_step, n_rand * self.world)
+        begin, end = dp.shard_batch(n, self.rank, self.world)
+        self.last_batch = (epoch, p0 + begin, end - begin, begin, n)      # (epoch, first position, rays, offset, global n)
+        if end > begin:
+            cols, target, _ = bank.select(epoch, p0 + begin, end - begin, want_vd)
+            scale = self.world * (end - begin) / n
+        else:
+            cols, target, _ = bank.select(epoch, p0, 1, want_vd)
+            scale = 0.0
+        loss, psnr = self._step(bank.H, bank.W, bank.K, cols, target, bank.near, bank.far, ray_id0=begin,
+                                loss_scale=scale)
+        if end == begin:
+            nan = torch.full((), float("nan"), device=loss.device)
+            return nan, nan.clone()
+        return loss, psnr
 
     def __call__(self, H, W, K, batch_rays, target_s, near=0., far=1.):
         return self._step(H, W, K, batch_rays, target_s, near, far)
@@ -252,12 +365,15 @@ class TrainStep:
             tails = self.bucket.tails(nets)
             opt.step(grad_scale=scale, guards=tails if len(tails) == len(nets) else None)
 
-    def _step(self, H, W, K, rays, target_s, near, far):
+    def _step(self, H, W, K, rays, target_s, near, far, ray_id0=None, loss_scale=None):
+        """`ray_id0`: the global id of the first ray (default rank * rays); `loss_scale`: a factor on the image-loss
+        gradients (step_batch's world * n_r / n; None or 1 = none)."""
         i = self.global_step + 1                      # the reference iterates i = start+1 .. N_iters
         n_local = rays.shape[0] if isinstance(rays, RB.RayColumns) else rays[0].reshape(-1, 3).shape[0]
         prev = Fn.DRAWS
         if self.draws is not None:
-            self.draws.step, self.draws.ray_id0 = self.global_step, self.rank * n_local
+            self.draws.step = self.global_step
+            self.draws.ray_id0 = self.rank * n_local if ray_id0 is None else int(ray_id0)
             Fn.set_draw_source(self.draws)
         tape = Fn.MlpTape() if self.merged_backward else None
         Fn.MLP_TAPE = tape
@@ -274,6 +390,9 @@ class TrainStep:
             # backward((rgb, rgb0), (d loss / d rgb, d loss / d rgb0)) is loss.backward()
             loss4, g_rgb, g_rgb0 = Fn.image_loss_and_grads(rgb, rgb0, target_s)
             loss, psnr = loss4[0], loss4[3]
+            if loss_scale is not None and loss_scale != 1.0:
+                g_rgb = g_rgb * loss_scale
+                g_rgb0 = None if g_rgb0 is None else g_rgb0 * loss_scale
             if tape is not None and rgb0 is not None and merged_backward_ok(tape, self.nets):
                 backward_merged(tape, self.nets, (rgb, rgb0), (g_rgb, g_rgb0), self.bucket)
                 self.merged_steps += 1
@@ -284,7 +403,7 @@ class TrainStep:
             img_loss = img2mse(rgb, target_s)
             loss = img_loss if rgb0 is None else img_loss + img2mse(rgb0, target_s)
             psnr = mse2psnr(img_loss.detach())
-            loss.backward()
+            (loss if loss_scale is None or loss_scale == 1.0 else loss * loss_scale).backward()
         # (fine optimizer first, as the reference does; with ONE network both optimizers step the same weights, :438-447)
         self._exchange_and_step([self.optimizer, self.optimizer_coarse], self.nets, [self.nets, self.nets[:1]])
         new_lrate = self.learning_rate()
