@@ -92,6 +92,20 @@ BATCHING_SIGNATURES = {
                                 c_i, c_i, ctypes.c_float, ctypes.c_float] + [c_f] * 7 + [c_s]),
 }
 
+# ... and include/plnerf_hip_eval.h (ABI 601): held-out view metrics
+EVAL_SIGNATURES = {
+    "plnerf_eval_metrics": (c_i, [c_i] * 3 + [c_f] * 8 + [c_s]),
+}
+EVAL_ROW = 5                               # PLNERF_EVAL_ROW: fp64 values per frame, columns PLNERF_EVAL_*
+EVAL_SSE_RGB, EVAL_SSE_RGB0, EVAL_SSIM, EVAL_DEPTH_SSE, EVAL_DEPTH_COUNT = range(EVAL_ROW)
+EVAL_TILE_H, EVAL_TILE_W = 32, 64          # PLNERF_EVAL_TILE_H / _W
+
+
+def eval_workspace_bytes(n, H, W):
+    """PLNERF_EVAL_WORKSPACE_BYTES(n, H, W)."""
+    return n * -(-H // EVAL_TILE_H) * -(-W // EVAL_TILE_W) * EVAL_ROW * 8
+
+
 _lib = None
 
 
@@ -106,7 +120,7 @@ def lib():
                 "plnerf_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

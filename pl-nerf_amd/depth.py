@@ -22,6 +22,7 @@ import torch
 from . import _lib as L
 from . import functional as Fn
 from . import raybatch as RB
+from .evaluate import _score_views
 from .nerf import Embedder, NeRF
 from .optim import FlatAdam
 from .render import (MAX_ROWS_PER_LAUNCH, _draw_noise, _refuse_unsupported, _rgb_sigma, batchify, raw2outputs as _raw2outputs, sample_pdf,
@@ -430,6 +431,27 @@ def render(H, W, intrinsic, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near
 
 
 render_hyp = render
+
+
+def render_images_with_metrics(count, indices, images, depths, valid_depths, poses, H, W, intrinsics, lpips_alex, args,
+                               render_kwargs_test, embedcam_fn=None, with_test_time_optimization=False, *,
+                               keep_images=True):
+    """run_nerf_sample_based_depth.py:424-510: evaluate.render_images_with_metrics on this variant's render, with the
+    per-view intrinsics[i] = (fx, fy, cx, cy) and the sensor depths[i] [H,W,1] / valid_depths[i] [H,W] of every view.
+    With args.input_ch_cam > 0 the camera code is embedcam_fn(i), or zeros when embedcam_fn is None (set in
+    render_kwargs_test["embedded_cam"], as there).  with_test_time_optimization (the per-view optimisation of that code)
+    is not provided: it raises."""
+    if with_test_time_optimization:
+        raise NotImplementedError("with_test_time_optimization: the per-view camera-code optimisation is not provided")
+    dev = RB.default_device()
+
+    def set_camera_code(img_idx):
+        if getattr(args, "input_ch_cam", 0) > 0:
+            render_kwargs_test["embedded_cam"] = (torch.zeros((args.input_ch_cam,), device=dev) if embedcam_fn is None
+                                                  else embedcam_fn(torch.tensor(img_idx, device=dev)))
+    return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
+                        render_kwargs_test, render, lambda img_idx: intrinsics[img_idx, :], True, set_camera_code,
+                        keep_images)
 
 
 class _SpaceCarvingFn(torch.autograd.Function):

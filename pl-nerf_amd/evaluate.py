@@ -1,0 +1,232 @@
+"""Held-out view evaluation: run_plnerf.py:284-363 (render_images_with_metrics) with the evaluation utilities of
+run_nerf_helpers.py:537-570 (compute_rmse, MeanTracker).
+
+A frame's metrics -- img2mse and PSNR of rgb and rgb0, SSIM of the clamped frame, depth RMSE over the valid pixels --
+come from one launch of plnerf_eval_metrics (csrc/metrics.hip) on the frame where it already is, in HBM.  The reference
+copies the frame to the host and runs skimage's SSIM on the CPU; here each frame's fp64 row stays on the device until
+the loop ends and is read back once.  LPIPS is a network the caller supplies (`lpips_alex`), as in the reference; this
+package ships no LPIPS weights.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import raybatch as RB
+from .nerf import NeRF
+from .render import render
+
+
+def compute_rmse(prediction, target):
+    """run_nerf_helpers.py:537: root mean square difference; NaN for empty inputs (the mean of nothing)."""
+    return torch.sqrt(torch.mean((prediction - target) ** 2))
+
+
+class MeanTracker:
+    """run_nerf_helpers.py:540-570: running means of named values.  One total weight serves every key, so a key that
+    skips an add is averaged as the reference averages it; the update is the reference's, (m * w + l) / (w + weight)."""
+
+    def __init__(self):
+        self.reset()
+
+    def add(self, input, weight=1.):
+        for key, value in input.items():
+            previous = self.mean_dict.get(key, 0)
+            self.mean_dict[key] = (previous * self.total_weight + value) / (self.total_weight + weight)
+        self.total_weight += weight
+
+    def has(self, key):
+        return key in self.mean_dict
+
+    def get(self, key):
+        return self.mean_dict[key]
+
+    def as_dict(self):
+        return self.mean_dict
+
+    def reset(self):
+        self.mean_dict = dict()
+        self.total_weight = 0
+
+    def print(self, f=None):
+        for key, value in self.mean_dict.items():
+            print("{}: {}".format(key, value), file=f)
+
+
+def _psnr(mse):
+    """mse2psnr on a Python float: -10 log10(mse); inf for 0, as torch gives."""
+    if mse == 0:
+        return math.inf
+    return -10. * math.log(mse) / math.log(10.) if mse > 0 else math.nan
+
+
+def metric_rows(rgb, target, rgb0=None, depth=None, target_depth=None, valid=None, out=None, workspace=None):
+    """The [n, EVAL_ROW] fp64 device rows of plnerf_eval_metrics (columns _lib.EVAL_*) for frames rgb, target (and rgb0)
+    [n,H,W,3] or [H,W,3] fp32, depth / target_depth [n,H,W] or [H,W] fp32 and valid of that shape (bool or uint8) --
+    the depth three together or not at all.  One launch; nothing is synchronised.  `out` and `workspace`
+    (_lib.eval_workspace_bytes uint8) may be given to reuse buffers."""
+    lead = rgb.shape[:-3]
+    if rgb.dim() not in (3, 4) or rgb.shape[-1] != 3:
+        raise ValueError(f"rgb must be [H,W,3] or [n,H,W,3], got {tuple(rgb.shape)}")
+    for name, t in (("target", target), ("rgb0", rgb0)):
+        if t is not None and t.shape != rgb.shape:
+            raise ValueError(f"{name} {tuple(t.shape)} does not match rgb {tuple(rgb.shape)}")
+    given = [t is not None for t in (depth, target_depth, valid)]
+    if any(given) and not all(given):
+        raise ValueError("depth, target_depth and valid go together")
+    if all(given):
+        for name, t in (("depth", depth), ("target_depth", target_depth), ("valid", valid)):
+            if t.shape != rgb.shape[:-1]:
+                raise ValueError(f"{name} {tuple(t.shape)} does not match rgb's pixels {tuple(rgb.shape[:-1])}")
+        valid = valid.contiguous()
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+    n = int(np.prod(lead)) if len(lead) else 1
+    H, W = rgb.shape[-3], rgb.shape[-2]
+    if out is None:
+        out = torch.empty(n, L.EVAL_ROW, dtype=torch.float64, device=rgb.device)
+    if workspace is None:
+        workspace = torch.empty(L.eval_workspace_bytes(n, H, W), dtype=torch.uint8, device=rgb.device)
+    if out.shape != (n, L.EVAL_ROW) or workspace.numel() < L.eval_workspace_bytes(n, H, W):
+        raise ValueError("out must be [n, EVAL_ROW] and workspace at least eval_workspace_bytes(n, H, W)")
+    L.check(L.lib().plnerf_eval_metrics(
+        n, H, W, L.dptr(rgb, "rgb"), L.dptr(target, "target"), L.dptr(rgb0, "rgb0"), L.dptr(depth, "depth"),
+        L.dptr(target_depth, "target_depth"), L.dptr(valid, "valid", torch.uint8), L.dptr(workspace, "workspace", torch.uint8),
+        L.dptr(out, "out", torch.float64), L.stream()), "plnerf_eval_metrics")
+    return out
+
+
+def row_metrics(row, H, W, with_rgb0):
+    """One host row -> {img_loss, psnr, ssim[, img_loss0, psnr0][, depth_rmse]}; depth_rmse is left out when it is NaN
+    (no valid pixel), as the reference drops it."""
+    mse = float(row[L.EVAL_SSE_RGB]) / (3 * H * W)
+    m = {"img_loss": mse, "psnr": _psnr(mse), "ssim": float(row[L.EVAL_SSIM])}
+    if with_rgb0:
+        mse0 = float(row[L.EVAL_SSE_RGB0]) / (3 * H * W)
+        m.update({"img_loss0": mse0, "psnr0": _psnr(mse0)})
+    count = float(row[L.EVAL_DEPTH_COUNT])
+    rmse = math.sqrt(float(row[L.EVAL_DEPTH_SSE]) / count) if count > 0 else math.nan
+    if not math.isnan(rmse):
+        m["depth_rmse"] = rmse
+    return m
+
+
+def image_metrics(rgb, target, rgb0=None, depth=None, target_depth=None, valid=None):
+    """Metrics of one frame ([H,W,3] device tensors: a dict) or of a batch ([n,H,W,3]: a list of dicts), one kernel
+    launch: img_loss (mean square error of the UNCLAMPED rgb, as img2mse before the clamp), psnr, ssim (skimage's
+    structural_similarity of clamp(rgb, 0, 1) and target, data_range 1, 7x7 box windows), img_loss0 / psnr0 with rgb0,
+    depth_rmse over the valid pixels when there is one."""
+    rows = metric_rows(rgb, target, rgb0, depth, target_depth, valid).cpu().numpy()
+    H, W = rgb.shape[-3], rgb.shape[-2]
+    out = [row_metrics(r, H, W, rgb0 is not None) for r in rows]
+    return out[0] if rgb.dim() == 3 else out
+
+
+def _on_device(x, device, dtype=torch.float32):
+    return torch.as_tensor(x).to(device=device, dtype=dtype).contiguous()
+
+
+def _check_range(render_kwargs):
+    for net in (render_kwargs.get('network_fn'), render_kwargs.get('network_fine')):
+        if isinstance(net, NeRF) and net.precision in L.GUARDED_PRECISIONS and net.is_supported():
+            net.check_range()       # a clamped frame must not be scored silently
+
+
+def _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, chunk, render_kwargs_test,
+                 render_fn, intrinsic_of, with_depth, before_frame, keep_images):
+    """The loop of render_images_with_metrics (run_plnerf.py:284-363; run_nerf_sample_based_depth.py:424-510)."""
+    far = render_kwargs_test['far']
+    if count is None:
+        count, img_i = len(indices), indices
+    else:
+        count = min(count, len(indices))
+        img_i = np.random.choice(indices, size=count, replace=False)
+    dev = RB.default_device()
+
+    rows = torch.empty(count, L.EVAL_ROW, dtype=torch.float64, device=dev)
+    workspace = torch.empty(L.eval_workspace_bytes(1, H, W), dtype=torch.uint8, device=dev)
+    lpips_vals = torch.empty(count, dtype=torch.float64, device=dev) if lpips_alex is not None else None
+    if keep_images:
+        rgbs_res = torch.empty(count, 3, H, W)
+        rgbs0_res = torch.empty(count, 3, H, W)
+        target_rgbs_res = torch.empty(count, 3, H, W)
+        depths_res = torch.empty(count, 1, H, W)
+        depths0_res = torch.empty(count, 1, H, W)
+        target_depths_res = torch.empty(count, 1, H, W)
+        target_valid_depths_res = torch.empty(count, 1, H, W, dtype=bool)
+    extras = {}
+    with torch.no_grad():
+        for n, img_idx in enumerate(img_i):
+            before_frame(img_idx)
+            target = _on_device(images[img_idx], dev)
+            rgb, _, _, extras = render_fn(H, W, intrinsic_of(img_idx), chunk=chunk, c2w=poses[img_idx, :3, :4],
+                                          **render_kwargs_test)
+            rgb0 = extras.get('rgb0')
+            depth_args = ()
+            if with_depth:
+                target_depth = _on_device(depths[img_idx], dev)[:, :, 0].contiguous()
+                target_valid = torch.as_tensor(valid_depths[img_idx]).to(device=dev, dtype=torch.bool).contiguous()
+                depth_args = (extras['depth_map'].contiguous(), target_depth, target_valid)
+            metric_rows(rgb.contiguous(), target, None if rgb0 is None else rgb0.contiguous(), *depth_args,
+                        out=rows[n:n + 1], workspace=workspace)
+            if lpips_alex is not None:
+                lpips = lpips_alex(rgb.clamp(0, 1).permute(2, 0, 1).unsqueeze(0), target.permute(2, 0, 1).unsqueeze(0),
+                                   normalize=True)[0]
+                lpips_vals[n] = torch.as_tensor(lpips[0, 0, 0])
+            if keep_images:
+                rgbs_res[n] = rgb.clamp(0., 1.).permute(2, 0, 1).cpu()
+                target_rgbs_res[n] = target.permute(2, 0, 1).cpu()
+                depths_res[n] = (extras['depth_map'] / far).unsqueeze(0).cpu()
+                if with_depth:
+                    target_depths_res[n] = (target_depth / far).unsqueeze(0).cpu()
+                    target_valid_depths_res[n] = target_valid.unsqueeze(0).cpu()
+                else:
+                    target_depths_res[n] = 0.
+                    target_valid_depths_res[n] = False
+                if rgb0 is not None:
+                    depths0_res[n] = (extras['depth0'] / far).unsqueeze(0).cpu()
+                    rgbs0_res[n] = rgb0.clamp(0, 1).permute(2, 0, 1).cpu()
+    _check_range(render_kwargs_test)
+
+    host_rows = rows.cpu().numpy()
+    host_lpips = lpips_vals.cpu().tolist() if lpips_vals is not None else None
+    mean_metrics, mean_depth_metrics = MeanTracker(), MeanTracker()
+    with_rgb0 = 'rgb0' in extras
+    for n in range(count):
+        frame = row_metrics(host_rows[n], H, W, with_rgb0)
+        metrics = {"img_loss": frame["img_loss"], "psnr": frame["psnr"], "ssim": frame["ssim"]}
+        if host_lpips is not None:
+            metrics["lpips"] = host_lpips[n]
+        if with_rgb0:
+            metrics.update({"img_loss0": frame["img_loss0"], "psnr0": frame["psnr0"]})
+        if "depth_rmse" in frame:
+            mean_depth_metrics.add({"depth_rmse": frame["depth_rmse"]})
+        mean_metrics.add(metrics)
+
+    res = None
+    if keep_images:
+        res = {"rgbs": rgbs_res, "target_rgbs": target_rgbs_res, "depths": depths_res, "target_depths": target_depths_res,
+               "target_valid_depths": target_valid_depths_res}
+        if with_rgb0:
+            res.update({"rgbs0": rgbs0_res, "depths0": depths0_res})
+    all_mean_metrics = MeanTracker()
+    all_mean_metrics.add({**mean_metrics.as_dict(), **mean_depth_metrics.as_dict()})
+    return all_mean_metrics, res
+
+
+def render_images_with_metrics(count, indices, images, depths, valid_depths, poses, H, W, K, lpips_alex, args,
+                               render_kwargs_test, embedcam_fn=None, with_test_time_optimization=False, *,
+                               keep_images=True):
+    """run_plnerf.py:284-363: renders `count` views of `indices` (all of them in order for None, else
+    np.random.choice(indices, count, replace=False)) and returns (MeanTracker of img_loss, psnr, ssim[, lpips]
+    [, img_loss0, psnr0][, depth_rmse], res).  res holds CPU [count,3,H,W] / [count,1,H,W] tensors as the reference
+    builds them (frames clamped, depths divided by far; rgbs0 / depths0 when the renders carry rgb0).  Depths are scored
+    for args.dataset == "scannet" only, from depths[i] [H,W,1] and valid_depths[i] [H,W], as there.
+
+    lpips_alex: a callable called as the reference calls it (clamped frame and target, [1,3,H,W], normalize=True), its
+    [0][0,0,0] recorded as "lpips"; None leaves "lpips" out.  embedcam_fn and with_test_time_optimization are accepted
+    and unused, as in the reference.  keep_images=False (extension) skips res (None is returned for it), and with it
+    every per-frame copy to the host: the metric rows are read back once, after the last frame."""
+    with_depth = args.dataset == "scannet"
+    return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
+                        render_kwargs_test, render, lambda img_idx: K, with_depth, lambda img_idx: None, keep_images)
