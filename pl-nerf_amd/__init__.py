@@ -15,6 +15,7 @@ from .raybatch import RayColumns
 from .functional import DrawSource, set_draw_source
 from .evaluate import MeanTracker, compute_rmse, image_metrics, metric_rows, render_images_with_metrics
 from . import depth   # depth-supervised variant of the path (depth_supervised_exps/)
+from .depth import DepthTrainStep, DepthViews
 from .render import (batchify, batchify_rays, compute_weights, compute_weights_piecewise_linear, create_nerf,
                      raw2outputs, render, render_path, render_rays, run_network, sample_pdf,
                      sample_pdf_reformulation)
@@ -35,4 +36,5 @@ __all__ = [
     "render_rays", "run_network", "sample_pdf", "sample_pdf_reformulation", "img2mse", "library_path",
     "library_version", "depth", "FlatAdam", "TrainStep", "save_checkpoint", "checkpoint_path", "select_rays", "select_view_rays", "RayBank", "batch_schedule", "RayColumns", "DrawSource",
     "set_draw_source", "MeanTracker", "compute_rmse", "image_metrics", "metric_rows", "render_images_with_metrics",
+    "DepthViews", "DepthTrainStep",
 ]

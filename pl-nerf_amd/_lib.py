@@ -105,6 +105,15 @@ def eval_workspace_bytes(n, H, W):
     """PLNERF_EVAL_WORKSPACE_BYTES(n, H, W)."""
     return n * -(-H // EVAL_TILE_H) * -(-W // EVAL_TILE_W) * EVAL_ROW * 8
 
+# ... and include/plnerf_hip_depthfeed.h (ABI 601): the depth-supervised loop's data feed and depth scale / shift gradient
+DEPTHFEED_SIGNATURES = {
+    "plnerf_select_depth_rays": (c_i, [c_i] * 5 + [c_f] * 4 + [c_i] + [c_f] * 3 + [ctypes.c_float] * 2 +
+                                 [ctypes.c_uint64, ctypes.c_uint32, c_i, c_i] + [c_f] * 10 + [c_s]),
+    "plnerf_depth_scale_shift_grad": (c_i, [c_f] * 4 + [c_i] * 5 + [c_f] + [ctypes.c_float] * 2 + [c_i] * 2 + [c_f] * 3 +
+                                      [c_s]),
+}
+DEPTH_SS_WORKSPACE_BYTES = 4096        # PLNERF_DEPTH_SS_WORKSPACE_BYTES
+
 
 _lib = None
 
@@ -120,7 +129,8 @@ def lib():
                 "plnerf_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
+                list(DEPTHFEED_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

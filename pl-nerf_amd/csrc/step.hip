@@ -25,6 +25,7 @@
 // reference's order.
 #include "common.h"
 #include "philox.h"
+#include "pixel_select.h"
 #include "../../include/plnerf_hip_batching.h"
 
 using namespace plnerf;
@@ -71,46 +72,6 @@ __global__ __launch_bounds__(256) void normal_kernel(const RngArgs g, const int 
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (4 * b + k < n) row[k] = z[k];
-}
-
-// ---- pixel choice: a keyed bijection of [0, M) (4-round Feistel network on 2 hb bits, cycle-walked into the
-// domain), evaluated at the global ray ids: distinct ids -> distinct pixels, i.e. a draw WITHOUT replacement like the
-// reference's np.random.choice(..., replace=False), with no H x W permutation to build.
-struct PixelPerm {
-    uint32_t key[4];
-    uint32_t M;
-    int hb;
-};
-
-__device__ __forceinline__ uint32_t mix32(uint32_t h) {
-    h *= 0x9E3779B1u; h ^= h >> 15; h *= 0x85EBCA77u; h ^= h >> 13; h *= 0xC2B2AE3Du; h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ uint32_t perm_index(const PixelPerm& p, uint32_t x) {
-    const uint32_t mask = (1u << p.hb) - 1u;
-    do {
-        uint32_t L = x >> p.hb, Rr = x & mask;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t F = mix32(Rr + p.key[r]) & mask;
-            const uint32_t nl = Rr;
-            Rr = L ^ F;
-            L = nl;
-        }
-        x = (L << p.hb) | Rr;
-    } while (x >= p.M);
-    return x;
-}
-
-// pixel (row, col) -> camera ray direction d and |d| (run_nerf_helpers.py:166-169):
-// dirs = ((i - cx) / fx, -(j - cy) / fy, -1);  rays_d[k] = sum_j dirs[j] * c2w[k][j], summed left to right as torch does
-__device__ __forceinline__ float pixel_ray(const int row, const int col, const float fx, const float fy, const float cx,
-                                           const float cy, const float* c2w, float d[3]) {
-    const float d0 = ((float)col - cx) / fx, d1 = -((float)row - cy) / fy, d2 = -1.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d[k] = (d0 * c2w[4 * k + 0] + d1 * c2w[4 * k + 1]) + d2 * c2w[4 * k + 2];
-    return sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
 }
 
 struct SelectArgs {
@@ -600,21 +561,6 @@ extern "C" int plnerf_normal(uint64_t seed, uint32_t stream_id, uint32_t step, i
                        out);
     PLNERF_CHECK_LAUNCH();
     return PLNERF_OK;
-}
-
-// the keyed bijection of [0, M) (M <= 2^30): 2 hb >= log2 M bits, round keys from one Philox block on (seed, ctr)
-// under a per-use domain constant
-static PixelPerm make_perm(uint64_t M, uint32_t domain, uint64_t seed, uint32_t ctr) {
-    PixelPerm p{};
-    int bits = 1;
-    while ((1ull << bits) < M) ++bits;
-    p.hb = (bits + 1) / 2;
-    if (p.hb < 1) p.hb = 1;
-    p.M = (uint32_t)M;
-    uint32_t c[4] = {domain, 0u, 0xffffffffu, ctr};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    for (int i = 0; i < 4; ++i) p.key[i] = c[i];
-    return p;
 }
 
 extern "C" int plnerf_select_rays(int H, int W, float fx, float fy, float cx, float cy, const float* c2w_host,

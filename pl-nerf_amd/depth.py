@@ -544,20 +544,135 @@ def create_nerf(args, scene_render_params=None, device=None):
     return render_kwargs_train, RB.test_time_kwargs(render_kwargs_train, perturb=False), start, grad_vars, optimizer
 
 
+class DepthViews:
+    """The training views of the depth-supervised loop, resident on the device (run_nerf_sample_based_depth.py:1043-1068),
+    and their per-step ray batch (plnerf_select_depth_rays): what get_ray_batch_from_one_image_hypothesis_idx (:960-1001)
+    and :1111-1120 compute on the host from the full H x W ray grid, in one launch for the step's rays alone.
+
+    images [V, H, W, 3]; poses [V, 3 or 4, 4] (camera to world); intrinsics [V, 4] = (fx, fy, cx, cy) per view;
+    hypotheses [V, n_hyp, H, W] (a trailing axis of one allowed: the reference's [V, n_hyp, H, W, 1]; the gt-depth
+    override of :1066-1068 is n_hyp = 1); valid: the space-carving mask, V * H * W values in any shape (gt_valid_depths
+    [V, 1, H, W, 1] there), non-zero = valid, or None (every pixel); near, far: the ray bounds."""
+
+    def __init__(self, images, poses, intrinsics, hypotheses, valid, near, far, device=None):
+        dev = RB.default_device(device if device is not None else
+                                (images.device if isinstance(images, torch.Tensor) and images.is_cuda else None))
+        f32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
+        self.images = f32(images)
+        if self.images.dim() != 4 or self.images.shape[-1] != 3:
+            raise ValueError(f"images must be [V, H, W, 3], got {tuple(self.images.shape)}")
+        V, H, W = self.images.shape[:3]
+        self.poses = f32(poses)
+        if self.poses.dim() != 3 or self.poses.shape[0] != V or self.poses.shape[1] not in (3, 4) or self.poses.shape[2] != 4:
+            raise ValueError(f"poses must be [V, 3 or 4, 4], got {tuple(self.poses.shape)}")
+        self.intrinsics = f32(intrinsics).reshape(V, -1)
+        if self.intrinsics.shape[1] != 4:
+            raise ValueError(f"intrinsics must be [V, 4] = (fx, fy, cx, cy), got {tuple(self.intrinsics.shape)}")
+        hyp = f32(hypotheses)
+        if hyp.dim() == 5 and hyp.shape[-1] == 1:
+            hyp = hyp[..., 0]
+        if hyp.dim() != 4 or hyp.shape[0] != V or tuple(hyp.shape[2:]) != (H, W):
+            raise ValueError(f"hypotheses must be [V, n_hyp, H, W], got {tuple(torch.as_tensor(hypotheses).shape)}")
+        self.hypotheses = hyp.contiguous()
+        self.valid = None
+        if valid is not None:
+            v = torch.as_tensor(valid).to(dev)
+            if v.numel() != V * H * W:
+                raise ValueError(f"valid must hold V * H * W = {V * H * W} values, got {tuple(v.shape)}")
+            self.valid = (v.reshape(V, H, W) != 0).to(torch.uint8).contiguous()
+        self.n_views, self.H, self.W, self.n_hyp = V, H, W, hyp.shape[1]
+        self.near, self.far, self.device = float(near), float(far), dev
+
+    def select(self, view, step, R, ray_id0=0, scale=None, shift=None, seed=0, want_viewdirs=True, want_extras=False):
+        """Rays ray_id0 .. ray_id0 + R - 1 of step `step`'s pixel sample of view `view` (a host integer: the reference's
+        img_i), drawn without replacement by the keyed bijection of plnerf_select_rays (seed, step): distinct within the
+        step, disjoint across ranks with disjoint id ranges.  scale, shift: the per-view DEPTH_SCALES / DEPTH_SHIFTS
+        ([V] or [V, 1] fp32 on the device, read there), or None (1 and 0).
+        Returns (RayColumns, target_s [R, 3], target_h [n_hyp, R, 1] = hyp * scale[view] + shift[view], mask [R] 0. / 1.);
+        want_extras: also (hyp_raw [n_hyp, R, 1], pixels [R, 2] int32 (row, col))."""
+        dev, R = self.device, int(R)
+        o, d = torch.empty(R, 3, device=dev), torch.empty(R, 3, device=dev)
+        vd = torch.empty(R, 3, device=dev) if want_viewdirs else None
+        nr, fr = torch.empty(R, device=dev), torch.empty(R, device=dev)
+        target = torch.empty(R, 3, device=dev)
+        th, mask = torch.empty(self.n_hyp, R, 1, device=dev), torch.empty(R, device=dev)
+        raw = torch.empty(self.n_hyp, R, 1, device=dev) if want_extras else None
+        pix = torch.empty(R, 2, device=dev, dtype=torch.int32) if want_extras else None
+        for name, t in (("scale", scale), ("shift", shift)):
+            if t is not None and t.numel() != self.n_views:
+                raise ValueError(f"{name} must hold one value per view ({self.n_views}), got {tuple(t.shape)}")
+        L.check(L.lib().plnerf_select_depth_rays(
+            self.n_views, int(view), self.H, self.W, self.n_hyp, L.dptr(self.images, "images"),
+            L.dptr(self.hypotheses, "hypotheses"), L.dptr(self.valid, "valid", torch.uint8), L.dptr(self.poses, "poses"), self.poses.shape[1],
+            L.dptr(self.intrinsics, "intrinsics"), L.dptr(None if scale is None else scale.detach(), "scale"),
+            L.dptr(None if shift is None else shift.detach(), "shift"), self.near, self.far, int(seed), int(step),
+            int(ray_id0), R, L.dptr(o), L.dptr(d), L.dptr(vd), L.dptr(nr), L.dptr(fr), L.dptr(target), L.dptr(th),
+            L.dptr(mask), L.dptr(raw), L.dptr(pix, "pixels", torch.int32), L.stream()), "plnerf_select_depth_rays")
+        cols = RB.RayColumns(o, d, nr, fr, vd)
+        if want_extras:
+            return cols, target, th, mask, raw, pix
+        return cols, target, th, mask
+
+
+def learning_rate(i, lrate, start_decay_lrate=400000, end_decay_lrate=500000):
+    """The depth script's learning rate at iteration i (run_nerf_sample_based_depth.py:1105-1108):
+    lrate * 0.1^((i - start) / (end - start)) for start < i <= end; None outside that window, where the loop leaves the
+    optimizer's rate as it was (after the window: the last value written, lrate / 10)."""
+    if i > start_decay_lrate and i <= end_decay_lrate:
+        portion = (i - start_decay_lrate) / (end_decay_lrate - start_decay_lrate)
+        return lrate * (0.1 ** portion)
+    return None
+
+
+def scaleshift_steps(i, warm_start_nerf, freeze_ss, space_carving_weight):
+    """Whether iteration i steps the depth scale / shift Adam (:1142, 1159-1161): only the space-carving term reaches
+    them, so before it first switches on (i > warm_start_nerf) their gradients are None and Adam skips them; from then on
+    the term is on at every iteration and optimizer_ss steps while i < freeze_ss."""
+    return space_carving_weight > 0. and i > warm_start_nerf and i < freeze_ss
+
+
+def save_checkpoint(path, global_step, network_fn, network_fine, optimizer, depth_scales=None, depth_shifts=None):
+    """The depth script's checkpoint dict (run_nerf_sample_based_depth.py:1168-1183): global_step, both networks, the one
+    optimizer, and the per-view depth_scales / depth_shifts ([V, 1] fp32).  create_nerf's reload restores the step
+    counter, the networks and the optimizer; like the reference it does NOT reload the scales and shifts (train_nerf
+    re-initialises them from scale_init / shift_init): a resumed run that needs them reads the two keys itself."""
+    d = {'global_step': global_step,
+         'network_fn_state_dict': network_fn.state_dict(),
+         'optimizer_state_dict': optimizer.state_dict()}
+    if network_fine is not None:
+        d['network_fine_state_dict'] = network_fine.state_dict()
+    if depth_shifts is not None:
+        d['depth_shifts'] = depth_shifts.detach().reshape(-1, 1).float().clone()
+    if depth_scales is not None:
+        d['depth_scales'] = depth_scales.detach().reshape(-1, 1).float().clone()
+    torch.save(d, path)
+
+
 class DepthTrainStep:
     """One iteration of the reference's depth-supervised loop (run_nerf_sample_based_depth.py:1126-1157):
     loss = mse(rgb) + space_carving_weight * space_carving(pred_hyp, target_h) + mse(rgb0); backward;
-    clip_grad_value_(0.1); Adam.  `ray_batch` is the packed [R, 11] batch render_rays takes."""
+    clip_grad_value_(0.1); Adam.  `ray_batch` is the packed [R, 11] batch render_rays takes.
+
+    step_view is the whole loop body from the view on (:1104-1161): learning-rate schedule, the step's rays of a
+    DepthViews view, this call, and the per-view depth scale / shift Adam.  The iteration counter is the reference's
+    i = start + 1, start + 2, ...: it keys the pixel sample and the draws, the schedule, warm_start_nerf and freeze_ss."""
 
     def __init__(self, args, render_kwargs_train, optimizer, grad_vars, distributed=None, range_check_every=100, seed=0,
-                 counter_rng=True):
+                 counter_rng=True, start=0, n_views=None):
         """counter_rng: the step's draws (stratified jitter, importance samples, the hypotheses' u) come from a
         functional.DrawSource keyed on (seed, step, GLOBAL ray id) and are generated inside the kernels that consume
         them -- a global batch gives the same step whether one rank renders it or N ranks a shard each, like
-        train.TrainStep.  False: torch.rand, as the reference draws."""
+        train.TrainStep.  False: torch.rand, as the reference draws.
+        start: create_nerf's restored step count (the next iteration is start + 1).  n_views: allocate the per-view
+        depth scales / shifts now (else at the first step_view, from its DepthViews)."""
         from . import dp
         self.args, self.kw, self.optimizer, self.grad_vars = args, render_kwargs_train, optimizer, grad_vars
-        self.global_step = 0
+        self.global_step = int(start)
+        self.seed = seed
+        self.last_pixels = None      # step_view: this rank's pixels [R, 2] (row, col) of its last step
+        # DEPTH_SCALES / DEPTH_SHIFTS [V, 1] and their own Adam (:1071-1082)
+        self.depth_scales = self.depth_shifts = self.optimizer_ss = None
+        self._ss_grad = None
         # the 16-bit modes guard their Adam steps with the networks' range status words; the host looks every
         # `range_check_every` steps, as train.TrainStep does (0: never -- the caller does)
         self.range_check_every = int(range_check_every)
@@ -565,6 +680,7 @@ class DepthTrainStep:
         distributed = torch.distributed.is_initialized() if distributed is None else distributed
         self.bucket = None
         self.rank = torch.distributed.get_rank() if distributed else 0
+        self.world = torch.distributed.get_world_size() if distributed else 1
         self.draws = Fn.DrawSource(seed=seed) if counter_rng else None
         # both networks' backward as one launch sequence, as train.TrainStep (train.backward_merged)
         self.merged_backward = os.environ.get("PLNERF_MERGED_BWD", "1") != "0"
@@ -572,7 +688,28 @@ class DepthTrainStep:
         if distributed and torch.distributed.get_world_size() > 1:
             dp.broadcast_parameters(nets)      # replicas start from rank 0's weights (see train.TrainStep)
             dp.broadcast_optimizer_state([optimizer])
+            self.global_step = dp.broadcast_scalar(self.global_step, device=next(nets[0].parameters()).device)
             self.bucket = dp.GradientBucket(nets)
+        if n_views is not None:
+            self.init_depth_scale_shift(n_views, next(nets[0].parameters()).device)
+
+    def init_depth_scale_shift(self, n_views, device):
+        """DEPTH_SCALES = ones([V, 1]) * scale_init, DEPTH_SHIFTS = ones([V, 1]) * shift_init, leaf tensors, and their Adam
+        at scaleshift_lr (:1071-1082; defaults 1.0, 0.0, 1e-6).  Identical on every rank: no broadcast."""
+        a = self.args
+        ones = torch.ones((int(n_views), 1), dtype=torch.float, device=device)
+        self.depth_scales = (ones * getattr(a, "scale_init", 1.0)).requires_grad_(True)
+        self.depth_shifts = (ones * getattr(a, "shift_init", 0.0)).requires_grad_(True)
+        self.optimizer_ss = torch.optim.Adam(params=(self.depth_scales, self.depth_shifts),
+                                             lr=getattr(a, "scaleshift_lr", 1e-6))
+        self._ss_grad = torch.zeros(2, int(n_views), device=device)
+
+    def learning_rate(self, i=None):
+        """The rate the schedule writes into every param group before iteration i (default: the next one,
+        global_step + 1), or None where it leaves the rate alone (module function learning_rate)."""
+        a = self.args
+        i = self.global_step + 1 if i is None else i
+        return learning_rate(i, a.lrate, getattr(a, "start_decay_lrate", 400000), getattr(a, "end_decay_lrate", 500000))
 
     def check_range(self):
         """As train.TrainStep.check_range: reconcile withheld steps, raise on a set range status word."""
@@ -586,8 +723,42 @@ class DepthTrainStep:
                 f"plnerf_amd: {withheld} optimizer step(s) were withheld because another rank's forward left the "
                 "IEEE-half range (that rank's check_range() says which network)")
 
-    def __call__(self, ray_batch, target_s, target_h, space_carving_mask=None, cached_u=None, pytest=False):
+    def step_view(self, views, img_i, n_rand=None):
+        """The loop body from the drawn view on (run_nerf_sample_based_depth.py:1104-1161) for view `img_i` of `views` (a
+        DepthViews; the caller draws img_i, as np.random.choice(i_train) there, the same on every rank): the learning-rate
+        schedule written into every param group; this rank's n_rand rays (ray ids rank * n_rand ...) of the step's pixel
+        sample with target_h = hyp * DEPTH_SCALES[img_i] + DEPTH_SHIFTS[img_i] (plnerf_select_depth_rays); the step of
+        __call__; then, while scaleshift_steps(i, ...), the scale / shift gradient (plnerf_depth_scale_shift_grad, summed
+        over the ranks and scaled by 1 / world like the networks') and their Adam step -- unclipped: clip_grad_value_
+        applies to the networks only (:1156).  Returns what __call__ returns."""
         a = self.args
+        n_rand = int(n_rand if n_rand is not None else a.N_rand)
+        if self.depth_scales is None:
+            self.init_depth_scale_shift(views.n_views, views.device)
+        if self.depth_scales.shape[0] != views.n_views:
+            raise ValueError(f"the depth scales hold {self.depth_scales.shape[0]} views, `views` {views.n_views}")
+        i = self.global_step + 1
+        lr = self.learning_rate(i)
+        if lr is not None:      # train_utils/hyperparameter_update.py:3-5
+            for group in self.optimizer.param_groups:
+                group['lr'] = lr
+        cols, target_s, target_h, mask, hyp_raw, pix = views.select(
+            img_i, self.global_step, n_rand, ray_id0=self.rank * n_rand, scale=self.depth_scales, shift=self.depth_shifts,
+            seed=self.seed, want_viewdirs=bool(self.kw.get("use_viewdirs", True)), want_extras=True)
+        self.last_pixels = pix
+        ss = None
+        if scaleshift_steps(i, getattr(a, "warm_start_nerf", 0), getattr(a, "freeze_ss", 0),
+                            getattr(a, "space_carving_weight", 0.)):
+            ss = (int(img_i), hyp_raw)
+        return self._step(cols, target_s, target_h, mask, None, False, ss)
+
+    def __call__(self, ray_batch, target_s, target_h, space_carving_mask=None, cached_u=None, pytest=False):
+        return self._step(ray_batch, target_s, target_h, space_carving_mask, cached_u, pytest)
+
+    def _step(self, ray_batch, target_s, target_h, space_carving_mask, cached_u, pytest, ss=None):
+        """__call__'s body; ss = (view, hyp_raw [n_hyp, R, 1]): also step the depth scales / shifts."""
+        a = self.args
+        ss_work = None
         kw = {k: v for k, v in self.kw.items() if k not in ("ndc", "near", "far")}
         prev = Fn.DRAWS
         if self.draws is not None and ray_batch.is_cuda:
@@ -609,11 +780,15 @@ class DepthTrainStep:
             # both image terms, the space-carving term and the three gradients in one launch (plnerf_depth_loss);
             # backward((rgb, rgb0, pred_hyp), (their gradients)) is loss.backward()
             hyp = out["pred_hyp"] if carve else None
-            loss5, g_rgb, g_rgb0, g_hyp = Fn.depth_loss_and_grads(
+            loss5, g_rgb, g_rgb0, g_hyp, choice = Fn.depth_loss_and_grads(
                 rgb, rgb0, target_s, hyp, target_h if carve else None, getattr(a, "space_carving_weight", 0.),
                 threshold=getattr(a, "space_carving_threshold", 0.0), mask=space_carving_mask if carve else None,
                 is_joint=getattr(a, "is_joint", False), sharded=self.bucket is not None,
-                group=self.bucket.group if self.bucket is not None else None)
+                group=self.bucket.group if self.bucket is not None else None, want_choice=True)
+            if ss is not None and carve:
+                # d loss / d (DEPTH_SCALES, DEPTH_SHIFTS), dense over the views, from the hypotheses the loss chose; a
+                # sharded batch sums them over the ranks in one small all-reduce, waited together with the networks'
+                ss_work = self._scale_shift_grad(ss, hyp, target_h, space_carving_mask, choice)
             loss, img_loss, sc = loss5[0], loss5[1], loss5[3]
             roots = [(rgb, g_rgb)] + ([(rgb0, g_rgb0)] if rgb0 is not None else []) + ([(hyp, g_hyp)] if carve else [])
             from .train import backward_merged, merged_backward_ok
@@ -623,6 +798,9 @@ class DepthTrainStep:
             else:
                 torch.autograd.backward(tuple(r for r, _ in roots), tuple(gr for _, gr in roots))
         else:
+            if ss is not None and carve:
+                raise NotImplementedError("plnerf_amd: the depth scale / shift gradient needs the fused loss (CUDA tensors, "
+                                          "rgb [R, 3])")
             img_loss = torch.mean((rgb - target_s) ** 2)
             loss = img_loss
             sc = torch.zeros((), device=ray_batch.device)
@@ -648,6 +826,10 @@ class DepthTrainStep:
             scale = self.bucket.finish(defer_scale=flat_adam)
             tails = self.bucket.tails()
             tails = tails if len(tails) == len(self.nets) else None
+        ss_step = ss is not None and carve
+        if ss_step and ss_work is not None:
+            ss_work.wait()
+            self._ss_grad.mul_(1.0 / self.world)
         if flat_adam:
             # clip_grad_value_(0.1) folded into the step kernel (:1156), applied to the averaged gradient
             self.optimizer.step(clip_value=0.1, grad_scale=scale, guards=tails)
@@ -656,7 +838,24 @@ class DepthTrainStep:
         else:
             torch.nn.utils.clip_grad_value_(self.grad_vars, 0.1)
             self.optimizer.step()
+        if ss_step:      # (:1159-1161: after the networks' step, no clipping)
+            self.depth_scales.grad = self._ss_grad[0].reshape(-1, 1)
+            self.depth_shifts.grad = self._ss_grad[1].reshape(-1, 1)
+            self.optimizer_ss.step()
         self.global_step += 1
         if self.range_check_every and self.global_step % self.range_check_every == 0:
             self.check_range()
         return loss.detach(), img_loss.detach(), sc.detach(), out
+
+    def _scale_shift_grad(self, ss, pred_hyp, target_h, mask, choice):
+        """Writes this rank's d loss / d (scales, shifts) into self._ss_grad [2, V]; returns the pending all-reduce (SUM)
+        of a sharded batch, or None."""
+        view, hyp_raw = ss
+        a = self.args
+        Fn.depth_scale_shift_grad(pred_hyp, target_h, hyp_raw, getattr(a, "space_carving_weight", 0.), view,
+                                  self._ss_grad.shape[1], threshold=getattr(a, "space_carving_threshold", 0.0), mask=mask,
+                                  is_joint=getattr(a, "is_joint", False), joint_choice=choice, out=self._ss_grad)
+        if self.bucket is None:
+            return None
+        return torch.distributed.all_reduce(self._ss_grad, op=torch.distributed.ReduceOp.SUM, group=self.bucket.group,
+                                            async_op=True)

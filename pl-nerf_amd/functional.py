@@ -878,7 +878,7 @@ def joint_choice(pred_hyp, target_h, mask, threshold=0.0, group=None):
 
 
 def depth_loss_and_grads(rgb, rgb0, target, pred_hyp, target_h, weight, threshold=0.0, mask=None, is_joint=False,
-                         group=None, sharded=False):
+                         group=None, sharded=False, want_choice=False):
     """plnerf_depth_loss: the depth-supervised loop's loss and its three gradients in one launch (is_joint: the
     hypothesis is chosen per image -- per point column -- instead of per ray, model/run_nerf_helpers.py:72-77).
     Returns (loss5 = [total, img, img0, space carving, psnr], g_rgb, g_rgb0, g_hyp); rgb0 / pred_hyp may be None.
@@ -887,7 +887,9 @@ def depth_loss_and_grads(rgb, rgb0, target, pred_hyp, target_h, weight, threshol
     from the mean over ALL rays of the batch (nn.DataParallel gathers the outputs before the loss,
     run_nerf_sample_based_depth.py:564, 585), so the shards' column sums (plnerf_depth_joint_sums, fp64 [n_hyp, n_points],
     a few KB) are added over `group` before the minimum is taken -- every rank then differentiates the same hypotheses,
-    and the ranks' averaged loss is the one-rank loss of the global batch."""
+    and the ranks' averaged loss is the one-rank loss of the global batch.
+
+    want_choice: a fifth value, that exchanged choice ([n_points] int32), or None where the kernel chose from these rays."""
     rgb_c, t_c = _f32c(rgb), _f32c(target)
     rgb0_c = None if rgb0 is None else _f32c(rgb0)
     _expect(rgb_c.shape == t_c.shape and rgb_c.dim() == 2 and rgb_c.shape[1] == 3, "rgb / target must be [R, 3]")
@@ -915,4 +917,29 @@ def depth_loss_and_grads(rgb, rgb0, target, pred_hyp, target_h, weight, threshol
                                       float(threshold), L.dptr(loss5), L.dptr(g1),
                                       L.dptr(g0),
                                       L.dptr(g_h), L.dptr(ws, "workspace", torch.float64), L.stream()), "plnerf_depth_loss")
+    if want_choice:
+        return loss5, g1, g0, g_h, choice
     return loss5, g1, g0, g_h
+
+
+def depth_scale_shift_grad(pred_hyp, target_h, hyp_raw, weight, view, n_views, threshold=0.0, mask=None, is_joint=False,
+                           joint_choice=None, out=None):
+    """plnerf_depth_scale_shift_grad: d total / d (DEPTH_SCALES, DEPTH_SHIFTS) of depth_loss_and_grads' space-carving term
+    (run_nerf_sample_based_depth.py:1113-1120: target_h = hyp_raw * scale[view] + shift[view]), dense over the n_views
+    views with zeros outside row `view`, as autograd leaves them.  Same inputs as depth_loss_and_grads took; joint_choice
+    the exchanged is_joint choice (want_choice) of a sharded batch, else None.  Returns [2, n_views] fp32 (row 0 the
+    scale's gradient, row 1 the shift's) -- `out` if given."""
+    hyp_c, th_c, raw_c = _f32c(pred_hyp), _f32c(target_h), _f32c(hyp_raw)
+    R, P, H, PT = hyp_c.shape[0], hyp_c.shape[1], th_c.shape[0], th_c.shape[-1]
+    _expect(th_c.dim() == 3 and th_c.shape[1] == R and PT in (1, P) and raw_c.shape == th_c.shape,
+            f"pred_hyp [R, P] / target_h, hyp_raw [H, R, 1 or P]: got {tuple(hyp_c.shape)} / {tuple(th_c.shape)} / "
+            f"{tuple(raw_c.shape)}")
+    mask_c = None if mask is None else _f32c(mask).reshape(-1)
+    g = out if out is not None else torch.empty(2, n_views, device=hyp_c.device)
+    ws = _loss_workspace(hyp_c.device, L.DEPTH_SS_WORKSPACE_BYTES, "depth_ss")
+    L.check(L.lib().plnerf_depth_scale_shift_grad(
+        L.dptr(hyp_c, "pred_hyp"), L.dptr(th_c, "target_h"), L.dptr(raw_c, "hyp_raw"), L.dptr(mask_c, "mask"), R, P, H, PT,
+        int(bool(is_joint)), L.dptr(joint_choice if is_joint else None, "joint_choice", torch.int32), float(weight),
+        float(threshold), int(n_views), int(view), L.dptr(g[0], "g_scale"), L.dptr(g[1], "g_shift"),
+        L.dptr(ws, "workspace", torch.float64), L.stream()), "plnerf_depth_scale_shift_grad")
+    return g
