@@ -17,9 +17,14 @@ Other BASELINE configurations run with --workload {blender_128_64, llff_ndc, dep
 
 Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events around the dominant kernel (the fused
 fine-network MLP forward) on the launch stream and priced per SURVEY.md section 8d: algorithmic FLOP / launch time /
-dense 16-bit MFMA peak; `strict_fp32` re-times the step with the exact-fp32 kernels; `cpu_baseline` times the CPU
-oracle (a port of the reference's PyTorch path) on the host cores on a bounded sample.  The oracle is never on the
-measured GPU path.
+dense 16-bit MFMA peak.
+
+A plain run does only what that line's headline needs: set up, warm up, time the K steps, write --dump-outputs, print.
+Everything that takes runs of its own is behind --full (single GPU): `strict_fp32` re-times the step with the exact-fp32
+kernels; the extra legs (the other BASELINE workloads, the f16 throughput mode, the MLP alone in every precision, one
+800x800 frame, psnr_vs_ref); `roofline.sustained_peak` from a pure MFMA stream; `cpu_baseline` times the CPU oracle (a
+port of the reference's PyTorch path) on the host cores on a bounded sample.  The oracle is never on the measured GPU
+path.
 """
 import argparse
 import json
@@ -91,16 +96,21 @@ def parse(argv=None):
                          "fp16 training step; gradient tolerance stated in tests/test_gpu_modes.py).  bf16x3: the same "
                          "with bf16 forward elements.  fp32: exact fp32 MFMA, forward and backward.  bf16 / f16: plain "
                          "16-bit operands (throughput only, outside the 1e-5 contract)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strict-fp32", action="store_true", help="skip the exact-fp32 leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything that takes runs of its own (single GPU): the exact-fp32 "
+                         "leg, the extra legs, the sustained-MFMA probe of `roofline` and the CPU baseline; each can be "
+                         "left out again with its --no-* option.  Off by default: a plain run only sets up, warms up, "
+                         "times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-strict-fp32", action="store_true", help="--full: skip the exact-fp32 leg")
     ap.add_argument("--cpu-rays", type=int, default=1024)
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-no-grid", action="store_true", help="cpu_baseline: only the workload's own cell")
     ap.add_argument("--views", type=int, default=4, help="synthetic views resident on the device")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the bounded extra legs of the default single-GPU run (north_star's 65,536 x 192 MLP benchmark "
-                         "in every precision, the other BASELINE workloads x 10 steps, one 800x800 frame, the 200-step "
-                         "PSNR-vs-fp32 run); they add ~25 s to the run and nothing to the timed region")
+                    help="--full: skip the bounded extra legs (north_star's 65,536 x 192 MLP benchmark in every precision, "
+                         "the other BASELINE workloads x 10 steps, one 800x800 frame, the 200-step PSNR-vs-fp32 run) and "
+                         "the sustained-MFMA probe; they add ~25 s to the run and nothing to the timed region")
     ap.add_argument("--psnr-steps", type=int, default=200, help="steps of the psnr_vs_ref leg (each precision)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise RCCL and run the gradient all-reduce even with one rank (path check)")
@@ -446,8 +456,8 @@ def build_stub_step(rank, world):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Bounded extra legs of the default single-GPU run: every number the documents quote, on the one
-# line the driver records.  None of them is inside the timed region of `value`.
+# Bounded extra legs of a --full single-GPU run: every number the documents quote, on one line.
+# None of them is inside the timed region of `value`.
 # ---------------------------------------------------------------------------------------------------------------------
 def leg_mlp_only(P, dev, rays=65536, samples=192, iters=3):
     """north_star's MLP benchmark: the fused PE + MLP forward (inference) at 65,536 x 192 rows, every precision, each
@@ -658,7 +668,7 @@ def main(argv=None):
         dumped = dict(dump_outputs(a.dump_outputs, step, nets), step=a.warmup + a.steps - 1)
 
     strict = None
-    if a.precision != "fp32" and not a.no_strict_fp32 and world == 1 and not cpu:
+    if a.full and a.precision != "fp32" and not a.no_strict_fp32 and world == 1 and not cpu:
         # the strictly reference-equal arithmetic (exact fp32 MFMA forward and backward), same workload, short leg
         step32, nets32 = build_step(P, a, "fp32", scene, dev, rank, world, False)
         s_steps = max(3, min(a.steps, 5))
@@ -669,7 +679,7 @@ def main(argv=None):
         torch.cuda.empty_cache()
 
     extra = {}
-    if world == 1 and not cpu and not a.no_extra_legs and a.workload == "blender_64_128" and not a.force_dist:
+    if a.full and world == 1 and not cpu and not a.no_extra_legs and a.workload == "blender_64_128" and not a.force_dist:
         # -- the other BASELINE workloads, 10 steps each (configs[3], configs[4] per GPU, the config file's own 128 + 64)
         import copy
         wl = {}
@@ -778,8 +788,8 @@ def main(argv=None):
         flop_exec = FWD_FLOP_PER_ROW_EXECUTED["h16" if h16 else "fp32"]
         ach_exec = rows_fine * flop_exec / (fwd_ms * 1e-3) / 1e12 if fwd_ms else None
         issued = (ach_exec * MFMA_PER_PRODUCT[a.precision]) if ach_exec else None
-        # (not under --no-extra-legs: the profiling runs of tools/ use that flag, and a 0.2 s MFMA stream would head their kernel stats)
-        sustained = mfma_sustained_tflops() if (h16 and world == 1 and not a.no_extra_legs) else None
+        # (--full only, and not under --no-extra-legs: a 0.2 s MFMA stream would head the kernel stats of tools/' profiling runs)
+        sustained = mfma_sustained_tflops() if (a.full and h16 and world == 1 and not a.no_extra_legs) else None
         took_merged = bool(merged_steps) and merged_steps >= a.warmup + a.steps
         bytes_per_row = FWD_TRAIN_BYTES_PER_ROW["h16" if h16 else "fp32"]
         ach_gbs = rows_fine * bytes_per_row / (fwd_ms * 1e-3) / 1e9 if fwd_ms else None
@@ -847,7 +857,7 @@ def main(argv=None):
         if strict is not None:
             out["strict_fp32"] = strict
         out.update(extra)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a)
         # RCCL writes its version banner through C stdio, which is block-buffered on a pipe and would otherwise
         # come out at process exit, AFTER this line: flush it first so that the JSON is the last line of stdout

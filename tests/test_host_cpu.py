@@ -843,3 +843,16 @@ def test_bench_dump_outputs(built, tmp_path):
     assert runs[0]["loss.npy"].shape == () and runs[0]["network_fn.weight.npy"].shape == (32, 64)
     r = _run_bench("--gpus", "1", "--stub-cpu", "--steps", "0")
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+def test_bench_full_is_opt_in(built):
+    """A plain run times the steps and prints the line; the legs that take runs of their own (exact fp32, the other
+    workloads and precisions, the sustained-MFMA probe, the CPU baseline) run only under `--full`, which the
+    self-launcher passes on to its ranks like every other option."""
+    import json
+    import bench
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    r = _run_bench("--gpus", "2", "--stub-cpu", "--full", "--steps", "2", "--warmup", "1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["n_gpus"] == 2 and out["steps"] == 2

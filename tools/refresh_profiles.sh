@@ -7,8 +7,8 @@ out=$R/gpurun_out/${ROUND:-r06}p
 mkdir -p $out
 cd $R
 echo "${COMMIT:-unknown}" > $out/commit.txt
-# the driver's command form: every leg on the one line (workloads, throughput mode, 65536x192 MLP, 800x800 frame, psnr_vs_ref, strict fp32, cpu)
-python bench.py --steps 20 --warmup 5 > $out/bench_default_f16x3.json 2> $out/bench_default.err
+# --full: every leg on the one line (workloads, throughput mode, 65536x192 MLP, 800x800 frame, psnr_vs_ref, strict fp32, cpu)
+python bench.py --full --steps 20 --warmup 5 > $out/bench_default_f16x3.json 2> $out/bench_default.err
 for p in bf16x3 f16 bf16 fp32; do python bench.py --no-cpu-baseline --no-strict-fp32 --no-extra-legs --precision $p 2>/dev/null | tail -1; done > $out/bench_other_modes.jsonl
 python bench.py --force-dist --no-cpu-baseline --no-strict-fp32 --no-extra-legs 2>/dev/null | tail -1 > $out/bench_force_dist_1gpu.json
 python tools/scale_run.py --gpus 1,2 > $out/scale_run_on_1gpu_box.json 2> $out/scale_run.err
