@@ -114,6 +114,21 @@ DEPTHFEED_SIGNATURES = {
 }
 DEPTH_SS_WORKSPACE_BYTES = 4096        # PLNERF_DEPTH_SS_WORKSPACE_BYTES
 
+# ... and include/plnerf_hip_sampleerr.h (ABI 601): the importance-sampling error of the depth script's evaluation
+SAMPLEERR_SIGNATURES = {
+    "plnerf_sample_error_workspace_bytes": (ctypes.c_size_t, [c_i]),
+    "plnerf_sample_error": (c_i, [c_i, c_i] + [c_f] * 3 + [c_i, c_f, c_f, c_s]),
+}
+SAMPLEERR_ROW = 2                          # PLNERF_SAMPLEERR_ROW: fp64 values per row, columns PLNERF_SAMPLEERR_*
+SAMPLEERR_SUM, SAMPLEERR_COUNT = range(SAMPLEERR_ROW)
+SAMPLEERR_RAYS_PER_GROUP = 64              # PLNERF_SAMPLEERR_RAYS_PER_GROUP
+SAMPLEERR_MAX_N = 1024                     # PLNERF_SAMPLEERR_MAX_N
+
+
+def sample_error_workspace_bytes(R):
+    """plnerf_sample_error_workspace_bytes(R), restated: one partial row per group of rays."""
+    return -(-R // SAMPLEERR_RAYS_PER_GROUP) * SAMPLEERR_ROW * 8 if R > 0 else 0
+
 
 _lib = None
 
@@ -130,7 +145,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-                list(DEPTHFEED_SIGNATURES.items()):
+                list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

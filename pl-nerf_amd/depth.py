@@ -13,6 +13,7 @@ What differs from the NVS path (render.py):
     the transmittance / density knots (g_tau, g_T of plnerf_quad_bwd);
   * one Adam over both networks, gradient values clipped to 0.1 (:1155-1157).
 """
+import math
 import os
 import sys
 
@@ -22,7 +23,7 @@ import torch
 from . import _lib as L
 from . import functional as Fn
 from . import raybatch as RB
-from .evaluate import _score_views
+from .evaluate import MeanTracker, _check_range, _choose_views, _score_views, sample_error_rows
 from .nerf import Embedder, NeRF
 from .optim import FlatAdam
 from .render import (MAX_ROWS_PER_LAUNCH, _draw_noise, _refuse_unsupported, _rgb_sigma, batchify, raw2outputs as _raw2outputs, sample_pdf,
@@ -443,15 +444,66 @@ def render_images_with_metrics(count, indices, images, depths, valid_depths, pos
     is not provided: it raises."""
     if with_test_time_optimization:
         raise NotImplementedError("with_test_time_optimization: the per-view camera-code optimisation is not provided")
-    dev = RB.default_device()
+    set_camera_code = _camera_code_setter(args, render_kwargs_test, embedcam_fn, RB.default_device())
+    return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
+                        render_kwargs_test, render, lambda img_idx: intrinsics[img_idx, :], True, set_camera_code,
+                        keep_images)
 
+
+def _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev):
+    """The evaluation loops' camera code of view img_idx (run_nerf_sample_based_depth.py:384-395, 458-469): with
+    args.input_ch_cam > 0, embedcam_fn(i), or zeros when embedcam_fn is None, set in render_kwargs_test["embedded_cam"]."""
     def set_camera_code(img_idx):
         if getattr(args, "input_ch_cam", 0) > 0:
             render_kwargs_test["embedded_cam"] = (torch.zeros((args.input_ch_cam,), device=dev) if embedcam_fn is None
                                                   else embedcam_fn(torch.tensor(img_idx, device=dev)))
-    return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
-                        render_kwargs_test, render, lambda img_idx: intrinsics[img_idx, :], True, set_camera_code,
-                        keep_images)
+    return set_camera_code
+
+
+def test_images_samples(count, indices, images, depths, valid_depths, poses, H, W, intrinsics, lpips_alex, args,
+                        render_kwargs_test, embedcam_fn=None, with_test_time_optimization=False):
+    """run_nerf_sample_based_depth.py:349-421 (`--task test_samples_error`): how close the importance samples land to
+    the rendered surface.  For each of `count` views of `indices` (all of them in order for None, else
+    np.random.choice(indices, count, replace=False)), rendered under no_grad with the per-view intrinsics[i] =
+    (fx, fy, cx, cy) and camera code (as render_images_with_metrics sets it), the mean over the pixels where
+    valid_depths[i] [H,W] is set of mean_k |pred_hyp - depth_map|.  Returns a MeanTracker of "importance_sampling_error",
+    one add per view whose mean is not NaN (a view without a valid pixel adds nothing).
+
+    The frame is rendered in args.chunk-ray chunks with get_rays and render; each chunk's hypotheses are scored on the
+    device by plnerf_sample_error as soon as they exist (added to the view's fp64 row) and dropped, so no [H,W,N]
+    hypothesis plane is ever held.  The rows are read back once, after the last view; the means are fp64 (the
+    reference's are fp32).  images, depths and lpips_alex are accepted and unused, as there; the reference's
+    metrics_depth_samples.txt is MeanTracker.print(f) on the caller's side.  with_test_time_optimization raises."""
+    if with_test_time_optimization:
+        raise NotImplementedError("with_test_time_optimization: the per-view camera-code optimisation is not provided")
+    dev = RB.default_device()
+    count, img_i = _choose_views(count, indices)
+    set_camera_code = _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev)
+    chunk, n_rays = args.chunk, H * W
+    rows = torch.zeros(count, L.SAMPLEERR_ROW, dtype=torch.float64, device=dev)
+    workspace = torch.empty(L.sample_error_workspace_bytes(min(chunk, n_rays)), dtype=torch.uint8, device=dev)
+    with torch.no_grad():
+        for n, img_idx in enumerate(img_i):
+            set_camera_code(img_idx)
+            intrinsic = intrinsics[img_idx, :]
+            rays_o, rays_d = get_rays(H, W, intrinsic, poses[img_idx, :3, :4])
+            rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
+            valid = torch.as_tensor(valid_depths[img_idx]).to(device=dev, dtype=torch.bool).reshape(-1)
+            for first in range(0, n_rays, chunk):
+                last = min(first + chunk, n_rays)
+                rays = torch.stack([rays_o[first:last], rays_d[first:last]])
+                _, _, _, extras = render(H, W, intrinsic, chunk=chunk, rays=rays, **render_kwargs_test)
+                sample_error_rows(extras['pred_hyp'].contiguous(), extras['depth_map'].contiguous(), valid[first:last],
+                                  out=rows[n], workspace=workspace, accumulate=True)
+                del extras
+    _check_range(render_kwargs_test)
+
+    mean_depth_metrics = MeanTracker()
+    for total, counted in rows.cpu().tolist():
+        error = total / counted if counted > 0 else math.nan      # torch.mean of no pixel is NaN
+        if not math.isnan(error):
+            mean_depth_metrics.add({"importance_sampling_error": error})
+    return mean_depth_metrics
 
 
 class _SpaceCarvingFn(torch.autograd.Function):

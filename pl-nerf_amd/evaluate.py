@@ -96,6 +96,38 @@ def metric_rows(rgb, target, rgb0=None, depth=None, target_depth=None, valid=Non
     return out
 
 
+def sample_error_rows(pred_hyp, depth, valid=None, out=None, workspace=None, accumulate=False):
+    """The [SAMPLEERR_ROW] fp64 device row of plnerf_sample_error (columns _lib.SAMPLEERR_SUM / _COUNT) for hypotheses
+    pred_hyp [..., N] fp32 against depth [...] fp32 (the rendered depth_map), over the rays where valid [...] (bool or
+    uint8; None = every ray) is set: the sum over those rays of mean_k |pred_hyp - depth|, and their number.
+    accumulate=True adds both to `out` on the device instead of overwriting it (a frame scored chunk by chunk in stream
+    order).  One call, two launches; nothing is synchronised.  `out` and `workspace`
+    (_lib.sample_error_workspace_bytes(R) uint8, R = depth.numel()) may be given to reuse buffers."""
+    if pred_hyp.dim() < 1:
+        raise ValueError("pred_hyp must be [..., N]")
+    if depth.shape != pred_hyp.shape[:-1]:
+        raise ValueError(f"depth {tuple(depth.shape)} does not match pred_hyp's rays {tuple(pred_hyp.shape[:-1])}")
+    if valid is not None:
+        if valid.shape != depth.shape:
+            raise ValueError(f"valid {tuple(valid.shape)} does not match depth {tuple(depth.shape)}")
+        valid = valid.contiguous()
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+    R, N = depth.numel(), pred_hyp.shape[-1]
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True adds to `out`: pass the row to add to")
+        out = torch.empty(L.SAMPLEERR_ROW, dtype=torch.float64, device=pred_hyp.device)
+    if workspace is None:
+        workspace = torch.empty(L.sample_error_workspace_bytes(R), dtype=torch.uint8, device=pred_hyp.device)
+    if out.shape != (L.SAMPLEERR_ROW,) or workspace.numel() < L.sample_error_workspace_bytes(R):
+        raise ValueError("out must be [SAMPLEERR_ROW] and workspace at least sample_error_workspace_bytes(R)")
+    L.check(L.lib().plnerf_sample_error(
+        R, N, L.dptr(pred_hyp, "pred_hyp"), L.dptr(depth, "depth"), L.dptr(valid, "valid", torch.uint8),
+        1 if accumulate else 0, L.dptr(workspace, "workspace", torch.uint8), L.dptr(out, "out", torch.float64),
+        L.stream()), "plnerf_sample_error")
+    return out
+
+
 def row_metrics(row, H, W, with_rgb0):
     """One host row -> {img_loss, psnr, ssim[, img_loss0, psnr0][, depth_rmse]}; depth_rmse is left out when it is NaN
     (no valid pixel), as the reference drops it."""
@@ -132,15 +164,20 @@ def _check_range(render_kwargs):
             net.check_range()       # a clamped frame must not be scored silently
 
 
+def _choose_views(count, indices):
+    """The views an evaluation loop renders (run_plnerf.py:285-294): every index in order for count None, else
+    np.random.choice(indices, min(count, len), replace=False) under the caller's seed.  Returns (count, views)."""
+    if count is None:
+        return len(indices), indices
+    count = min(count, len(indices))
+    return count, np.random.choice(indices, size=count, replace=False)
+
+
 def _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, chunk, render_kwargs_test,
                  render_fn, intrinsic_of, with_depth, before_frame, keep_images):
     """The loop of render_images_with_metrics (run_plnerf.py:284-363; run_nerf_sample_based_depth.py:424-510)."""
     far = render_kwargs_test['far']
-    if count is None:
-        count, img_i = len(indices), indices
-    else:
-        count = min(count, len(indices))
-        img_i = np.random.choice(indices, size=count, replace=False)
+    count, img_i = _choose_views(count, indices)
     dev = RB.default_device()
 
     rows = torch.empty(count, L.EVAL_ROW, dtype=torch.float64, device=dev)
