@@ -130,6 +130,54 @@ def sample_error_workspace_bytes(R):
     return -(-R // SAMPLEERR_RAYS_PER_GROUP) * SAMPLEERR_ROW * 8 if R > 0 else 0
 
 
+# ... and include/plnerf_hip_step.h (ABI 601): one call = one optimisation step.  The three structs live in host memory;
+# every pointer field is a device pointer (c_void_p: assign `tensor.data_ptr()`).
+STEP_RAYS_VIEW, STEP_RAYS_BANK = 0, 1      # PLNERF_STEP_RAYS_*
+
+
+class StepConfig(ctypes.Structure):
+    """plnerf_step_config."""
+    _fields_ = [("max_rays", c_i), ("n_samples", c_i), ("n_importance", c_i), ("mode", c_i), ("color_mode", c_i),
+                ("lindisp", c_i), ("perturb", c_i), ("white_bkgd", c_i), ("farcolorfix", c_i),
+                ("raw_noise_std", ctypes.c_float), ("zero_tol", ctypes.c_float), ("epsilon", ctypes.c_float), ("ndc", c_i),
+                ("ndc_focal", ctypes.c_double), ("H", c_i), ("W", c_i), ("fx", ctypes.c_float), ("fy", ctypes.c_float),
+                ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("near", ctypes.c_float), ("far", ctypes.c_float),
+                ("precision", c_i), ("fwd_kernel", c_i), ("input_ch", c_i), ("input_ch_views", c_i), ("ray_source", c_i),
+                ("n_views", c_i), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("adam_eps", ctypes.c_float),
+                ("seed", ctypes.c_uint64), ("bank_seed", ctypes.c_uint64)]
+
+
+class StepNet(ctypes.Structure):
+    """plnerf_step_net."""
+    _fields_ = [("params", ctypes.c_void_p * N_PARAM_TENSORS), ("param_flat", c_f), ("grad_flat", c_f), ("exp_avg", c_f),
+                ("exp_avg_sq", c_f), ("n_params", ctypes.c_int64), ("packed", c_f), ("skip_if_set", c_f),
+                ("skip_if_set2", c_f), ("withheld", c_f)]
+
+
+class StepIo(ctypes.Structure):
+    """plnerf_step_io."""
+    _fields_ = [("coarse", StepNet), ("fine", StepNet), ("t_vals", c_f), ("u_vals", c_f), ("views", c_f), ("poses", c_f),
+                ("images", c_f), ("loss4", c_f)]
+
+
+class StepArgs(ctypes.Structure):
+    """plnerf_step_args."""
+    _fields_ = [("rays", c_i), ("step", ctypes.c_uint32), ("ray_id0", c_i), ("c2w", ctypes.c_float * 12), ("image", c_f),
+                ("crop_r0", c_i), ("crop_c0", c_i), ("crop_rows", c_i), ("crop_cols", c_i), ("epoch", ctypes.c_uint32),
+                ("pos0", c_i), ("lr_fine", ctypes.c_float), ("lr_coarse", ctypes.c_float), ("adam_step_fine", c_i),
+                ("adam_step_coarse", c_i), ("loss_scale", ctypes.c_float)]
+
+
+STEP_STRUCTS = {"plnerf_step_config": StepConfig, "plnerf_step_net": StepNet, "plnerf_step_io": StepIo,
+                "plnerf_step_args": StepArgs}
+STEP_SIGNATURES = {
+    "plnerf_train_step_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(StepConfig)]),
+    "plnerf_train_step": (c_i, [ctypes.POINTER(StepConfig), ctypes.POINTER(StepIo), ctypes.POINTER(StepArgs), c_f,
+                                ctypes.c_size_t, c_s]),
+}
+STEP_WORKSPACE_ALIGN = 256                 # the workspace's alignment (include/plnerf_hip_step.h)
+
+
 _lib = None
 
 
@@ -145,7 +193,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-                list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()):
+                list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -429,6 +429,9 @@ def create_nerf(args, device=None):
     def network_query_fn(inputs, viewdirs, network_fn):
         return run_network(inputs, viewdirs, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn,
                            netchunk=args.netchunk)
+    # (what the closure encodes with: a caller that runs the networks itself -- train.TrainStep's one-call route -- can tell
+    # whether the kernels' own encoding is this query function's)
+    network_query_fn.embedders = (embed_fn, embeddirs_fn)
 
     on_gpu = device.type == "cuda"
     # modes whose kernels can clamp at the IEEE-half maximum (forward: f16x3 / f16; saved planes: every 16-bit mode):

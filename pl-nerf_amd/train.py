@@ -13,6 +13,7 @@ there: one view per step (`TrainStep.step_view`, its no_batching branch) and ran
 """
 import ctypes
 import os
+import sys
 
 import numpy as np
 import torch
@@ -21,9 +22,12 @@ from . import _lib as L
 from . import dp
 from . import functional as Fn
 from . import raybatch as RB
+from . import stepplan
 from .optim import FlatAdam
 from .rays import ndc_rays
 from .render import render, render_rays
+
+Rn = sys.modules[render_rays.__module__]      # (the module: the package attribute `render` is the function)
 
 
 class _MseFn(torch.autograd.Function):
@@ -238,7 +242,7 @@ class TrainStep:
     renders it or N ranks render a shard each.  `counter_rng=False` restores torch.rand."""
 
     def __init__(self, args, render_kwargs_train, optimizer, optimizer_coarse, start=0, distributed=None, seed=0,
-                 counter_rng=True, range_check_every=100, pipeline=None):
+                 counter_rng=True, range_check_every=100, pipeline=None, one_call=False):
         """The step runs on ONE stream in the reference's order: render, loss, backward, both optimizers.  (Rounds 3-4
         also carried two-stream schedules -- the coarse network's chain beside the fine pass, and across step boundaries;
         bit-identical, measured +1.4 % / -0.8 % with twice the step jitter, profiles/r04_pipeline_ab.txt -- removed in
@@ -272,6 +276,13 @@ class TrainStep:
         self.merged_backward = os.environ.get("PLNERF_MERGED_BWD", "1") != "0"
         self.merged_steps = 0      # steps that took the merged backward (the rest went through torch.autograd.backward)
         self.last_batch = None     # step_batch: (epoch, first bank position, rays, offset in the global batch, global n)
+        # one_call=True: step_view / step_batch hand every step that qualifies (_one_call_ok) to the library as ONE call --
+        # plnerf_train_step enqueues the launch sequence of the fused route below itself, bit for bit the same step, without
+        # the ~23 Python -> ctypes -> autograd round trips between the launches (stepplan.StepPlan holds its buffers).  A
+        # step that does not qualify takes the route below, silently; one_call_steps counts the ones that did.
+        self.one_call = bool(one_call)
+        self.one_call_steps = 0
+        self._plan = self._plan_key = None
         self.bucket = None
         if distributed and self.world > 1:
             # replicas must start from the same weights (create_nerf initialises from each process's own RNG, and a
@@ -293,6 +304,10 @@ class TrainStep:
         """The loop body from the view on (run_plnerf.py:1259-1316): choose this rank's n_rand pixels of the view on
         the device, then the optimisation step.  `image` [H, W, 3] lives on the device."""
         n_rand = int(n_rand if n_rand is not None else self.args.N_rand)
+        if self.one_call:
+            out = self._step_view_one_call(H, W, K, c2w, image, near, far, n_rand, precrop)
+            if out is not None:
+                return out
         cols, target, _ = select_view_rays(H, W, K, c2w, image, n_rand, near, far, seed=self.seed,
                                            step=self.global_step, ray_id0=self.rank * n_rand, precrop=precrop,
                                            want_viewdirs=bool(self.kw.get("use_viewdirs", True)))
@@ -311,6 +326,13 @@ class TrainStep:
         n_rand = int(n_rand if n_rand is not None else self.args.N_rand)
         want_vd = bool(self.kw.get("use_viewdirs", True))
         epoch, p0, n = bank.schedule(self.global_step, n_rand * self.world)
+        if self.one_call and self._one_call_ok(n) and n <= n_rand:      # (one process: the whole batch, weight 1)
+            plan = self._plan_for("bank", n_rand, bank.H, bank.W, bank.K, bank.near, bank.far, bank)
+            steps = plan.adam_steps() if plan is not None else None
+            if steps is not None:
+                self.last_batch = (epoch, p0, n, 0, n)
+                return self._one_call_done(plan.run(n, self.global_step, 0, self.optimizer_coarse.param_groups[0]['lr'],
+                                                    self.optimizer.param_groups[0]['lr'], steps, epoch=epoch, pos0=p0))
         begin, end = dp.shard_batch(n, self.rank, self.world)
         self.last_batch = (epoch, p0 + begin, end - begin, begin, n)      # (epoch, first position, rays, offset, global n)
         if end > begin:
@@ -328,6 +350,79 @@ class TrainStep:
 
     def __call__(self, H, W, K, batch_rays, target_s, near=0., far=1.):
         return self._step(H, W, K, batch_rays, target_s, near, far)
+
+    def _one_call_ok(self, n_rays):
+        """Can this step go to the library as one call (plnerf_train_step)?  What the entry enqueues is the fused route of
+        _step with the merged backward: the reference's two native networks in one 16-bit precision (merged_backward_ok's
+        conditions, known here before anything runs), piecewise-linear mode with importance sampling, counter-based draws,
+        the kernels' own encoding, a batch that fits one launch per network, one process, nobody watching the stages
+        (render.STAGE_TAP, functional.KERNEL_TIMER) -- and not a constant_init warm-up step."""
+        kw = self.kw
+        if not (self.merged_backward and self.draws is not None and self.bucket is None and len(self.nets) == 2):
+            return False
+        if self.global_step + 1 < getattr(self.args, "constant_init", 0) or Rn.STAGE_TAP is not None or \
+                Fn.KERNEL_TIMER is not None:
+            return False
+        S, N = int(kw.get("N_samples", 0)), int(kw.get("N_importance", 0))
+        if kw.get("mode") != "linear" or kw.get("color_mode") not in ("midpoint", "left") or kw.get("pytest", False) or \
+                not kw.get("use_viewdirs", False) or N < 1 or S < 2 or S + N > 1024:
+            return False
+        if not 1 <= n_rays <= getattr(self.args, "chunk", 1024 * 32) or n_rays * (S + N) > Rn.MAX_ROWS_PER_LAUNCH:
+            return False
+        emb = getattr(kw.get("network_query_fn"), "embedders", None)      # (create_nerf's query function says what it encodes with)
+        if emb is None:
+            return False
+        c, f = self.nets
+        return c is not f and c.precision == f.precision and all(
+            n.is_native() and n.precision in L.GUARDED_PRECISIONS and n.density_beta == 0.0 and Rn._fusable(n, emb[0], emb[1], True)
+            and all(p.is_cuda and p.requires_grad for p in n.param_list()) for n in (c, f))
+
+    def _plan_for(self, kind, max_rays, H, W, K, near, far, bank):
+        """The StepPlan of this configuration: the one in hand while it still describes the live buffers, else a new one
+        (None: the optimizers are not FlatAdams over exactly the two networks)."""
+        key = stepplan.plan_key(self.kw, kind, max_rays, H, W, K, near, far, bank, self.seed)
+        plan = self._plan
+        if plan is not None and key == self._plan_key and plan.current():
+            return plan
+        self._plan = self._plan_key = None
+        opts = (self.optimizer_coarse, self.optimizer)
+        if not stepplan.StepPlan.supported(self.nets, opts):
+            return None
+        self._plan = stepplan.StepPlan(self.kw, self.nets, opts, kind, max_rays, H, W, K, near, far, self.seed, bank)
+        self._plan_key = key
+        return self._plan
+
+    def _step_view_one_call(self, H, W, K, c2w, image, near, far, n_rand, precrop):
+        """step_view through plnerf_train_step; None when the step does not qualify (nothing has happened then)."""
+        if image is None or not image.is_cuda or not self._one_call_ok(n_rand):
+            return None
+        plan = self._plan_for("view", n_rand, H, W, K, near, far, None)
+        steps = plan.adam_steps() if plan is not None else None
+        if steps is None:
+            return None
+        if precrop is not None:
+            dH, dW = precrop
+            crop = (H // 2 - dH, W // 2 - dW, 2 * dH, 2 * dW)
+        else:
+            crop = (0, 0, H, W)
+        c2w_host = [float(v) for v in torch.as_tensor(c2w, device="cpu")[:3, :4].reshape(-1)]
+        img = image.detach().to(torch.float32).contiguous()
+        return self._one_call_done(plan.run(n_rand, self.global_step, self.rank * n_rand,
+                                            self.optimizer_coarse.param_groups[0]['lr'], self.optimizer.param_groups[0]['lr'],
+                                            steps, c2w=c2w_host, image=img, crop=crop))
+
+    def _one_call_done(self, loss4):
+        """The host state _step leaves behind: both learning rates, the step count, the range poll."""
+        new_lrate = self.learning_rate()
+        for group in self.optimizer.param_groups:
+            group['lr'] = new_lrate
+        for group in self.optimizer_coarse.param_groups:
+            group['lr'] = new_lrate                   # sic: the reference uses the fine rate here (line 1315)
+        self.global_step += 1
+        self.one_call_steps += 1
+        if self.range_check_every and self.global_step % self.range_check_every == 0:
+            self.check_range()
+        return loss4[0], loss4[3]
 
     def _render(self, H, W, K, rays, near, far, constant_init):
         chunk = getattr(self.args, "chunk", 1024 * 32)
