@@ -177,6 +177,55 @@ STEP_SIGNATURES = {
 }
 STEP_WORKSPACE_ALIGN = 256                 # the workspace's alignment (include/plnerf_hip_step.h)
 
+# ... and include/plnerf_hip_depthstep.h (ABI 601): one call = one step of the depth-supervised loop, under the same
+# conventions (host structs, device pointers as c_void_p)
+c_fl = ctypes.c_float
+
+
+class DepthStepConfig(ctypes.Structure):
+    """plnerf_depth_step_config."""
+    _fields_ = [("max_rays", c_i), ("n_samples", c_i), ("n_importance", c_i), ("color_mode", c_i), ("lindisp", c_i),
+                ("perturb", c_i), ("white_bkgd", c_i), ("raw_noise_std", c_fl), ("zero_tol", c_fl), ("epsilon", c_fl),
+                ("n_views", c_i), ("H", c_i), ("W", c_i), ("n_hyp", c_i), ("pose_rows", c_i), ("near", c_fl), ("far", c_fl),
+                ("precision", c_i), ("fwd_kernel", c_i), ("input_ch", c_i), ("input_ch_views", c_i), ("input_scale", c_fl),
+                ("density_beta", c_fl), ("is_joint", c_i), ("space_carving_weight", c_fl), ("space_carving_threshold", c_fl),
+                ("clip_value", c_fl), ("beta1", c_fl), ("beta2", c_fl), ("adam_eps", c_fl), ("ss_beta1", c_fl),
+                ("ss_beta2", c_fl), ("ss_adam_eps", c_fl), ("seed", ctypes.c_uint64)]
+
+
+class DepthStepIo(ctypes.Structure):
+    """plnerf_depth_step_io."""
+    _fields_ = [("coarse", StepNet), ("fine", StepNet), ("t_vals", c_f), ("u_vals", c_f), ("images", c_f), ("hyp", c_f),
+                ("valid", c_f), ("poses", c_f), ("intrinsics", c_f), ("scale", c_f), ("shift", c_f), ("ss_grad", c_f),
+                ("ss_exp_avg", c_f), ("ss_exp_avg_sq", c_f), ("loss5", c_f)]
+
+
+class DepthStepArgs(ctypes.Structure):
+    """plnerf_depth_step_args."""
+    _fields_ = [("view", c_i), ("rays", c_i), ("step", ctypes.c_uint32), ("ray_id0", c_i), ("lr", c_fl), ("adam_step", c_i),
+                ("carve", c_i), ("ss_step", c_i), ("ss_lr", c_fl), ("ss_adam_step", c_i)]
+
+
+DEPTH_STEP_MAX_SAMPLES = 1022              # n_samples + n_importance of plnerf_depth_train_step (PLNERF_MAX_SAMPLES)
+DEPTH_STEP_VIEWS = ("rgb", "rgb0", "depth", "depth0", "acc", "acc0", "disp", "disp0", "z_std", "pred_hyp", "z_vals", "z_vals0",
+                    "pixels", "target_h", "mask")
+
+
+class DepthStepViews(ctypes.Structure):
+    """plnerf_depth_step_views: byte offsets inside the workspace."""
+    _fields_ = [(name, ctypes.c_size_t) for name in DEPTH_STEP_VIEWS]
+
+
+DEPTHSTEP_STRUCTS = {"plnerf_depth_step_config": DepthStepConfig, "plnerf_depth_step_io": DepthStepIo,
+                     "plnerf_depth_step_args": DepthStepArgs, "plnerf_depth_step_views": DepthStepViews}
+DEPTHSTEP_SIGNATURES = {
+    "plnerf_depth_train_step_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DepthStepConfig)]),
+    "plnerf_depth_train_step_layout": (c_i, [ctypes.POINTER(DepthStepConfig), ctypes.POINTER(DepthStepViews)]),
+    "plnerf_depth_train_step": (c_i, [ctypes.POINTER(DepthStepConfig), ctypes.POINTER(DepthStepIo),
+                                      ctypes.POINTER(DepthStepArgs), c_f, ctypes.c_size_t, c_s]),
+    "plnerf_depth_ss_adam": (c_i, [c_f] * 5 + [c_i] + [c_fl] * 4 + [c_i, c_fl, c_s]),
+}
+
 
 _lib = None
 
@@ -193,7 +242,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-                list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
+                list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + list(DEPTHSTEP_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

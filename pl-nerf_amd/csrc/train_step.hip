@@ -2,32 +2,14 @@
 // library call.  The step is the sequence of this library's own entry points that train.TrainStep._step reaches through
 // Python, ctypes and torch.autograd on its fused route -- the same launches with the same arguments, in the same order, on
 // the one stream -- so the two routes agree bit for bit; what the Python route does between those launches in torch (the
-// density noise's scale, the loss scale on the two image gradients) are the two small kernels below.  No kernel of the
+// density noise's scale, the loss scale on the two image gradients) is the small kernel of step_common.h.  No kernel of the
 // path is duplicated here.
-#include "common.h"
+#include "step_common.h"
 #include "../../include/plnerf_hip_batching.h"
-#include "../../include/plnerf_hip_step.h"
 
 namespace {
 
-constexpr size_t ALIGN = 256;
-constexpr uint32_t NOISE_STREAM = 2;      // functional.DrawSource.NOISE: the coarse pass's density noise; the fine pass's is + 1
-
-// x[i] *= s over two buffers in one launch (torch: `t * python_float`, the scalar rounded to fp32 first)
-__global__ __launch_bounds__(256) void scale2_kernel(float* __restrict__ a, const size_t na, float* __restrict__ b,
-                                                     const size_t nb, const float s) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < na) a[i] = a[i] * s;
-    else if (i < na + nb) b[i - na] = b[i - na] * s;
-}
-
-int scale2(float* a, size_t na, float* b, size_t nb, float s, hipStream_t st) {
-    const size_t n = na + nb;
-    if (n == 0) return PLNERF_OK;
-    hipLaunchKernelGGL(scale2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, na, b, nb, s);
-    PLNERF_CHECK_LAUNCH();
-    return PLNERF_OK;
-}
+using namespace plnerf_step;      // ALIGN, NOISE_STREAM, scale2, Carver, check_net (shared with depth_train_step.hip)
 
 // The workspace, carved for config.max_rays: the same addresses at every step of a run.
 struct Plan {
@@ -39,18 +21,6 @@ struct Plan {
     uint32_t *absmax_c, *absmax_f;
     void *saved_c, *saved_f, *bwd_c, *bwd_f;
     size_t bytes;
-};
-
-struct Carver {
-    unsigned char* base;
-    size_t off;
-    template <typename T>
-    T* take(size_t nbytes) {
-        T* p = (T*)(base + off);      // (base may be NULL: the size query only adds up)
-        off += (nbytes + ALIGN - 1) / ALIGN * ALIGN;
-        return p;
-    }
-    float* floats(size_t n) { return take<float>(n * sizeof(float)); }
 };
 
 Plan carve(const plnerf_step_config* c, void* workspace) {
@@ -99,13 +69,6 @@ int check_config(const plnerf_step_config* c) {
     if (c->n_samples > PLNERF_MAX_SAMPLES || c->n_samples + c->n_importance > 1024) return PLNERF_ERANGE;
     // (row counts are ints throughout the ABI)
     if ((uint64_t)c->max_rays * (uint64_t)(c->n_samples + c->n_importance) > (uint64_t)INT32_MAX / 4) return PLNERF_ERANGE;
-    return PLNERF_OK;
-}
-
-int check_net(const plnerf_step_net* n) {
-    if (!n->param_flat || !n->grad_flat || !n->exp_avg || !n->exp_avg_sq || !n->packed || n->n_params < 1) return PLNERF_EINVAL;
-    for (int i = 0; i < PLNERF_N_PARAM_TENSORS; ++i)
-        if (!n->params[i] || n->params[i] < n->param_flat || n->params[i] >= n->param_flat + n->n_params) return PLNERF_EINVAL;
     return PLNERF_OK;
 }
 

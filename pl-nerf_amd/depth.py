@@ -577,6 +577,8 @@ def create_nerf(args, scene_render_params=None, device=None):
     def network_query_fn(inputs, viewdirs, embedded_cam, network_fn):
         return run_network(inputs, viewdirs, embedded_cam, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn,
                            bb_center=box[0], bb_scale=box[1], netchunk=getattr(args, "netchunk", 1024 * 64))
+    # (what the query function encodes with and its bounding box: DepthTrainStep's one-call route asks, as train.TrainStep's)
+    network_query_fn.embedders, network_query_fn.box = (embed_fn, embeddirs_fn), box
     # (optim.FlatAdam on the GPU: one launch per network's gradient buffer)
     half_range = device.type == "cuda" and getattr(args, "precision", "fp32") in L.GUARDED_PRECISIONS
     guarded = [n for n in (model, model_fine) if n is not None and n.is_supported()]      # (the layer-by-layer route is fp32: no word)
@@ -707,10 +709,21 @@ class DepthTrainStep:
 
     step_view is the whole loop body from the view on (:1104-1161): learning-rate schedule, the step's rays of a
     DepthViews view, this call, and the per-view depth scale / shift Adam.  The iteration counter is the reference's
-    i = start + 1, start + 2, ...: it keys the pixel sample and the draws, the schedule, warm_start_nerf and freeze_ss."""
+    i = start + 1, start + 2, ...: it keys the pixel sample and the draws, the schedule, warm_start_nerf and freeze_ss.
+
+    one_call=True: step_view hands every step that qualifies (_one_call_ok) to the library as ONE call --
+    plnerf_depth_train_step (include/plnerf_hip_depthstep.h) enqueues the launch sequence of the fused route of _step itself,
+    bit for bit the same step, without the Python -> ctypes -> autograd round trips between the launches
+    (stepplan.DepthStepPlan holds its buffers).  A step that does not qualify, and every __call__ on a caller-made batch,
+    takes the existing route, silently; one_call_steps counts the ones that did.  Such a step returns (loss, img_loss,
+    space_carving, out) with `out` holding rgb_map, rgb0, depth_map, depth0, acc_map, acc0, disp_map, disp0, pred_hyp, z_std,
+    z_vals and z_vals0 as VIEWS of the plan's workspace -- valid until that plan's next step, like last_pixels; `raw`,
+    `weights`, `weights0` and `u` are not provided on this route.  With one_call=True the depth scales' and shifts' Adam is
+    plnerf_depth_ss_adam on EVERY step of this object, one-call or not (moments in a [2, V] pair the step owns: a mixed run
+    has one arithmetic); with one_call=False it stays torch.optim.Adam."""
 
     def __init__(self, args, render_kwargs_train, optimizer, grad_vars, distributed=None, range_check_every=100, seed=0,
-                 counter_rng=True, start=0, n_views=None):
+                 counter_rng=True, start=0, n_views=None, one_call=False):
         """counter_rng: the step's draws (stratified jitter, importance samples, the hypotheses' u) come from a
         functional.DrawSource keyed on (seed, step, GLOBAL ray id) and are generated inside the kernels that consume
         them -- a global batch gives the same step whether one rank renders it or N ranks a shard each, like
@@ -725,6 +738,11 @@ class DepthTrainStep:
         # DEPTH_SCALES / DEPTH_SHIFTS [V, 1] and their own Adam (:1071-1082)
         self.depth_scales = self.depth_shifts = self.optimizer_ss = None
         self._ss_grad = None
+        self.one_call = bool(one_call)
+        self.one_call_steps = 0
+        self._plan = self._plan_key = None
+        self._ss_m = self._ss_v = None      # one_call: the scale / shift Adam's moments [2, V] and its step count
+        self._ss_steps = 0
         # the 16-bit modes guard their Adam steps with the networks' range status words; the host looks every
         # `range_check_every` steps, as train.TrainStep does (0: never -- the caller does)
         self.range_check_every = int(range_check_every)
@@ -752,9 +770,13 @@ class DepthTrainStep:
         ones = torch.ones((int(n_views), 1), dtype=torch.float, device=device)
         self.depth_scales = (ones * getattr(a, "scale_init", 1.0)).requires_grad_(True)
         self.depth_shifts = (ones * getattr(a, "shift_init", 0.0)).requires_grad_(True)
-        self.optimizer_ss = torch.optim.Adam(params=(self.depth_scales, self.depth_shifts),
-                                             lr=getattr(a, "scaleshift_lr", 1e-6))
         self._ss_grad = torch.zeros(2, int(n_views), device=device)
+        if self.one_call:      # plnerf_depth_ss_adam: torch.optim.Adam's defaults, moments and step count kept here
+            self.optimizer_ss = None
+            self._ss_m, self._ss_v, self._ss_steps = torch.zeros_like(self._ss_grad), torch.zeros_like(self._ss_grad), 0
+        else:
+            self.optimizer_ss = torch.optim.Adam(params=(self.depth_scales, self.depth_shifts),
+                                                 lr=getattr(a, "scaleshift_lr", 1e-6))
 
     def learning_rate(self, i=None):
         """The rate the schedule writes into every param group before iteration i (default: the next one,
@@ -794,6 +816,10 @@ class DepthTrainStep:
         if lr is not None:      # train_utils/hyperparameter_update.py:3-5
             for group in self.optimizer.param_groups:
                 group['lr'] = lr
+        if self.one_call:
+            done = self._step_view_one_call(views, img_i, n_rand, i)
+            if done is not None:
+                return done
         cols, target_s, target_h, mask, hyp_raw, pix = views.select(
             img_i, self.global_step, n_rand, ray_id0=self.rank * n_rand, scale=self.depth_scales, shift=self.depth_shifts,
             seed=self.seed, want_viewdirs=bool(self.kw.get("use_viewdirs", True)), want_extras=True)
@@ -803,6 +829,84 @@ class DepthTrainStep:
                             getattr(a, "space_carving_weight", 0.)):
             ss = (int(img_i), hyp_raw)
         return self._step(cols, target_s, target_h, mask, None, False, ss)
+
+    def _one_call_ok(self, views, n_rays):
+        """Can this step go to the library as one call (plnerf_depth_train_step)?  What the entry enqueues is the fused route
+        of _step with the merged backward: two native networks in one 16-bit guarded precision and with one density
+        activation, piecewise-linear mode with importance sampling, counter-based draws, the kernels' own encoding on an
+        identity bounding box, no camera code, a batch that fits one launch per network, one process, nobody watching the
+        stages (STAGE_TAP, functional.KERNEL_TIMER), not `pytest`."""
+        kw = self.kw
+        if not (self.merged_backward and self.draws is not None and self.bucket is None and len(self.nets) == 2):
+            return None
+        if STAGE_TAP is not None or Fn.KERNEL_TIMER is not None or not FUSE_STAGES or not isinstance(views, DepthViews):
+            return None
+        S, N = int(kw.get("N_samples", 0)), int(kw.get("N_importance", 0))
+        if kw.get("mode") != "linear" or kw.get("color_mode") not in ("midpoint", "left") or kw.get("pytest", False) or \
+                not kw.get("use_viewdirs", False) or N < 1 or S < 2 or S + N > L.DEPTH_STEP_MAX_SAMPLES:
+            return None
+        if kw.get("precomputed_z_samples") is not None or kw.get("cached_u") is not None:
+            return None
+        cam = kw.get("embedded_cam")
+        if cam is not None and cam.numel() > 0:
+            return None
+        if not 1 <= n_rays or n_rays * (S + N) > MAX_ROWS_PER_LAUNCH:
+            return None
+        qfn = kw.get("network_query_fn")
+        emb, box = getattr(qfn, "embedders", None), getattr(qfn, "box", None)      # (create_nerf's query function says them)
+        if emb is None or box is None:
+            return None
+        enc = _kernel_encoding(emb[0], emb[1], True)
+        if enc is None or not _host_box(*box)[2]:
+            return None
+        fx, fd, scale = enc
+        c, f = self.nets
+        ok = c is not f and c.precision == f.precision and c.density_beta == f.density_beta and all(
+            n.is_native() and n.precision in L.GUARDED_PRECISIONS and n.has_fused_encoding() and n.input_ch == 3 + 6 * fx
+            and n.input_ch_views == 3 + 6 * fd and all(p.is_cuda and p.requires_grad and p.device == views.device
+                                                       for p in n.param_list()) for n in (c, f))
+        return scale if ok else None
+
+    def _plan_for(self, views, max_rays, input_scale):
+        """The DepthStepPlan of this configuration: the one in hand while it still describes the live buffers, else a new
+        one (None: the optimizer is not a FlatAdam over exactly the two networks)."""
+        from . import stepplan
+        key = stepplan.depth_plan_key(self.args, self.kw, max_rays, views, self.seed) + (input_scale,) + tuple(
+            t.data_ptr() for t in (self.depth_scales, self.depth_shifts, self._ss_grad, self._ss_m, self._ss_v))
+        plan = self._plan
+        if plan is not None and key == self._plan_key and plan.current():
+            return plan
+        self._plan = self._plan_key = None
+        if not stepplan.DepthStepPlan.supported(self.nets, self.optimizer):
+            return None
+        self._plan = stepplan.DepthStepPlan(self.args, self.kw, self.nets, self.optimizer, views, max_rays, self.seed,
+                                            input_scale, self.depth_scales.detach(), self.depth_shifts.detach(), self._ss_grad,
+                                            self._ss_m, self._ss_v)
+        self._plan_key = key
+        return self._plan
+
+    def _step_view_one_call(self, views, img_i, n_rand, i):
+        """step_view through plnerf_depth_train_step; None when the step does not qualify (nothing has happened then)."""
+        input_scale = self._one_call_ok(views, n_rand)
+        if input_scale is None or not 0 <= int(img_i) < views.n_views or self.rank * n_rand + n_rand > views.H * views.W:
+            return None
+        plan = self._plan_for(views, n_rand, input_scale)
+        adam_step = plan.adam_step() if plan is not None else None
+        if adam_step is None:
+            return None
+        a = self.args
+        weight, warm = getattr(a, "space_carving_weight", 0.), getattr(a, "warm_start_nerf", 0)
+        ss_step = scaleshift_steps(i, warm, getattr(a, "freeze_ss", 0), weight)
+        if ss_step:
+            self._ss_steps += 1
+        loss5 = plan.run(int(img_i), n_rand, self.global_step, self.rank * n_rand, self.optimizer.param_groups[0]['lr'],
+                         adam_step, weight > 0. and i > warm, ss_step, float(getattr(a, "scaleshift_lr", 1e-6)), self._ss_steps)
+        self.last_pixels = plan.view_of("pixels", (n_rand, 2), torch.int32)
+        self.global_step += 1
+        self.one_call_steps += 1
+        if self.range_check_every and self.global_step % self.range_check_every == 0:
+            self.check_range()
+        return loss5[0], loss5[1], loss5[3], plan.outputs(n_rand)
 
     def __call__(self, ray_batch, target_s, target_h, space_carving_mask=None, cached_u=None, pytest=False):
         return self._step(ray_batch, target_s, target_h, space_carving_mask, cached_u, pytest)
@@ -881,7 +985,8 @@ class DepthTrainStep:
         ss_step = ss is not None and carve
         if ss_step and ss_work is not None:
             ss_work.wait()
-            self._ss_grad.mul_(1.0 / self.world)
+            if not self.one_call:      # (plnerf_depth_ss_adam takes the factor as its grad_scale)
+                self._ss_grad.mul_(1.0 / self.world)
         if flat_adam:
             # clip_grad_value_(0.1) folded into the step kernel (:1156), applied to the averaged gradient
             self.optimizer.step(clip_value=0.1, grad_scale=scale, guards=tails)
@@ -890,7 +995,14 @@ class DepthTrainStep:
         else:
             torch.nn.utils.clip_grad_value_(self.grad_vars, 0.1)
             self.optimizer.step()
-        if ss_step:      # (:1159-1161: after the networks' step, no clipping)
+        if ss_step and self.one_call:
+            self._ss_steps += 1
+            L.check(L.lib().plnerf_depth_ss_adam(
+                L.dptr(self.depth_scales.detach(), "depth_scales"), L.dptr(self.depth_shifts.detach(), "depth_shifts"),
+                L.dptr(self._ss_grad), L.dptr(self._ss_m), L.dptr(self._ss_v), self._ss_grad.shape[1],
+                float(getattr(a, "scaleshift_lr", 1e-6)), 0.9, 0.999, 1e-8, self._ss_steps,
+                1.0 / self.world if ss_work is not None else 1.0, L.stream()), "plnerf_depth_ss_adam")
+        elif ss_step:      # (:1159-1161: after the networks' step, no clipping)
             self.depth_scales.grad = self._ss_grad[0].reshape(-1, 1)
             self.depth_shifts.grad = self._ss_grad[1].reshape(-1, 1)
             self.optimizer_ss.step()

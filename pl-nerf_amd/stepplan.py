@@ -27,19 +27,26 @@ def plan_key(kw, kind, max_rays, H, W, K, near, far, bank, seed):
 
 
 class _NetSlot:
-    """One network, its optimizer and the device addresses the plan recorded for them."""
+    """One network, its optimizer and the device addresses the plan recorded for them.  The network's 24 parameters are
+    parameters `first` .. `first + 23` of the optimizer's one flat group: all of it (an optimizer per network, StepPlan)
+    or one half (the depth loop's one optimizer over both networks, DepthStepPlan)."""
 
-    def __init__(self, net, opt, grad_flat, io_net, others):
+    def __init__(self, net, opt, grad_flat, io_net, others, first=0, launches=1):
         self.net, self.opt, self.io = net, opt, io_net
         self.group = opt.param_groups[0]
-        self.ps = self.group['params']
+        self.all_ps = self.group['params']
         self.fl = opt._flat[0]
         self.precision = net.precision
-        sizes = self.fl['sizes']
+        sizes = self.fl['sizes'][first:first + L.N_PARAM_TENSORS]
+        self.ps = self.all_ps[first:first + L.N_PARAM_TENSORS]
         self.n = sum(sizes)
         self.last_off = self.n - sizes[-1]
-        self.base = self.fl['param'].data_ptr()
-        self.m_ptr, self.v_ptr = self.fl['m'].data_ptr(), self.fl['v'].data_ptr()
+        self.launches = launches           # plnerf_adam_step launches of one step of `opt` (FlatAdam._launches_per_step)
+        lo = 4 * sum(self.fl['sizes'][:first])
+        self.flat_ptr = self.fl['param'].data_ptr()
+        self.base = self.flat_ptr + lo
+        self.m_ptr, self.v_ptr = self.fl['m'].data_ptr() + lo, self.fl['v'].data_ptr() + lo
+        self.lo = lo
         net.status_word()                  # (allocates the packed buffer and zeroes its status word, if that is still to do)
         self.packed_ptr = net._packed.data_ptr()
         self.grad_flat = grad_flat         # [n + GRAD_TAIL]
@@ -72,10 +79,10 @@ class _NetSlot:
     def current(self):
         ps, fl, net, opt = self.ps, self.fl, self.net, self.opt
         pk = net._packed
-        return (opt._flat[0] is fl and opt.param_groups[0] is self.group and self.group['params'] is ps and
-                fl['param'].data_ptr() == self.base and ps[0].data.data_ptr() == self.base and
-                ps[-1].data.data_ptr() == self.base + 4 * self.last_off and fl['m'].data_ptr() == self.m_ptr and
-                fl['v'].data_ptr() == self.v_ptr and pk is not None and pk.data_ptr() == self.packed_ptr and
+        return (opt._flat[0] is fl and opt.param_groups[0] is self.group and self.group['params'] is self.all_ps and
+                fl['param'].data_ptr() == self.flat_ptr and ps[0].data.data_ptr() == self.base and
+                ps[-1].data.data_ptr() == self.base + 4 * self.last_off and fl['m'].data_ptr() + self.lo == self.m_ptr and
+                fl['v'].data_ptr() + self.lo == self.v_ptr and pk is not None and pk.data_ptr() == self.packed_ptr and
                 net.precision == self.precision and opt._withheld is self.withheld and len(opt.guards) == len(self.guards) and
                 all(a is b for a, b in zip(opt.guards, self.guards)))
 
@@ -96,7 +103,7 @@ class _NetSlot:
         torch._foreach_add_(self.steps, 1.0)
         self.fl['uniform_step'] = float(self.steps[0])
         self.opt._guarded_now = bool(self.guards)
-        self.opt._launches_per_step = 1
+        self.opt._launches_per_step = self.launches
         ps, grads = self.ps, self.grads
         if ps[0].grad is not grads[0] or ps[-1].grad is not grads[-1]:      # (the other route, or a zero_grad, replaced them)
             for p, g in zip(ps, grads):
@@ -209,3 +216,140 @@ class StepPlan:
         self.slots[0].advance()
         self.slots[1].advance()
         return loss4
+
+
+def depth_plan_key(args, kw, max_rays, views, seed):
+    """Everything a DepthStepPlan's config is built from (the DepthViews by identity; current() watches their tensors)."""
+    g = lambda name, default: getattr(args, name, default)
+    return (int(max_rays), id(views), int(seed), int(kw["N_samples"]), int(kw["N_importance"]), kw["color_mode"],
+            bool(kw.get("lindisp", False)), kw.get("perturb", 0.) > 0., bool(kw.get("white_bkgd", False)),
+            float(kw.get("raw_noise_std", 0.)), float(kw.get("zero_tol", 1e-4)), float(kw.get("epsilon", 1e-3)),
+            bool(g("is_joint", False)), float(g("space_carving_weight", 0.)), float(g("space_carving_threshold", 0.0)),
+            L.FWD_KERNEL)
+
+
+class DepthStepPlan:
+    """The host side of plnerf_depth_train_step (include/plnerf_hip_depthstep.h), StepPlan's sibling for the depth loop:
+    nets = (coarse, fine) stepped by ONE FlatAdam `opt` whose one flat group holds exactly their 48 parameters, coarse
+    first (depth.create_nerf); `views` a depth.DepthViews; scale, shift: DEPTH_SCALES / DEPTH_SHIFTS [V, 1]; ss_grad,
+    ss_m, ss_v [2, V]: their dense gradient and Adam moments.  The workspace is zeroed once (the loss kernel's partials);
+    a step's rendered outputs are views of it (outputs()), valid until this plan's next step."""
+    CLIP_VALUE = 0.1      # clip_grad_value_ of run_nerf_sample_based_depth.py:1156
+
+    @staticmethod
+    def supported(nets, opt):
+        if not (isinstance(opt, FlatAdam) and len(opt.param_groups) == 1 and len(opt._flat) == 1 and opt._flat[0] is not None):
+            return False
+        group = opt.param_groups[0]
+        ps, plist = group['params'], list(nets[0].param_list()) + list(nets[1].param_list())
+        if len(ps) != len(plist) or any(a is not b for a, b in zip(ps, plist)):
+            return False
+        if group.get('weight_decay', 0) or group.get('amsgrad') or group.get('maximize'):
+            return False
+        return all(isinstance(g, torch.Tensor) or any(g is n for n in nets) for g in opt.guards)
+
+    def __init__(self, args, kw, nets, opt, views, max_rays, seed, input_scale, scale, shift, ss_grad, ss_m, ss_v,
+                 ss_betas=(0.9, 0.999), ss_eps=1e-8):
+        coarse, fine = nets
+        dev = coarse.param_list()[0].device
+        g = lambda name, default: getattr(args, name, default)
+        self.device, self.views = dev, views
+        cfg = self.config = L.DepthStepConfig()
+        cfg.max_rays, cfg.n_samples, cfg.n_importance = int(max_rays), int(kw["N_samples"]), int(kw["N_importance"])
+        cfg.color_mode = L.COLOR[kw["color_mode"]]
+        cfg.lindisp, cfg.perturb = int(bool(kw.get("lindisp", False))), int(kw.get("perturb", 0.) > 0.)
+        cfg.white_bkgd = int(bool(kw.get("white_bkgd", False)))
+        cfg.raw_noise_std = float(kw.get("raw_noise_std", 0.))
+        cfg.zero_tol, cfg.epsilon = float(kw.get("zero_tol", 1e-4)), float(kw.get("epsilon", 1e-3))
+        cfg.n_views, cfg.H, cfg.W, cfg.n_hyp = views.n_views, views.H, views.W, views.n_hyp
+        cfg.pose_rows = int(views.poses.shape[1])
+        cfg.near, cfg.far = float(views.near), float(views.far)
+        cfg.precision, cfg.fwd_kernel = L.PRECISION[coarse.precision], L.FWD_KERNEL
+        cfg.input_ch, cfg.input_ch_views = int(coarse.input_ch), int(coarse.hip_view_ch)
+        cfg.input_scale, cfg.density_beta = float(input_scale), float(coarse.density_beta)
+        cfg.is_joint = int(bool(g("is_joint", False)))
+        cfg.space_carving_weight = float(g("space_carving_weight", 0.))
+        cfg.space_carving_threshold = float(g("space_carving_threshold", 0.0))
+        cfg.clip_value = self.CLIP_VALUE
+        group = opt.param_groups[0]
+        cfg.beta1, cfg.beta2, cfg.adam_eps = float(group['betas'][0]), float(group['betas'][1]), float(group['eps'])
+        cfg.ss_beta1, cfg.ss_beta2, cfg.ss_adam_eps = float(ss_betas[0]), float(ss_betas[1]), float(ss_eps)
+        cfg.seed = int(seed)
+        nbytes = L.lib().plnerf_depth_train_step_workspace_bytes(ctypes.byref(cfg))
+        if nbytes == 0:
+            raise ValueError("plnerf_depth_train_step refuses this configuration")
+        raw = torch.zeros((nbytes + L.STEP_WORKSPACE_ALIGN) // 4 + 1, device=dev, dtype=torch.float32)
+        pad = (-raw.data_ptr()) % L.STEP_WORKSPACE_ALIGN
+        self.workspace = raw[pad // 4:]
+        self.workspace_bytes = nbytes
+        self.layout = L.DepthStepViews()
+        L.check(L.lib().plnerf_depth_train_step_layout(ctypes.byref(cfg), ctypes.byref(self.layout)),
+                "plnerf_depth_train_step_layout")
+        self.t_vals = Fn.cpu_linspace(cfg.n_samples, dev)
+        self.u_vals = Fn.cpu_linspace(cfg.n_importance, dev)
+        # both networks' gradients back to back in one allocation, a GRAD_TAIL behind each: functional._mlp_backward_launch's
+        # layout, which FlatAdam.step walks as two runs (one plnerf_adam_step launch each)
+        fl = opt._flat[0]
+        n24 = L.N_PARAM_TENSORS
+        sizes = [sum(fl['sizes'][:n24]) + Fn.GRAD_TAIL, sum(fl['sizes'][n24:]) + Fn.GRAD_TAIL]
+        self.grad_block = torch.zeros(sum(sizes), device=dev, dtype=torch.float32)
+        io = self.io = L.DepthStepIo()
+        self.slots = (_NetSlot(coarse, opt, self.grad_block[:sizes[0]], io.coarse, nets, first=0, launches=2),
+                      _NetSlot(fine, opt, self.grad_block[sizes[0]:], io.fine, nets, first=n24, launches=2))
+        io.t_vals, io.u_vals = self.t_vals.data_ptr(), self.u_vals.data_ptr()
+        self.tensors = (views.images, views.hypotheses, views.valid, views.poses, views.intrinsics, scale, shift, ss_grad,
+                        ss_m, ss_v)
+        self.ptrs = self._tensor_ptrs()
+        (io.images, io.hyp, io.valid, io.poses, io.intrinsics, io.scale, io.shift, io.ss_grad, io.ss_exp_avg,
+         io.ss_exp_avg_sq) = self.ptrs
+        self.args = L.DepthStepArgs()
+        self._refs = (ctypes.byref(cfg), ctypes.byref(io), ctypes.byref(self.args), ctypes.c_void_p(self.workspace.data_ptr()))
+
+    def _tensor_ptrs(self):
+        v = self.views
+        live = (v.images, v.hypotheses, v.valid, v.poses, v.intrinsics) + self.tensors[5:]
+        return tuple(None if t is None else t.data_ptr() for t in live)
+
+    def current(self):
+        """Does every address the structs hold still belong to the live objects (networks, optimizer, the DepthViews'
+        tensors, the scale / shift buffers)?"""
+        return self.slots[0].current() and self.slots[1].current() and self._tensor_ptrs() == self.ptrs
+
+    def adam_step(self):
+        """The optimizer's step count after this update, or None when its 48 parameters disagree on theirs."""
+        c, f = self.slots[0].next_adam_step(), self.slots[1].next_adam_step()
+        return c if (c is not None and c == f) else None
+
+    def run(self, view, rays, step, ray_id0, lr, adam_step, carve, ss_step=False, ss_lr=0.0, ss_adam_step=0):
+        """Enqueue one step on the current stream; returns its loss5 = [total, image, image (coarse), space carving, psnr]
+        (a fresh tensor: an earlier step's stays what it was)."""
+        a = self.args
+        a.view, a.rays, a.step, a.ray_id0 = view, rays, step, ray_id0
+        a.lr, a.adam_step = lr, adam_step
+        a.carve, a.ss_step, a.ss_lr, a.ss_adam_step = int(carve), int(ss_step), ss_lr, ss_adam_step
+        loss5 = torch.empty(5, device=self.device)
+        self.io.loss5 = loss5.data_ptr()
+        cfg, io, args, ws = self._refs
+        L.check(L.lib().plnerf_depth_train_step(cfg, io, args, ws, self.workspace_bytes, L.stream()), "plnerf_depth_train_step")
+        self.slots[0].advance()
+        self.slots[1].advance()
+        return loss5
+
+    def view_of(self, name, shape, dtype=torch.float32):
+        """One of the layout's outputs as a tensor over the workspace (no copy)."""
+        off = getattr(self.layout, name) // 4
+        n = 1
+        for s in shape:
+            n *= s
+        t = self.workspace[off:off + n]
+        return (t if dtype == torch.float32 else t.view(dtype)).view(*shape)
+
+    def outputs(self, R):
+        """The step's rendered tensors under the reference's keys, as views of the workspace: valid until this plan's next
+        step."""
+        S, N = self.config.n_samples, self.config.n_importance
+        v = self.view_of
+        return {'rgb_map': v("rgb", (R, 3)), 'rgb0': v("rgb0", (R, 3)), 'depth_map': v("depth", (R,)), 'depth0': v("depth0", (R,)),
+                'acc_map': v("acc", (R,)), 'acc0': v("acc0", (R,)), 'disp_map': v("disp", (R,)), 'disp0': v("disp0", (R,)),
+                'pred_hyp': v("pred_hyp", (R, N)), 'z_std': v("z_std", (R,)), 'z_vals': v("z_vals", (R, S + N)),
+                'z_vals0': v("z_vals0", (R, S))}
