@@ -130,6 +130,12 @@ def sample_error_workspace_bytes(R):
     return -(-R // SAMPLEERR_RAYS_PER_GROUP) * SAMPLEERR_ROW * 8 if R > 0 else 0
 
 
+# ... and include/plnerf_hip_constepi.h (ABI 601): piecewise-constant mode's coarse epilogue and final stage, one launch each
+CONSTEPI_SIGNATURES = {
+    "plnerf_coarse_epilogue_const": (c_i, [c_f] * 8 + [c_i, ctypes.c_uint64, ctypes.c_uint32] + [c_i] * 5 + [c_f] * 8 + [c_s]),
+    "plnerf_fine_epilogue_const": (c_i, [c_f] * 7 + [c_i, ctypes.c_uint64, ctypes.c_uint32] + [c_i] * 5 + [c_f] * 10 + [c_s]),
+}
+
 # ... and include/plnerf_hip_step.h (ABI 601): one call = one optimisation step.  The three structs live in host memory;
 # every pointer field is a device pointer (c_void_p: assign `tensor.data_ptr()`).
 STEP_RAYS_VIEW, STEP_RAYS_BANK = 0, 1      # PLNERF_STEP_RAYS_*
@@ -242,7 +248,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-                list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + list(DEPTHSTEP_SIGNATURES.items()):
+                list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()) + list(CONSTEPI_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + \
+                list(DEPTHSTEP_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

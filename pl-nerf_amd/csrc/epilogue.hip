@@ -12,9 +12,16 @@
 // function is the one the separate kernels use (ray_dev.h), so the results are bit-identical to
 // plnerf_quad_fwd -> plnerf_sample_pl -> plnerf_merge_sort -> plnerf_ray_points
 // (tests/test_gpu_parity.py::test_fused_coarse_epilogue_equals_separate_launches).
+//
+// Piecewise-constant mode (MODE = PLNERF_MODE_CONSTANT: the vanilla-NeRF baseline, `constant_init`, the depth script's
+// constant configuration) is the same kernel with compute_weights (run_plnerf.py:504-513) as the quadrature and sample_pdf
+// (run_nerf_helpers.py:241-284) on z_mid / weights[1:-1] as the sampler -- bit-identical to
+// plnerf_quad_fwd -> torch z_mid -> plnerf_sample_const -> plnerf_merge_sort -> plnerf_ray_points
+// (tests/test_gpu_const_epilogue.py); entry points in include/plnerf_hip_constepi.h.
 #include "common.h"
 #include "philox.h"
 #include "ray_dev.h"
+#include "../../include/plnerf_hip_constepi.h"
 
 using namespace plnerf;
 
@@ -36,7 +43,7 @@ struct EpiArgs {
     float* disp_map;
     float* acc_map;
     float* depth_map;
-    float* weights;          // optional [R, S+1]
+    float* weights;          // optional [R, S+1] (constant mode: [R, S])
     float* tau;              // optional [R, S+2]
     float* T;                // optional [R, S+2]
     float* z_fine;           // [R, S+N]
@@ -46,6 +53,7 @@ struct EpiArgs {
     float* samples;          // [R, N], NOT clamped
     int64_t* inds;           // [R, N] searchsorted indices (plnerf_sample_pl_bwd wants them)
     float* u_out;            // [R, N] the draws used (the variant's render_rays returns them)
+    float* bins_out;         // constant mode, optional [R, S-1]: the sampler's bins z_mid (plnerf_sample_const_bwd wants them)
 };
 
 // HYP = false: the coarse pass's epilogue (samples clamped, merged, sorted, turned into positions).
@@ -53,20 +61,22 @@ struct EpiArgs {
 // (run_nerf_sample_based_depth.py:923-934): the samples are the depth hypotheses pred_hyp -- not clamped, kept with their
 // indices and draws for the sampler's backward -- and z_std is theirs (:934); nothing is sorted or positioned.
 // KPL: registers per lane of the general sort network (64 KPL >= S + N); KS: of the samples' own network (64 KS >= N)
-template <int KPL, bool HYP, int KS = KPL>
+// MODE: the quadrature rule and its sampler.  Constant mode keeps the row layout: Tr holds the sampler's weights
+// w[1:-1] + 1e-5, cdf the S - 1 entries of [0, cumsum(pdf)]; the bins z_mid are formed from zk where they are read.
+template <int KPL, bool HYP, int KS = KPL, int MODE = PLNERF_MODE_LINEAR>
 __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
-    constexpr int MODE = PLNERF_MODE_LINEAR;
+    constexpr bool LINEAR = MODE == PLNERF_MODE_LINEAR;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int ray = blockIdx.x * WAVES + wave;
     const bool live = ray < a.R;
     if (!live) ray = a.R - 1;
-    const int S = a.S, K = S + 2, n = S + 1, N = a.N, NF = S + N;
+    const int S = a.S, K = S + 2, n = LINEAR ? S + 1 : S, N = a.N, NF = S + N;
     float* zk = smem + (size_t)wave * a.lds_stride;   // K knots [near, z, far]
     float* tau = zk + K;                               // K
     float* col = tau + K;                              // 3 S
-    float* Tr = col + 3 * S;                           // K
-    float* cdf = Tr + K;                               // K
+    float* Tr = col + 3 * S;                           // K  (constant mode: the sampler's S - 2 weights)
+    float* cdf = Tr + K;                               // K  (constant mode: S - 1 entries)
     float* smp = cdf + K;                              // N clamped samples; later the sorted row (NF, aliases col..)
     float dnorm;
     load_ray(a.in, ray, lane, zk, tau, col, dnorm);
@@ -94,18 +104,21 @@ __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
             sb += (double)(w * elem_colour<MODE>(i, 2, S, col, a.color_mode, a.farcolorfix));
             sd += (double)(w * elem_depth<MODE>(i, zk));
             sa += (double)w;
-            Tr[i + 1] = Tn;
+            if constexpr (LINEAR) Tr[i + 1] = Tn;
+            else if (i >= 1 && i < S - 1) Tr[i - 1] = w + 1e-5f;      // sample_pdf's weights[..., 1:-1] + 1e-5
             if (live) {
                 if (a.weights) a.weights[(size_t)ray * n + i] = w;
-                if (a.T) a.T[(size_t)ray * K + i + 1] = Tn;
+                if (LINEAR && a.T) a.T[(size_t)ray * K + i + 1] = Tn;
             }
         }
-        // cdf = [0, cumsum(weights)] (fp64 running sum, each entry rounded to fp32), as sample_pl_kernel builds it
-        const double cincl = wave_incl_sum((double)w);
-        if (valid) cdf[i + 1] = (float)(ccarry + cincl);
-        ccarry = ccarry + __shfl(cincl, 63);
+        if constexpr (LINEAR) {
+            // cdf = [0, cumsum(weights)] (fp64 running sum, each entry rounded to fp32), as sample_pl_kernel builds it
+            const double cincl = wave_incl_sum((double)w);
+            if (valid) cdf[i + 1] = (float)(ccarry + cincl);
+            ccarry = ccarry + __shfl(cincl, 63);
+        }
     }
-    if (live) {
+    if (LINEAR && live) {
         if (a.T && lane == 0) a.T[(size_t)ray * K] = 1.0f;
         if (a.tau)
             for (int s = lane; s < K; s += 64) a.tau[(size_t)ray * K + s] = tau[s];
@@ -126,27 +139,61 @@ __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
         a.disp_map[ray] = 1.0f / tmax(1e-10f, depth / acc);
     }
     __syncthreads();
-    if (lane == 0) { Tr[0] = 1.0f; cdf[0] = 0.0f; cdf[K - 1] = 1.0f; }
+    const int B = S - 1;          // (constant mode) bins z_mid = cdf entries
+    if constexpr (LINEAR) {
+        if (lane == 0) { Tr[0] = 1.0f; cdf[0] = 0.0f; cdf[K - 1] = 1.0f; }
+    } else {
+        // cdf = [0, cumsum(pdf)], pdf = w' / sum(w') (sample_const_kernel's: torch.sum's order, IEEE division, fp64 running
+        // sum rounded per entry; the last entry is what the sum gives, not forced to 1)
+        const float total = torch_row_sum(Tr, B - 1, lane);
+        for (int base = 0; base < B - 1; base += 64) {
+            const int j = base + lane;
+            const float pdf = (j < B - 1) ? Tr[j] / total : 0.0f;
+            const double cincl = wave_incl_sum((double)pdf);
+            if (j < B - 1) cdf[j + 1] = (float)(ccarry + cincl);
+            ccarry = ccarry + __shfl(cincl, 63);
+        }
+        if (lane == 0) cdf[0] = 0.0f;
+        if constexpr (HYP) {
+            if (live && a.bins_out)
+                for (int j = lane; j < B; j += 64) a.bins_out[(size_t)ray * B + j] = 0.5f * (zk[j + 2] + zk[j + 1]);
+        }
+    }
     __syncthreads();
 
-    // ---- importance samples (sample_pl_kernel's loop), clamped to [near, far] ----
+    // ---- importance samples (sample_pl_kernel's / sample_const_kernel's loop), clamped to [near, far] ----
     const float lo = zk[0], hi = zk[K - 1];
-    const float zt = a.zero_tol, eps = a.eps;
+    [[maybe_unused]] const float zt = a.zero_tol, eps = a.eps;
     double ssum = 0.0;
     for (int k = lane; k < N; k += 64) {
         const float u = a.u ? a.u[(size_t)ray * a.u_row_stride + k] : rng_uniform(a.rng, a.rng.ray_id0 + ray, k);
-        const int ind = upper_bound(cdf, K, u);
-        const int below = ind - 1 > 0 ? ind - 1 : 0;
-        const int above = ind < K - 1 ? ind : K - 1;
-        const float s0 = zk[below], s1 = zk[above];
-        const float T0 = Tr[below];
-        const float tau0 = tau[below], tau1 = tau[above];
-        const int di = below < S ? below : S;
-        const float d = tau[di + 1] - tau[di];
-        float out = (d < zt && d > -zt) ? s0 : -1.0f;
-        const bool rising = d >= zt;
-        if (rising || d <= -zt) out = invert_segment(s0, s1, T0, tau0, tau1, u, eps, rising);      // (one evaluation, operands selected per lane)
-        if (out != out) out = s0;
+        int ind;
+        float out;
+        if constexpr (LINEAR) {
+            ind = upper_bound(cdf, K, u);
+            const int below = ind - 1 > 0 ? ind - 1 : 0;
+            const int above = ind < K - 1 ? ind : K - 1;
+            const float s0 = zk[below], s1 = zk[above];
+            const float T0 = Tr[below];
+            const float tau0 = tau[below], tau1 = tau[above];
+            const int di = below < S ? below : S;
+            const float d = tau[di + 1] - tau[di];
+            out = (d < zt && d > -zt) ? s0 : -1.0f;
+            const bool rising = d >= zt;
+            if (rising || d <= -zt) out = invert_segment(s0, s1, T0, tau0, tau1, u, eps, rising);      // (one evaluation, operands selected per lane)
+            if (out != out) out = s0;
+        } else {
+            ind = upper_bound(cdf, B, u);
+            const int below = ind - 1 > 0 ? ind - 1 : 0;
+            const int above = ind < B - 1 ? ind : B - 1;
+            const float c0 = cdf[below], c1 = cdf[above];
+            float denom = c1 - c0;
+            if (denom < 1e-5f) denom = 1.0f;
+            const float t = (u - c0) / denom;
+            // z_mid = .5 * (z[1:] + z[:-1]) of the two bins
+            const float b0 = 0.5f * (zk[below + 2] + zk[below + 1]), b1 = 0.5f * (zk[above + 2] + zk[above + 1]);
+            out = b0 + t * (b1 - b0);
+        }
         if constexpr (HYP) {
             if (live) {
                 a.samples[(size_t)ray * N + k] = out;
@@ -269,15 +316,33 @@ __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
     }
 }
 
-template <int KPL, bool HYP = false, int KS = KPL>
+template <int KPL, bool HYP = false, int KS = KPL, int MODE = PLNERF_MODE_LINEAR>
 int launch(const EpiArgs& a, size_t lds, hipStream_t st) {
     if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)coarse_epilogue_kernel<KPL, HYP, KS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-    hipLaunchKernelGGL((coarse_epilogue_kernel<KPL, HYP, KS>), dim3((a.R + WAVES - 1) / WAVES), dim3(WAVES * 64), lds, st, a);
+        (void)hipFuncSetAttribute((const void*)coarse_epilogue_kernel<KPL, HYP, KS, MODE>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((coarse_epilogue_kernel<KPL, HYP, KS, MODE>), dim3((a.R + WAVES - 1) / WAVES), dim3(WAVES * 64), lds, st,
+                       a);
     PLNERF_CHECK_LAUNCH();
     return PLNERF_OK;
 }
+
+// The coarse form's tiers.  (KS: the samples' own network; the small shapes get every size, the large ones sort their
+// samples on the full width)
+template <int MODE>
+int launch_coarse(const EpiArgs& a, size_t lds, hipStream_t st) {
+    const int nf = a.S + a.N, N = a.N;
+    if (nf <= 64) return launch<1, false, 1, MODE>(a, lds, st);
+    if (nf <= 128) return N <= 64 ? launch<2, false, 1, MODE>(a, lds, st) : launch<2, false, 2, MODE>(a, lds, st);
+    if (nf <= 256)
+        return N <= 64 ? launch<4, false, 1, MODE>(a, lds, st)
+                       : (N <= 128 ? launch<4, false, 2, MODE>(a, lds, st) : launch<4, false, 4, MODE>(a, lds, st));
+    if (nf <= 512) return launch<8, false, 8, MODE>(a, lds, st);
+    return launch<16, false, 16, MODE>(a, lds, st);
+}
+
+// zk, tau, Tr, cdf: 4 (S+2); col 3 S; samples N   (the sorted row of S + N <= 3 S + 2 (S+2) + N reuses col onwards)
+inline int lds_row(int S, int N) { return ((4 * (S + 2) + 3 * S + N) + 3) & ~3; }
 
 }  // namespace
 
@@ -304,18 +369,10 @@ extern "C" int plnerf_coarse_epilogue(const float* raw, const float* z, const fl
     a.zero_tol = zero_tol; a.eps = epsilon;
     a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
     a.weights = weights; a.tau = tau; a.T = T; a.z_fine = z_fine; a.pts = pts; a.z_std = z_std;
-    // zk, tau, Tr, cdf: 4 (S+2); col 3 S; samples N   (the sorted row of S + N <= 3 S + 2 (S+2) + N reuses col onwards)
-    a.lds_stride = ((4 * (S + 2) + 3 * S + N) + 3) & ~3;
+    a.lds_stride = lds_row(S, N);
     const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
     if (lds > 160 * 1024) return PLNERF_ERANGE;
-    hipStream_t st = (hipStream_t)stream;
-    const int nf = S + N;
-    // (KS: the samples' own network; the small shapes get every size, the large ones sort their samples on the full width)
-    if (nf <= 64) return launch<1>(a, lds, st);
-    if (nf <= 128) return N <= 64 ? launch<2, false, 1>(a, lds, st) : launch<2>(a, lds, st);
-    if (nf <= 256) return N <= 64 ? launch<4, false, 1>(a, lds, st) : (N <= 128 ? launch<4, false, 2>(a, lds, st) : launch<4>(a, lds, st));
-    if (nf <= 512) return launch<8>(a, lds, st);
-    return launch<16>(a, lds, st);
+    return launch_coarse<PLNERF_MODE_LINEAR>(a, lds, (hipStream_t)stream);
 }
 
 
@@ -344,8 +401,63 @@ extern "C" int plnerf_fine_epilogue(const float* raw, const float* z, const floa
     a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
     a.weights = weights; a.tau = tau; a.T = T; a.z_std = z_std;
     a.samples = samples; a.inds = inds; a.u_out = u_out;
-    a.lds_stride = ((4 * (S + 2) + 3 * S + N) + 3) & ~3;
+    a.lds_stride = lds_row(S, N);
     const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
     if (lds > 160 * 1024) return PLNERF_ERANGE;
     return launch<1, true>(a, lds, (hipStream_t)stream);      // (KPL sizes the sort network only: unused here)
+}
+
+
+// ---- piecewise-constant mode (include/plnerf_hip_constepi.h) ----
+extern "C" int plnerf_coarse_epilogue_const(const float* raw, const float* z, const float* near, const float* far,
+                                            const float* rays_o, const float* rays_d, const float* noise, const float* u,
+                                            int u_row_stride, uint64_t seed, uint32_t step, int ray_id0, int R, int S, int N,
+                                            int white_bkgd, float* rgb_map, float* disp_map, float* acc_map,
+                                            float* depth_map, float* weights, float* z_fine, float* pts, float* z_std,
+                                            plnerf_stream_t stream) {
+    if (R < 0 || S < 3 || N < 1) return PLNERF_EINVAL;      // (S >= 3: the sampler needs one interior weight)
+    if (u && u_row_stride != 0 && u_row_stride != N) return PLNERF_EINVAL;
+    if (S > PLNERF_MAX_SAMPLES || S + N > 1024) return PLNERF_ERANGE;
+    if (R == 0) return PLNERF_OK;
+    if (!raw || !z || !near || !far || !rays_o || !rays_d || !rgb_map || !disp_map || !acc_map || !depth_map ||
+        !z_fine || !pts || !z_std)
+        return PLNERF_EINVAL;
+    EpiArgs a{};
+    a.in = RayIn{raw, z, near, far, rays_d, noise, S};
+    a.rays_o = rays_o; a.u = u; a.u_row_stride = u_row_stride;
+    a.rng = RngArgs{(uint32_t)seed, (uint32_t)(seed >> 32), 1u, step, ray_id0, u ? 0 : 1};
+    a.R = R; a.S = S; a.N = N; a.white_bkgd = white_bkgd;
+    a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
+    a.weights = weights; a.z_fine = z_fine; a.pts = pts; a.z_std = z_std;
+    a.lds_stride = lds_row(S, N);
+    const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
+    if (lds > 160 * 1024) return PLNERF_ERANGE;
+    return launch_coarse<PLNERF_MODE_CONSTANT>(a, lds, (hipStream_t)stream);
+}
+
+extern "C" int plnerf_fine_epilogue_const(const float* raw, const float* z, const float* near, const float* far,
+                                          const float* rays_d, const float* noise, const float* u, int u_row_stride,
+                                          uint64_t seed, uint32_t step, int ray_id0, int R, int S, int N, int white_bkgd,
+                                          float* rgb_map, float* disp_map, float* acc_map, float* depth_map, float* weights,
+                                          float* bins_out, float* samples, int64_t* inds, float* u_out, float* z_std,
+                                          plnerf_stream_t stream) {
+    if (R < 0 || S < 3 || N < 1) return PLNERF_EINVAL;
+    if (u && u_row_stride != 0 && u_row_stride != N) return PLNERF_EINVAL;
+    if (S > PLNERF_MAX_SAMPLES || N > 1024) return PLNERF_ERANGE;
+    if (R == 0) return PLNERF_OK;
+    if (!raw || !z || !near || !far || !rays_d || !rgb_map || !disp_map || !acc_map || !depth_map || !weights ||
+        !samples || !inds || !z_std)
+        return PLNERF_EINVAL;
+    EpiArgs a{};
+    a.in = RayIn{raw, z, near, far, rays_d, noise, S};
+    a.u = u; a.u_row_stride = u_row_stride;
+    a.rng = RngArgs{(uint32_t)seed, (uint32_t)(seed >> 32), 4u, step, ray_id0, u ? 0 : 1};      // (stream 4: as plnerf_fine_epilogue)
+    a.R = R; a.S = S; a.N = N; a.white_bkgd = white_bkgd;
+    a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
+    a.weights = weights; a.z_std = z_std;
+    a.samples = samples; a.inds = inds; a.u_out = u_out; a.bins_out = bins_out;
+    a.lds_stride = lds_row(S, N);
+    const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
+    if (lds > 160 * 1024) return PLNERF_ERANGE;
+    return launch<1, true, 1, PLNERF_MODE_CONSTANT>(a, lds, (hipStream_t)stream);
 }

@@ -22,44 +22,6 @@ namespace {
 
 constexpr int WAVES = 4;
 
-// fp32 row sum with the association order of torch.sum's vectorised CPU kernel (8-lane
-// vectors, 4 interleaved accumulators, leftover vectors into accumulator 0,
-// ((a0+a1)+a2)+a3, then the scalar tail first and the 8 vector lanes after it).
-// Verified against torch 2.10 CPU for every n in 1..510 (tests/test_gpu_parity.py::test_sample_pdf_every_bin_count).
-// 4 <= n <= 7 is its own case there (round 5: found by tools/fuzz_samplers.py on weights that put u ON a cdf entry -- 24
-// search indices of 32,634 differed at 5 weights): one 4-lane vector, the tail added to lane 0 in order, then the lanes in
-// order -- (((((x0 + x4) + x5) + x6) + x1) + x2) + x3.
-// Lanes 0..7 of the wave play the 8 SIMD lanes; result is broadcast to the wave.
-__device__ __forceinline__ float torch_row_sum(const float* x, int n, int lane) {
-    if (n >= 4 && n < 8) {      // (uniform)
-        float t = x[0];
-        for (int e = 4; e < n; ++e) t = t + x[e];
-        t = t + x[1];
-        t = t + x[2];
-        return t + x[3];
-    }
-    const int nvec = n >> 3;
-    const int g4 = nvec & ~3;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (lane < 8) {
-        for (int v = 0; v < g4; v += 4) {
-            a0 = a0 + x[(v + 0) * 8 + lane];
-            a1 = a1 + x[(v + 1) * 8 + lane];
-            a2 = a2 + x[(v + 2) * 8 + lane];
-            a3 = a3 + x[(v + 3) * 8 + lane];
-        }
-        for (int v = g4; v < nvec; ++v) a0 = a0 + x[v * 8 + lane];
-        a0 = a0 + a1;
-        a0 = a0 + a2;
-        a0 = a0 + a3;
-    }
-    float total = 0.f;
-    for (int e = nvec * 8; e < n; ++e) total = total + x[e];   // uniform across lanes
-#pragma unroll
-    for (int l = 0; l < 8; ++l) total = total + __shfl(a0, l);
-    return total;
-}
-
 struct SampleConstArgs {
     const float* bins;
     const float* weights;

@@ -259,7 +259,9 @@ def render_rays(ray_batch, use_viewdirs, network_fn, network_query_fn, N_samples
     # mode): plnerf_coarse_epilogue (raw2outputs + importance sampling + clamp + sort + positions) and
     # plnerf_fine_epilogue (raw2outputs + the hypotheses' sampler + z_std); bit-identical to the separate calls below.
     tap = STAGE_TAP
-    fused = FUSE_STAGES and fused_glue and mode == "linear" and color_mode in ("midpoint", "left") and tap is None
+    # Piecewise-constant mode likewise (plnerf_coarse_epilogue_const / plnerf_fine_epilogue_const; the sampler needs three depths).
+    fused = FUSE_STAGES and fused_glue and tap is None and (
+        (mode == "linear" and color_mode in ("midpoint", "left")) or (mode == "constant" and N_samples >= 3))
     if fused_glue:
         # depths, jitter and positions in one launch (plnerf_coarse_samples: bit-identical to the expressions below,
         # which are :775-790 and run_plnerf.py:683-708 alike); the jitter from the reference's draw, or in the kernel
@@ -286,7 +288,7 @@ def render_rays(ray_batch, use_viewdirs, network_fn, network_query_fn, N_samples
             u = _joint_row(draws, n, dev) if is_joint else None
         rgb, disp, acc, depth, w, tau, T, hyp, u_used, _, z_std = Fn.FineEpilogueFn.apply(
             _rgb_sigma(raw), z_vals, near, far, rays_d, _draw_noise(raw, raw_noise_std, pytest), u, n, color_mode,
-            white_bkgd, False, zero_tol, epsilon, draws)
+            white_bkgd, False, zero_tol, epsilon, draws, mode)
         return rgb, disp, acc, w, depth, hyp, u_used, z_std
 
     if fused and N_importance == 0:
@@ -297,7 +299,7 @@ def render_rays(ray_batch, use_viewdirs, network_fn, network_query_fn, N_samples
         u0 = _nvs_draw_u([N_rays], N_importance, det, pytest, dev) if (pytest or det or draws is None) else None
         rgb_map_0, disp_map_0, acc_map_0, depth_map_0, z_vals, pts, _, weights_0 = Fn.CoarseEpilogueFn.apply(
             _rgb_sigma(raw), z_vals, near, far, rays_o, rays_d, _draw_noise(raw, raw_noise_std, pytest), u0,
-            N_importance, color_mode, white_bkgd, False, zero_tol, epsilon, draws, True)
+            N_importance, color_mode, white_bkgd, False, zero_tol, epsilon, draws, True, mode)
         run_fn = network_fn if network_fine is None else network_fine
         raw = network_query_fn(pts, viewdirs, embedded_cam, run_fn)
         rgb_map, disp_map, acc_map, weights, depth_map, pred_depth_hyp, u, z_std = last_stage(raw, z_vals, N_importance,

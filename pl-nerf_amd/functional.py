@@ -227,11 +227,14 @@ class CoarseEpilogueFn(torch.autograd.Function):
     """run_plnerf.py:714-735 in piecewise-linear mode as one launch (plnerf_coarse_epilogue): raw2outputs of the
     coarse pass, sample_pdf_reformulation, clamp, sort(cat), the fine pass's sample positions and z_std.
     Differentiable with respect to `raw` through the coarse maps (backward = plnerf_quad_bwd); the samples are
-    detached on the reference path (:728).  `u` None = drawn inside the kernel from `draws`."""
+    detached on the reference path (:728).  `u` None = drawn inside the kernel from `draws`.
+    mode="constant": the same stages in piecewise-constant mode (plnerf_coarse_epilogue_const: compute_weights, z_vals_mid,
+    sample_pdf on weights[..., 1:-1]); color_mode, farcolorfix, zero_tol and eps are ignored there, weights are [R,S]."""
 
     @staticmethod
     def forward(ctx, raw, z, near, far, rays_o, rays_d, noise, u, N, color_mode, white_bkgd, farcolorfix, zero_tol,
-                eps, draws, want_weights=False):
+                eps, draws, want_weights=False, mode="linear"):
+        _expect(mode in ("linear", "constant"), f"mode must be 'linear' or 'constant', got {mode!r}")
         R, S = z.shape
         dev = raw.device
         _expect(tuple(raw.shape) == (R, S, 4), f"raw must be [{R}, {S}, 4], got {tuple(raw.shape)}")
@@ -248,17 +251,26 @@ class CoarseEpilogueFn(torch.autograd.Function):
         z_fine = torch.empty(R, S + N, device=dev)
         pts = torch.empty(R, S + N, 3, device=dev)
         # (the coarse weights reach HBM only for a caller that returns them: the depth-supervised variant's `weights0`)
-        weights = torch.empty(R, S + 1, device=dev) if want_weights else None
+        linear = mode == "linear"
+        weights = torch.empty(R, S + 1 if linear else S, device=dev) if want_weights else None
         seed, step, ray0 = (draws.seed, draws.step, draws.first_ray()) if draws is not None else (0, 0, 0)
-        L.check(L.lib().plnerf_coarse_epilogue(
-            L.dptr(raw_c, "raw"), L.dptr(z_c, "z_vals"), L.dptr(near_c, "near"), L.dptr(far_c, "far"),
-            L.dptr(o_c, "rays_o"), L.dptr(d_c, "rays_d"), L.dptr(noise_c, "noise"), L.dptr(u_c, "u"), stride, seed, step,
-            ray0, R, S, int(N), L.COLOR[color_mode], int(bool(white_bkgd)), int(bool(farcolorfix)), float(zero_tol),
-            float(eps), L.dptr(rgb), L.dptr(disp), L.dptr(acc), L.dptr(depth), L.dptr(weights), None, None, L.dptr(z_fine),
-            L.dptr(pts), L.dptr(z_std), L.stream()), "plnerf_coarse_epilogue")
+        if linear:
+            L.check(L.lib().plnerf_coarse_epilogue(
+                L.dptr(raw_c, "raw"), L.dptr(z_c, "z_vals"), L.dptr(near_c, "near"), L.dptr(far_c, "far"),
+                L.dptr(o_c, "rays_o"), L.dptr(d_c, "rays_d"), L.dptr(noise_c, "noise"), L.dptr(u_c, "u"), stride, seed, step,
+                ray0, R, S, int(N), L.COLOR[color_mode], int(bool(white_bkgd)), int(bool(farcolorfix)), float(zero_tol),
+                float(eps), L.dptr(rgb), L.dptr(disp), L.dptr(acc), L.dptr(depth), L.dptr(weights), None, None, L.dptr(z_fine),
+                L.dptr(pts), L.dptr(z_std), L.stream()), "plnerf_coarse_epilogue")
+        else:
+            color_mode = "midpoint"      # (what raw2outputs hands plnerf_quad_bwd in constant mode, which ignores it)
+            L.check(L.lib().plnerf_coarse_epilogue_const(
+                L.dptr(raw_c, "raw"), L.dptr(z_c, "z_vals"), L.dptr(near_c, "near"), L.dptr(far_c, "far"),
+                L.dptr(o_c, "rays_o"), L.dptr(d_c, "rays_d"), L.dptr(noise_c, "noise"), L.dptr(u_c, "u"), stride, seed, step,
+                ray0, R, S, int(N), int(bool(white_bkgd)), L.dptr(rgb), L.dptr(disp), L.dptr(acc), L.dptr(depth),
+                L.dptr(weights), L.dptr(z_fine), L.dptr(pts), L.dptr(z_std), L.stream()), "plnerf_coarse_epilogue_const")
         ctx.save_for_backward(raw_c, z_c, near_c, far_c, d_c, noise_c if noise_c is not None else torch.empty(0),
                               depth, acc)
-        ctx.cfg = ("linear", color_mode, bool(white_bkgd), bool(farcolorfix), noise_c is not None)
+        ctx.cfg = (mode, color_mode, bool(white_bkgd), bool(farcolorfix), noise_c is not None)
         if weights is None:
             weights = torch.empty(0, device=dev)
         ctx.mark_non_differentiable(z_fine, pts, z_std, weights)
@@ -270,7 +282,7 @@ class CoarseEpilogueFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rgb, g_disp, g_acc, g_depth, g_z, g_pts, g_std, g_w=None):
         g_raw = _quad_backward(ctx.saved_tensors, ctx.cfg, g_rgb, g_disp, g_acc, None, g_depth, None, None)
-        return (g_raw,) + (None,) * 15
+        return (g_raw,) + (None,) * 16
 
 
 class FineEpilogueFn(torch.autograd.Function):
@@ -279,11 +291,16 @@ class FineEpilogueFn(torch.autograd.Function):
     hypotheses (depth_supervised_exps/run_nerf_sample_based_depth.py:909-934), plus z_std = std(hypotheses).
     Differentiable with respect to `raw` through the maps, the weights AND the hypotheses (which keep their tape in the
     reference: :923-934): backward = plnerf_sample_pl_bwd (g_hyp -> g_tau, g_T), then plnerf_quad_bwd.
-    u: [R, N], one shared row [N] (is_joint), or None = drawn in the kernel from `draws`."""
+    u: [R, N], one shared row [N] (is_joint), or None = drawn in the kernel from `draws`.
+    mode="constant": the stage in piecewise-constant mode (plnerf_fine_epilogue_const: compute_weights, then
+    sample_pdf_return_u on z_vals_mid and weights[..., 1:-1], model/run_nerf_helpers.py:343-394); weights are [R,S], tau and T
+    come back empty, and the backward is plnerf_sample_const_bwd (g_hyp -> the interior weights), then plnerf_quad_bwd."""
     HYP_STREAM = 4
 
     @staticmethod
-    def forward(ctx, raw, z, near, far, rays_d, noise, u, N, color_mode, white_bkgd, farcolorfix, zero_tol, eps, draws):
+    def forward(ctx, raw, z, near, far, rays_d, noise, u, N, color_mode, white_bkgd, farcolorfix, zero_tol, eps, draws,
+                mode="linear"):
+        _expect(mode in ("linear", "constant"), f"mode must be 'linear' or 'constant', got {mode!r}")
         R, S = z.shape
         dev = raw.device
         _expect(tuple(raw.shape) == (R, S, 4), f"raw must be [{R}, {S}, 4], got {tuple(raw.shape)}")
@@ -297,12 +314,28 @@ class FineEpilogueFn(torch.autograd.Function):
         stride = 0 if (u_c is None or u_c.dim() == 1) else N
         rgb = torch.empty(R, 3, device=dev)
         disp, acc, depth, z_std = (torch.empty(R, device=dev) for _ in range(4))
-        w = torch.empty(R, S + 1, device=dev)
-        tau, T = torch.empty(R, S + 2, device=dev), torch.empty(R, S + 2, device=dev)
         hyp = torch.empty(R, N, device=dev)
         inds = torch.empty(R, N, device=dev, dtype=torch.int64)
         u_used = u_c if (u_c is not None and u_c.dim() == 2) else torch.empty(R, N, device=dev)
         seed, step, ray0 = (draws.seed, draws.step, draws.first_ray()) if draws is not None else (0, 0, 0)
+        if mode == "constant":
+            w = torch.empty(R, S, device=dev)
+            bins = torch.empty(R, S - 1, device=dev)
+            tau = T = torch.empty(0, device=dev)
+            L.check(L.lib().plnerf_fine_epilogue_const(
+                L.dptr(raw_c, "raw"), L.dptr(z_c, "z_vals"), L.dptr(near_c, "near"), L.dptr(far_c, "far"), L.dptr(d_c, "rays_d"),
+                L.dptr(noise_c, "noise"), L.dptr(u_c, "u"), stride, seed, step, ray0, R, S, int(N), int(bool(white_bkgd)),
+                L.dptr(rgb), L.dptr(disp), L.dptr(acc), L.dptr(depth), L.dptr(w), L.dptr(bins), L.dptr(hyp),
+                L.dptr(inds, "inds", torch.int64), None if u_used is u_c else L.dptr(u_used), L.dptr(z_std), L.stream()),
+                "plnerf_fine_epilogue_const")
+            ctx.save_for_backward(raw_c, z_c, near_c, far_c, d_c, noise_c if noise_c is not None else torch.empty(0),
+                                  depth, acc, bins, w, u_used, inds)
+            ctx.cfg = ("constant", "midpoint", bool(white_bkgd), bool(farcolorfix), noise_c is not None)
+            ctx.mark_non_differentiable(tau, T, u_used, inds, z_std)
+            ctx.set_materialize_grads(False)
+            return rgb, disp, acc, depth, w, tau, T, hyp, u_used, inds, z_std
+        w = torch.empty(R, S + 1, device=dev)
+        tau, T = torch.empty(R, S + 2, device=dev), torch.empty(R, S + 2, device=dev)
         L.check(L.lib().plnerf_fine_epilogue(
             L.dptr(raw_c, "raw"), L.dptr(z_c, "z_vals"), L.dptr(near_c, "near"), L.dptr(far_c, "far"), L.dptr(d_c, "rays_d"),
             L.dptr(noise_c, "noise"), L.dptr(u_c, "u"), stride, seed, step, ray0, R, S, int(N), L.COLOR[color_mode],
@@ -320,6 +353,22 @@ class FineEpilogueFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rgb, g_disp, g_acc, g_depth, g_w, g_tau, g_T, g_hyp, g_u, g_inds, g_std):
         raw_c, z_c, near_c, far_c, d_c, noise_c, depth, acc, tau, T, u_used, inds = ctx.saved_tensors
+        if ctx.cfg[0] == "constant":
+            bins, w = tau, T          # (what the constant forward saved in their places)
+            if g_hyp is not None:
+                R, S = z_c.shape
+                N = inds.shape[-1]
+                g_in = torch.empty(R, S - 2, device=z_c.device)
+                L.check(L.lib().plnerf_sample_const_bwd(
+                    L.dptr(bins), L.dptr(w[:, 1:-1].contiguous()), L.dptr(u_used), N, L.dptr(inds, "inds", torch.int64),
+                    L.dptr(_f32c(g_hyp)), R, S - 1, N, L.dptr(g_in), L.stream()), "plnerf_sample_const_bwd")
+                # the slice's backward: the interior of a zero [R,S] cotangent, joined with the returned weights' own
+                g_s = torch.zeros(R, S, device=z_c.device)
+                g_s[:, 1:-1] = g_in
+                g_w = g_s if g_w is None else g_w + g_s
+            g_raw = _quad_backward((raw_c, z_c, near_c, far_c, d_c, noise_c, depth, acc), ctx.cfg, g_rgb, g_disp, g_acc,
+                                   g_w, g_depth, None, None)
+            return (g_raw,) + (None,) * 14
         if g_hyp is not None:
             R, S = z_c.shape
             N = inds.shape[-1]
@@ -333,7 +382,7 @@ class FineEpilogueFn(torch.autograd.Function):
             g_T = gT if g_T is None else g_T + gT
         g_raw = _quad_backward((raw_c, z_c, near_c, far_c, d_c, noise_c, depth, acc), ctx.cfg, g_rgb, g_disp, g_acc, g_w,
                                g_depth, g_tau, g_T)
-        return (g_raw,) + (None,) * 13
+        return (g_raw,) + (None,) * 14
 
 
 _LOSS_WS = {}

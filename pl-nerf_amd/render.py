@@ -21,6 +21,9 @@ DEBUG = False
 # the coarse pass's epilogue runs as its separate launches (bit-identical to the fused one:
 # test_fused_coarse_epilogue_equals_separate_launches), which is where those tensors exist in HBM.
 STAGE_TAP = None
+# Piecewise-constant mode's coarse epilogue as one launch (plnerf_coarse_epilogue_const).  (Tests switch it off to compare with
+# the separate launches, bit for bit -- as depth.FUSE_STAGES.)
+FUSE_CONST_EPILOGUE = True
 MAX_ROWS_PER_LAUNCH = 1 << 21   # MLP rows per kernel launch when activations are saved (~21 GB fp32)
 
 
@@ -252,18 +255,25 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, mode, color_
 
     raw = network_query_fn(pts, viewdirs, network_fn)
     tap = STAGE_TAP
-    fused_epilogue = fused_glue and N_importance > 0 and mode == "linear" and color_mode in ("midpoint", "left") \
-        and tap is None
+    fused_epilogue = fused_glue and N_importance > 0 and tap is None and (
+        (mode == "linear" and color_mode in ("midpoint", "left")) or
+        (mode == "constant" and FUSE_CONST_EPILOGUE and N_samples >= 3))
     if tap is not None:
         tap.update(z_vals0=z_vals, raw0=raw)
     if fused_epilogue:
         # coarse raw2outputs + sampler + clamp + sort + fine positions + z_std: one launch (weights, tau, T and the
         # cdf never reach HBM); identical values to the separate calls below
+        # (piecewise-constant mode -- the vanilla-NeRF baseline, the constant_init warm-up -- likewise:
+        # plnerf_coarse_epilogue_const in place of quadrature, z_vals_mid, sample_pdf, merge sort, torch.std and positions)
         det = perturb == 0.
+        if mode == "constant":      # (torch.rand draws in the separate calls' order: the density noise, then u)
+            noise = _draw_noise(raw, raw_noise_std, pytest)
         u = _draw_u([N_rays], N_importance, det, pytest, dev) if (pytest or det or draws is None) else None
+        if mode == "linear":
+            noise = _draw_noise(raw, raw_noise_std, pytest)
         rgb_map_0, disp_map_0, acc_map_0, depth_map_0, z_vals, pts, z_std = Fn.CoarseEpilogueFn.apply(
-            _rgb_sigma(raw), z_vals, near, far, rays_o, rays_d, _draw_noise(raw, raw_noise_std, pytest), u,
-            N_importance, color_mode, white_bkgd, farcolorfix, zero_tol, epsilon, draws, False)
+            _rgb_sigma(raw), z_vals, near, far, rays_o, rays_d, noise, u,
+            N_importance, color_mode, white_bkgd, farcolorfix, zero_tol, epsilon, draws, False, mode)
     else:
         rgb_map, disp_map, acc_map, weights, depth_map, tau, T = raw2outputs(
             raw, z_vals, near, far, rays_d, mode, color_mode, raw_noise_std, pytest=pytest, white_bkgd=white_bkgd,
