@@ -232,6 +232,19 @@ DEPTHSTEP_SIGNATURES = {
     "plnerf_depth_ss_adam": (c_i, [c_f] * 5 + [c_i] + [c_fl] * 4 + [c_i, c_fl, c_s]),
 }
 
+# ... and include/plnerf_hip_conststep.h (ABI 601): piecewise-constant mode's one-call steps, on the structs above, and the
+# one-launch backward of plnerf_fine_epilogue_const they need
+CONSTSTEP_SIGNATURES = {
+    "plnerf_fine_epilogue_const_bwd": (c_i, [c_f] * 9 + [c_i, c_f] + [c_i] * 4 + [c_f] * 7 + [c_s]),
+    "plnerf_train_step_const_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(StepConfig)]),
+    "plnerf_train_step_const": (c_i, [ctypes.POINTER(StepConfig), ctypes.POINTER(StepIo), ctypes.POINTER(StepArgs), c_f,
+                                      ctypes.c_size_t, c_s]),
+    "plnerf_depth_train_step_const_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DepthStepConfig)]),
+    "plnerf_depth_train_step_const_layout": (c_i, [ctypes.POINTER(DepthStepConfig), ctypes.POINTER(DepthStepViews)]),
+    "plnerf_depth_train_step_const": (c_i, [ctypes.POINTER(DepthStepConfig), ctypes.POINTER(DepthStepIo),
+                                            ctypes.POINTER(DepthStepArgs), c_f, ctypes.c_size_t, c_s]),
+}
+
 
 _lib = None
 
@@ -249,7 +262,7 @@ def lib():
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
                 list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()) + list(CONSTEPI_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + \
-                list(DEPTHSTEP_SIGNATURES.items()):
+                list(DEPTHSTEP_SIGNATURES.items()) + list(CONSTSTEP_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

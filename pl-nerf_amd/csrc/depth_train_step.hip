@@ -7,7 +7,9 @@
 #include <math.h>
 
 #include "step_common.h"
+#include "ray_bwd_dev.h"
 #include "../../include/plnerf_hip_depthstep.h"
+#include "../../include/plnerf_hip_conststep.h"
 
 namespace {
 
@@ -82,9 +84,11 @@ Plan carve(const plnerf_depth_step_config* c, void* workspace) {
     return p;
 }
 
-int check_config(const plnerf_depth_step_config* c) {
+// constant: plnerf_depth_train_step_const's limits on top (its sampler needs one interior weight; the last stage's backward
+// keeps a longer LDS row than any kernel of the linear step)
+int check_config(const plnerf_depth_step_config* c, const bool constant) {
     if (!c) return PLNERF_EINVAL;
-    if (c->max_rays < 1 || c->n_samples < 2 || c->n_importance < 1) return PLNERF_EINVAL;
+    if (c->max_rays < 1 || c->n_samples < (constant ? 3 : 2) || c->n_importance < 1) return PLNERF_EINVAL;
     if (c->color_mode != PLNERF_COLOR_MIDPOINT && c->color_mode != PLNERF_COLOR_LEFT) return PLNERF_EINVAL;
     if (c->n_views < 1 || c->H < 1 || c->W < 1 || c->n_hyp < 1 || (c->pose_rows != 3 && c->pose_rows != 4)) return PLNERF_EINVAL;
     if (c->fwd_kernel != PLNERF_FWD_KERNEL_AUTO && c->fwd_kernel != PLNERF_FWD_KERNEL_RR && c->fwd_kernel != PLNERF_FWD_KERNEL_PP)
@@ -101,6 +105,27 @@ int check_config(const plnerf_depth_step_config* c) {
     // (row counts are ints throughout the ABI)
     if ((uint64_t)c->max_rays * (uint64_t)(c->n_samples + c->n_importance + 2) > (uint64_t)INT32_MAX / 4) return PLNERF_ERANGE;
     if ((uint64_t)c->max_rays * (uint64_t)c->n_hyp > (uint64_t)INT32_MAX / 4) return PLNERF_ERANGE;
+    if (constant && (size_t)plnerf::RAY_WAVES * plnerf::fine_const_bwd_row_floats(c->n_samples + c->n_importance, c->n_importance) *
+                            sizeof(float) > 160 * 1024)
+        return PLNERF_ERANGE;
+    return PLNERF_OK;
+}
+
+size_t workspace_bytes_of(const plnerf_depth_step_config* config, const bool constant) {
+    if (check_config(config, constant) != PLNERF_OK) return 0;
+    return carve(config, nullptr).bytes;
+}
+
+int layout_of(const plnerf_depth_step_config* config, plnerf_depth_step_views* out, const bool constant) {
+    const int rc = check_config(config, constant);
+    if (rc) return rc;
+    if (!out) return PLNERF_EINVAL;
+    const Plan p = carve(config, nullptr);      // (from a null base the addresses ARE the offsets)
+    const auto off = [](const void* q) { return (size_t)(uintptr_t)q; };
+    out->rgb = off(p.rgb); out->rgb0 = off(p.rgb0); out->depth = off(p.depth); out->depth0 = off(p.depth0);
+    out->acc = off(p.acc); out->acc0 = off(p.acc0); out->disp = off(p.disp); out->disp0 = off(p.disp0);
+    out->z_std = off(p.z_std); out->pred_hyp = off(p.hyp); out->z_vals = off(p.z_f); out->z_vals0 = off(p.z_c);
+    out->pixels = off(p.pixels); out->target_h = off(p.target_h); out->mask = off(p.mask);
     return PLNERF_OK;
 }
 
@@ -119,29 +144,14 @@ extern "C" int plnerf_depth_ss_adam(float* scale, float* shift, const float* gra
     return PLNERF_OK;
 }
 
-extern "C" size_t plnerf_depth_train_step_workspace_bytes(const plnerf_depth_step_config* config) {
-    if (check_config(config) != PLNERF_OK) return 0;
-    return carve(config, nullptr).bytes;
-}
+namespace {
 
-extern "C" int plnerf_depth_train_step_layout(const plnerf_depth_step_config* config, plnerf_depth_step_views* out) {
-    const int rc = check_config(config);
-    if (rc) return rc;
-    if (!out) return PLNERF_EINVAL;
-    const Plan p = carve(config, nullptr);      // (from a null base the addresses ARE the offsets)
-    const auto off = [](const void* q) { return (size_t)(uintptr_t)q; };
-    out->rgb = off(p.rgb); out->rgb0 = off(p.rgb0); out->depth = off(p.depth); out->depth0 = off(p.depth0);
-    out->acc = off(p.acc); out->acc0 = off(p.acc0); out->disp = off(p.disp); out->disp0 = off(p.disp0);
-    out->z_std = off(p.z_std); out->pred_hyp = off(p.hyp); out->z_vals = off(p.z_f); out->z_vals0 = off(p.z_c);
-    out->pixels = off(p.pixels); out->target_h = off(p.target_h); out->mask = off(p.mask);
-    return PLNERF_OK;
-}
-
-extern "C" int plnerf_depth_train_step(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io,
-                                       const plnerf_depth_step_args* a, void* workspace, size_t workspace_bytes,
-                                       plnerf_stream_t stream) {
+// constant: plnerf_depth_train_step_const.  The Plan is the linear step's: the last stage's weights [R,F] lie in the tau plane,
+// its bins [R,F-1] in the T plane.
+int depth_train_step(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io, const plnerf_depth_step_args* a,
+                     void* workspace, size_t workspace_bytes, plnerf_stream_t stream, const bool constant) {
     // ---- every check first: a refused call enqueues nothing ----
-    int rc = check_config(c);
+    int rc = check_config(c, constant);
     if (rc) return rc;
     if (!io || !a || !workspace || ((uintptr_t)workspace % ALIGN) != 0) return PLNERF_EINVAL;
     if (a->rays < 1 || a->rays > c->max_rays || a->ray_id0 < 0 || a->view < 0 || a->view >= c->n_views) return PLNERF_EINVAL;
@@ -185,10 +195,15 @@ extern "C" int plnerf_depth_train_step(const plnerf_depth_step_config* c, const 
         if (c->raw_noise_std != 1.0f) STEP_OK(scale2(p.noise_c, (size_t)R * S, nullptr, 0, c->raw_noise_std, st));
     }
     // (the depth script's raw2outputs ignores farcolorfix: 0 throughout)
-    STEP_OK(plnerf_coarse_epilogue(p.raw_c, p.z_c, p.near, p.far, o, d, noise ? p.noise_c : nullptr,
-                                   c->perturb ? nullptr : io->u_vals, 0, c->seed, a->step, a->ray_id0, R, S, N, c->color_mode,
-                                   white, 0, c->zero_tol, c->epsilon, p.rgb0, p.disp0, p.acc0, p.depth0, nullptr, nullptr, nullptr,
-                                   p.z_f, p.pts_f, p.z_std0, stream));
+    if (!constant)
+        STEP_OK(plnerf_coarse_epilogue(p.raw_c, p.z_c, p.near, p.far, o, d, noise ? p.noise_c : nullptr,
+                                       c->perturb ? nullptr : io->u_vals, 0, c->seed, a->step, a->ray_id0, R, S, N, c->color_mode,
+                                       white, 0, c->zero_tol, c->epsilon, p.rgb0, p.disp0, p.acc0, p.depth0, nullptr, nullptr,
+                                       nullptr, p.z_f, p.pts_f, p.z_std0, stream));
+    else
+        STEP_OK(plnerf_coarse_epilogue_const(p.raw_c, p.z_c, p.near, p.far, o, d, noise ? p.noise_c : nullptr,
+                                             c->perturb ? nullptr : io->u_vals, 0, c->seed, a->step, a->ray_id0, R, S, N, white,
+                                             p.rgb0, p.disp0, p.acc0, p.depth0, nullptr, p.z_f, p.pts_f, p.z_std0, stream));
 
     // ---- fine pass; its last stage also draws the depth hypotheses from the final weights ----
     STEP_OK(plnerf_mlp_pack_weights(io->fine.params, prec, xyz, dir, io->fine.packed, stream));
@@ -210,9 +225,15 @@ extern "C" int plnerf_depth_train_step(const plnerf_depth_step_config* c, const 
         STEP_OK(plnerf_normal(c->seed, NOISE_STREAM + 1, a->step, a->ray_id0, R, F, p.noise_f, stream));
         if (c->raw_noise_std != 1.0f) STEP_OK(scale2(p.noise_f, (size_t)R * F, nullptr, 0, c->raw_noise_std, st));
     }
-    STEP_OK(plnerf_fine_epilogue(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, u_in, 0, c->seed, a->step,
-                                 a->ray_id0, R, F, N, c->color_mode, white, 0, c->zero_tol, c->epsilon, p.rgb, p.disp, p.acc,
-                                 p.depth, p.w, p.tau, p.T, p.hyp, p.inds, c->perturb ? p.u_used : nullptr, p.z_std, stream));
+    float *const w_const = p.tau, *const bins_const = p.T;
+    if (!constant)
+        STEP_OK(plnerf_fine_epilogue(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, u_in, 0, c->seed, a->step,
+                                     a->ray_id0, R, F, N, c->color_mode, white, 0, c->zero_tol, c->epsilon, p.rgb, p.disp, p.acc,
+                                     p.depth, p.w, p.tau, p.T, p.hyp, p.inds, c->perturb ? p.u_used : nullptr, p.z_std, stream));
+    else
+        STEP_OK(plnerf_fine_epilogue_const(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, u_in, 0, c->seed, a->step,
+                                           a->ray_id0, R, F, N, white, p.rgb, p.disp, p.acc, p.depth, w_const, bins_const, p.hyp,
+                                           p.inds, c->perturb ? p.u_used : nullptr, p.z_std, stream));
 
     // ---- loss and its gradients; the scales' and shifts' gradient from the hypotheses the loss chose ----
     STEP_OK(plnerf_depth_loss(p.rgb, p.rgb0, p.target, carve_on ? p.hyp : nullptr, carve_on ? p.target_h : nullptr,
@@ -226,14 +247,21 @@ extern "C" int plnerf_depth_train_step(const plnerf_depth_step_config* c, const 
 
     // ---- backward: the hypotheses' gradient through the sampler, d loss / d raw of either pass (the fine one first, as
     //      autograd orders them), then both networks at once ----
-    if (carve_on)
-        STEP_OK(plnerf_sample_pl_bwd(p.z_f, p.tau, p.T, p.near, p.far, u_seen, u_seen_stride, p.inds, p.g_hyp, R, F, N,
-                                     c->zero_tol, c->epsilon, p.g_tau, p.g_T, stream));
-    STEP_OK(plnerf_quad_bwd(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, R, F, PLNERF_MODE_LINEAR, c->color_mode,
-                            white, 0, p.g_rgb, nullptr, nullptr, nullptr, carve_on ? p.g_tau : nullptr,
-                            carve_on ? p.g_T : nullptr, p.g_raw_f, p.absmax_f, stream));
-    STEP_OK(plnerf_quad_bwd(p.raw_c, p.z_c, p.near, p.far, d, noise ? p.noise_c : nullptr, R, S, PLNERF_MODE_LINEAR, c->color_mode,
-                            white, 0, p.g_rgb0, nullptr, nullptr, nullptr, nullptr, nullptr, p.g_raw_c, p.absmax_c, stream));
+    if (constant) {      // (the sampler's backward, the padded sum and the quadrature's in one launch; without g_hyp the last alone)
+        STEP_OK(plnerf_fine_epilogue_const_bwd(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, w_const, bins_const,
+                                               u_seen, u_seen_stride, p.inds, R, F, N, white, p.g_rgb, nullptr, nullptr, nullptr,
+                                               carve_on ? p.g_hyp : nullptr, p.g_raw_f, p.absmax_f, stream));
+    } else {
+        if (carve_on)
+            STEP_OK(plnerf_sample_pl_bwd(p.z_f, p.tau, p.T, p.near, p.far, u_seen, u_seen_stride, p.inds, p.g_hyp, R, F, N,
+                                         c->zero_tol, c->epsilon, p.g_tau, p.g_T, stream));
+        STEP_OK(plnerf_quad_bwd(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, R, F, PLNERF_MODE_LINEAR,
+                                c->color_mode, white, 0, p.g_rgb, nullptr, nullptr, nullptr, carve_on ? p.g_tau : nullptr,
+                                carve_on ? p.g_T : nullptr, p.g_raw_f, p.absmax_f, stream));
+    }
+    STEP_OK(plnerf_quad_bwd(p.raw_c, p.z_c, p.near, p.far, d, noise ? p.noise_c : nullptr, R, S,
+                            constant ? PLNERF_MODE_CONSTANT : PLNERF_MODE_LINEAR, c->color_mode, white, 0, p.g_rgb0, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, p.g_raw_c, p.absmax_c, stream));
     const plnerf_step_net* nets[2] = {&io->coarse, &io->fine};
     float* grads[2 * PLNERF_N_PARAM_TENSORS];
     for (int j = 0; j < 2; ++j)
@@ -268,4 +296,35 @@ extern "C" int plnerf_depth_train_step(const plnerf_depth_step_config* c, const 
                                      c->ss_beta1, c->ss_beta2, c->ss_adam_eps, a->ss_adam_step, 1.0f, stream));
 #undef STEP_OK
     return PLNERF_OK;
+}
+
+}  // namespace
+
+extern "C" size_t plnerf_depth_train_step_workspace_bytes(const plnerf_depth_step_config* config) {
+    return workspace_bytes_of(config, false);
+}
+
+extern "C" int plnerf_depth_train_step_layout(const plnerf_depth_step_config* config, plnerf_depth_step_views* out) {
+    return layout_of(config, out, false);
+}
+
+extern "C" int plnerf_depth_train_step(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io,
+                                       const plnerf_depth_step_args* a, void* workspace, size_t workspace_bytes,
+                                       plnerf_stream_t stream) {
+    return depth_train_step(c, io, a, workspace, workspace_bytes, stream, false);
+}
+
+// ---- piecewise-constant mode (include/plnerf_hip_conststep.h): the same carve, so the same bytes and offsets ----
+extern "C" size_t plnerf_depth_train_step_const_workspace_bytes(const plnerf_depth_step_config* config) {
+    return workspace_bytes_of(config, true);
+}
+
+extern "C" int plnerf_depth_train_step_const_layout(const plnerf_depth_step_config* config, plnerf_depth_step_views* out) {
+    return layout_of(config, out, true);
+}
+
+extern "C" int plnerf_depth_train_step_const(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io,
+                                             const plnerf_depth_step_args* a, void* workspace, size_t workspace_bytes,
+                                             plnerf_stream_t stream) {
+    return depth_train_step(c, io, a, workspace, workspace_bytes, stream, true);
 }

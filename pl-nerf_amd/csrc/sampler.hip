@@ -14,13 +14,13 @@
 // separately rounded fp32 op (eager PyTorch), and the bit-exact index contract of
 // plnerf_sample_const depends on that.
 #include "common.h"
-#include "ray_dev.h"
+#include "ray_bwd_dev.h"
 
 using namespace plnerf;
 
 namespace {
 
-constexpr int WAVES = 4;
+constexpr int WAVES = RAY_WAVES;
 
 struct SampleConstArgs {
     const float* bins;
@@ -77,107 +77,25 @@ __global__ __launch_bounds__(256) void sample_const_kernel(SampleConstArgs a) {
 
 
 struct SampleConstBwdArgs {
-    const float* bins;
-    const float* weights;
-    const float* u;
-    int u_row_stride;
-    const int64_t* inds;
-    const float* g_samples;
-    int R, B, N;
+    SampleConstBwdIn in;
+    int R;
     int lds_stride;
     float* g_weights;
 };
 
-// Backward of sample_const_kernel with respect to `weights` (what autograd derives for sample_pdf_return_u,
-// depth_supervised_exps/model/run_nerf_helpers.py:343-394, when pred_hyp carries a loss in constant mode):
-//   sample = b0 + t (b1 - b0),  t = (u - c0) / denom,  denom = c1 - c0 (or 1 where that is < 1e-5)
-//   cdf[j] = sum_{i<j} pdf[i],  pdf = w' / sum(w'),  w' = w + 1e-5
-// Per-knot sums run in sample order and the suffix sums are wave scans: deterministic, no atomics.
+// Backward of sample_const_kernel with respect to `weights`: sample_const_bwd_rows (ray_bwd_dev.h).
 __global__ __launch_bounds__(256) void sample_const_bwd_kernel(SampleConstBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int ray = blockIdx.x * WAVES + wave;
     const bool live = ray < a.R;
     if (!live) ray = a.R - 1;
-    const int B = a.B, n = a.B - 1, N = a.N;
-    float* cdf = smem + wave * a.lds_stride;   // B
-    float* bins = cdf + B;                      // B
-    float* wv = bins + B;                       // n  (weights + 1e-5), later g_pdf
-    float* g0 = wv + B;                         // N: gradient landing on cdf[below]
-    float* g1 = g0 + N;                         // N: on cdf[above]
-    int* lo = reinterpret_cast<int*>(g1 + N);   // N
-    int* hi = lo + N;                           // N
-    float* gc = reinterpret_cast<float*>(hi + N);   // B: g_cdf
-    // the cdf before its rounding to fp32 (round 6): c1 - c0 of two fp32 roundings carries 6e-8 / (c1 - c0) -- 1e-3 of the gradient
-    // on a narrow bin, in the reference's fp32 autograd and in this kernel until then; the derivative's VALUE now comes from these,
-    // which bins count as empty (c1 - c0 < 1e-5) stays the forward's fp32 decision (as plnerf_sample_pl_bwd: LABNOTES R6-13)
-    double* cdf64 = reinterpret_cast<double*>(gc + B);      // B  (4 B + 4 N floats precede it: 8-byte aligned)
-    for (int j = lane; j < B; j += 64) bins[j] = a.bins[(size_t)ray * B + j];
-    for (int j = lane; j < n; j += 64) wv[j] = a.weights[(size_t)ray * n + j] + 1e-5f;
-    __syncthreads();
-    const float total = torch_row_sum(wv, n, lane);
-    double total64 = 0.0;      // (the same row in fp64, from the fp32 weights: w + 1e-5 and its sum before any rounding)
-    for (int j = lane; j < n; j += 64) total64 += (double)a.weights[(size_t)ray * n + j] + 1e-5;
-    total64 = wave_sum(total64);
-    double carry = 0.0, carry64 = 0.0;
-    for (int base = 0; base < n; base += 64) {
-        const int j = base + lane;
-        const float pdf = (j < n) ? wv[j] / total : 0.0f;
-        const double incl = wave_incl_sum((double)pdf);
-        const double incl64 = wave_incl_sum((j < n) ? ((double)a.weights[(size_t)ray * n + j] + 1e-5) / total64 : 0.0);
-        if (j < n) { cdf[j + 1] = (float)(carry + incl); cdf64[j + 1] = carry64 + incl64; }
-        carry = carry + __shfl(incl, 63);
-        carry64 = carry64 + __shfl(incl64, 63);
-    }
-    if (lane == 0) { cdf[0] = 0.0f; cdf64[0] = 0.0; }
-    __syncthreads();
-    const float* urow = a.u + (size_t)ray * a.u_row_stride;
-    for (int k = lane; k < N; k += 64) {
-        const size_t o = (size_t)ray * N + k;
-        const float u = urow[k];
-        const int ind = (int)a.inds[o];
-        const int below = ind - 1 > 0 ? ind - 1 : 0;
-        const int above = ind < B - 1 ? ind : B - 1;
-        const float c0 = cdf[below], c1 = cdf[above];
-        const float d = c1 - c0;
-        const bool active = !(d < 1e-5f);
-        const double c0d = cdf64[below];
-        const double denom = active ? cdf64[above] - c0d : 1.0;
-        const double gt = (double)a.g_samples[o] * ((double)bins[above] - (double)bins[below]);
-        const double q = ((double)u - c0d) / denom;            // = t
-        // dt/dc0 = -1/denom + [active] t/denom ;  dt/dc1 = -[active] t/denom
-        g0[k] = (float)(gt * ((-1.0 / denom) + (active ? q / denom : 0.0)));
-        g1[k] = active ? (float)(gt * (-(q / denom))) : 0.0f;
-        lo[k] = below; hi[k] = above;
-    }
-    __syncthreads();
-    for (int j = lane; j < B; j += 64) {
-        float sacc = 0.0f;
-        for (int k = 0; k < N; ++k) {
-            if (lo[k] == j) sacc += g0[k];
-            if (hi[k] == j) sacc += g1[k];
-        }
-        gc[j] = sacc;
-    }
-    __syncthreads();
-    // g_pdf[i] = sum_{j > i} g_cdf[j]  (i = 0..n-1): suffix sums, scanned from the top in fp64
-    double tail = 0.0, dot = 0.0;
-    for (int base = 0; base < n; base += 64) {
-        const int p = base + lane;                  // position from the top: i = n - 1 - p, adds g_cdf[i + 1]
-        const int i = n - 1 - p;
-        const double v = (p < n) ? (double)gc[i + 1] : 0.0;
-        const double incl = wave_incl_sum(v);
-        if (p < n) {
-            const float gp = (float)(tail + incl);
-            dot += (double)gp * (double)(wv[i] / total);   // sum_k g_pdf[k] pdf[k]
-            cdf[i] = gp;                                      // g_pdf (the cdf row is no longer needed)
-        }
-        tail = tail + __shfl(incl, 63);
-    }
-    dot = wave_sum(dot);
-    __syncthreads();
+    const int n = a.in.B - 1;
+    float* cdf = smem + wave * a.lds_stride;
+    float total, dot;
+    sample_const_bwd_rows(a.in, ray, lane, cdf, total, dot);
     if (!live) return;
-    for (int i = lane; i < n; i += 64) a.g_weights[(size_t)ray * n + i] = (cdf[i] - (float)dot) / total;
+    for (int i = lane; i < n; i += 64) a.g_weights[(size_t)ray * n + i] = (cdf[i] - dot) / total;
 }
 
 struct SamplePlArgs {
@@ -526,8 +444,8 @@ extern "C" int plnerf_sample_const_bwd(const float* bins, const float* weights, 
     if (B > PLNERF_MAX_SAMPLES + 2) return PLNERF_ERANGE;
     if (R == 0) return PLNERF_OK;
     if (!bins || !weights || !u || !inds || !g_samples || !g_weights) return PLNERF_EINVAL;
-    SampleConstBwdArgs a{bins, weights, u, u_row_stride, inds, g_samples, R, B, N, 0, g_weights};
-    a.lds_stride = ((6 * B + 4 * N) + 3) & ~3;      // (+ the fp64 cdf)
+    SampleConstBwdArgs a{SampleConstBwdIn{bins, weights, B - 1, u, u_row_stride, inds, g_samples, B, N}, R, 0, g_weights};
+    a.lds_stride = (sample_const_bwd_row_floats(B, N) + 3) & ~3;      // (+ the fp64 cdf)
     const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
     int rc = set_lds((const void*)sample_const_bwd_kernel, lds);
     if (rc) return rc;

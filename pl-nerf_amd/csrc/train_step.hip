@@ -4,8 +4,11 @@
 // the one stream -- so the two routes agree bit for bit; what the Python route does between those launches in torch (the
 // density noise's scale, the loss scale on the two image gradients) is the small kernel of step_common.h.  No kernel of the
 // path is duplicated here.
+// plnerf_train_step_const (include/plnerf_hip_conststep.h) is the same sequence in piecewise-constant mode -- the route
+// TrainStep._step takes for mode == "constant" and under constant_init: one function serves both, `mode` says which.
 #include "step_common.h"
 #include "../../include/plnerf_hip_batching.h"
+#include "../../include/plnerf_hip_conststep.h"
 
 namespace {
 
@@ -50,10 +53,12 @@ Plan carve(const plnerf_step_config* c, void* workspace) {
     return p;
 }
 
-int check_config(const plnerf_step_config* c) {
+// mode: the entry's (plnerf_train_step: PLNERF_MODE_LINEAR; plnerf_train_step_const: PLNERF_MODE_CONSTANT, whose sampler
+// needs one interior weight)
+int check_config(const plnerf_step_config* c, const int mode) {
     if (!c) return PLNERF_EINVAL;
-    if (c->max_rays < 1 || c->n_samples < 2 || c->n_importance < 1) return PLNERF_EINVAL;
-    if (c->mode != PLNERF_MODE_LINEAR) return PLNERF_EINVAL;
+    if (c->max_rays < 1 || c->n_samples < (mode == PLNERF_MODE_LINEAR ? 2 : 3) || c->n_importance < 1) return PLNERF_EINVAL;
+    if (c->mode != mode) return PLNERF_EINVAL;
     if (c->color_mode != PLNERF_COLOR_MIDPOINT && c->color_mode != PLNERF_COLOR_LEFT) return PLNERF_EINVAL;
     if (c->ray_source != PLNERF_STEP_RAYS_VIEW && c->ray_source != PLNERF_STEP_RAYS_BANK) return PLNERF_EINVAL;
     if (c->H < 1 || c->W < 1 || (c->ndc && !(c->ndc_focal != 0.0))) return PLNERF_EINVAL;
@@ -72,17 +77,10 @@ int check_config(const plnerf_step_config* c) {
     return PLNERF_OK;
 }
 
-}  // namespace
-
-extern "C" size_t plnerf_train_step_workspace_bytes(const plnerf_step_config* config) {
-    if (check_config(config) != PLNERF_OK) return 0;
-    return carve(config, nullptr).bytes;
-}
-
-extern "C" int plnerf_train_step(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a,
-                                 void* workspace, size_t workspace_bytes, plnerf_stream_t stream) {
+int train_step(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a, void* workspace,
+               size_t workspace_bytes, plnerf_stream_t stream, const int mode) {
     // ---- every check first: a refused call enqueues nothing ----
-    int rc = check_config(c);
+    int rc = check_config(c, mode);
     if (rc) return rc;
     if (!io || !a || !workspace || ((uintptr_t)workspace % ALIGN) != 0) return PLNERF_EINVAL;
     if (a->rays < 1 || a->rays > c->max_rays || a->ray_id0 < 0) return PLNERF_EINVAL;
@@ -137,10 +135,16 @@ extern "C" int plnerf_train_step(const plnerf_step_config* c, const plnerf_step_
         STEP_OK(plnerf_normal(c->seed, NOISE_STREAM, a->step, a->ray_id0, R, S, p.noise_c, stream));
         if (c->raw_noise_std != 1.0f) STEP_OK(scale2(p.noise_c, (size_t)R * S, nullptr, 0, c->raw_noise_std, st));
     }
-    STEP_OK(plnerf_coarse_epilogue(p.raw_c, p.z_c, p.near, p.far, o, d, noise ? p.noise_c : nullptr,
-                                   c->perturb ? nullptr : io->u_vals, 0, c->seed, a->step, a->ray_id0, R, S, N, c->color_mode,
-                                   c->white_bkgd ? 1 : 0, c->farcolorfix ? 1 : 0, c->zero_tol, c->epsilon, p.rgb0, p.disp0, p.acc0,
-                                   p.depth0, nullptr, nullptr, nullptr, p.z_f, p.pts_f, p.z_std, stream));
+    if (mode == PLNERF_MODE_LINEAR)
+        STEP_OK(plnerf_coarse_epilogue(p.raw_c, p.z_c, p.near, p.far, o, d, noise ? p.noise_c : nullptr,
+                                       c->perturb ? nullptr : io->u_vals, 0, c->seed, a->step, a->ray_id0, R, S, N, c->color_mode,
+                                       c->white_bkgd ? 1 : 0, c->farcolorfix ? 1 : 0, c->zero_tol, c->epsilon, p.rgb0, p.disp0,
+                                       p.acc0, p.depth0, nullptr, nullptr, nullptr, p.z_f, p.pts_f, p.z_std, stream));
+    else
+        STEP_OK(plnerf_coarse_epilogue_const(p.raw_c, p.z_c, p.near, p.far, o, d, noise ? p.noise_c : nullptr,
+                                             c->perturb ? nullptr : io->u_vals, 0, c->seed, a->step, a->ray_id0, R, S, N,
+                                             c->white_bkgd ? 1 : 0, p.rgb0, p.disp0, p.acc0, p.depth0, nullptr, p.z_f, p.pts_f,
+                                             p.z_std, stream));
 
     // ---- fine pass ----
     STEP_OK(plnerf_mlp_pack_weights(io->fine.params, prec, xyz, dir, io->fine.packed, stream));
@@ -150,7 +154,7 @@ extern "C" int plnerf_train_step(const plnerf_step_config* c, const plnerf_step_
         STEP_OK(plnerf_normal(c->seed, NOISE_STREAM + 1, a->step, a->ray_id0, R, F, p.noise_f, stream));
         if (c->raw_noise_std != 1.0f) STEP_OK(scale2(p.noise_f, (size_t)R * F, nullptr, 0, c->raw_noise_std, st));
     }
-    STEP_OK(plnerf_quad_fwd(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, R, F, PLNERF_MODE_LINEAR, c->color_mode,
+    STEP_OK(plnerf_quad_fwd(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, R, F, mode, c->color_mode,
                             c->white_bkgd ? 1 : 0, c->farcolorfix ? 1 : 0, p.rgb, p.disp, p.acc, p.depth, nullptr, nullptr, nullptr,
                             stream));
 
@@ -159,10 +163,10 @@ extern "C" int plnerf_train_step(const plnerf_step_config* c, const plnerf_step_
     if (a->loss_scale != 1.0f) STEP_OK(scale2(p.g_rgb, (size_t)R * 3, p.g_rgb0, (size_t)R * 3, a->loss_scale, st));
 
     // ---- backward: d loss / d raw of either pass (the fine one first, as autograd orders them), then both networks at once ----
-    STEP_OK(plnerf_quad_bwd(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, R, F, PLNERF_MODE_LINEAR, c->color_mode,
+    STEP_OK(plnerf_quad_bwd(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, R, F, mode, c->color_mode,
                             c->white_bkgd ? 1 : 0, c->farcolorfix ? 1 : 0, p.g_rgb, nullptr, nullptr, nullptr, nullptr, nullptr,
                             p.g_raw_f, p.absmax_f, stream));
-    STEP_OK(plnerf_quad_bwd(p.raw_c, p.z_c, p.near, p.far, d, noise ? p.noise_c : nullptr, R, S, PLNERF_MODE_LINEAR, c->color_mode,
+    STEP_OK(plnerf_quad_bwd(p.raw_c, p.z_c, p.near, p.far, d, noise ? p.noise_c : nullptr, R, S, mode, c->color_mode,
                             c->white_bkgd ? 1 : 0, c->farcolorfix ? 1 : 0, p.g_rgb0, nullptr, nullptr, nullptr, nullptr, nullptr,
                             p.g_raw_c, p.absmax_c, stream));
     const plnerf_step_net* nets[2] = {&io->coarse, &io->fine};
@@ -192,4 +196,27 @@ extern "C" int plnerf_train_step(const plnerf_step_config* c, const plnerf_step_
                              io->coarse.skip_if_set, io->coarse.skip_if_set2, io->coarse.withheld, stream));
 #undef STEP_OK
     return PLNERF_OK;
+}
+
+}  // namespace
+
+extern "C" size_t plnerf_train_step_workspace_bytes(const plnerf_step_config* config) {
+    if (check_config(config, PLNERF_MODE_LINEAR) != PLNERF_OK) return 0;
+    return carve(config, nullptr).bytes;
+}
+
+extern "C" int plnerf_train_step(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a,
+                                 void* workspace, size_t workspace_bytes, plnerf_stream_t stream) {
+    return train_step(c, io, a, workspace, workspace_bytes, stream, PLNERF_MODE_LINEAR);
+}
+
+// ---- piecewise-constant mode (include/plnerf_hip_conststep.h): the same carve, so the same bytes and offsets ----
+extern "C" size_t plnerf_train_step_const_workspace_bytes(const plnerf_step_config* config) {
+    if (check_config(config, PLNERF_MODE_CONSTANT) != PLNERF_OK) return 0;
+    return carve(config, nullptr).bytes;
+}
+
+extern "C" int plnerf_train_step_const(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a,
+                                       void* workspace, size_t workspace_bytes, plnerf_stream_t stream) {
+    return train_step(c, io, a, workspace, workspace_bytes, stream, PLNERF_MODE_CONSTANT);
 }

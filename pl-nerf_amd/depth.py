@@ -725,7 +725,7 @@ class DepthTrainStep:
     has one arithmetic); with one_call=False it stays torch.optim.Adam."""
 
     def __init__(self, args, render_kwargs_train, optimizer, grad_vars, distributed=None, range_check_every=100, seed=0,
-                 counter_rng=True, start=0, n_views=None, one_call=False):
+                 counter_rng=True, start=0, n_views=None, one_call=False, one_call_const=False):
         """counter_rng: the step's draws (stratified jitter, importance samples, the hypotheses' u) come from a
         functional.DrawSource keyed on (seed, step, GLOBAL ray id) and are generated inside the kernels that consume
         them -- a global batch gives the same step whether one rank renders it or N ranks a shard each, like
@@ -742,6 +742,12 @@ class DepthTrainStep:
         self._ss_grad = None
         self.one_call = bool(one_call)
         self.one_call_steps = 0
+        # one_call_const=True (on its own or beside one_call): a step that qualifies in every respect but renders in
+        # piecewise-constant mode (kw["mode"] == "constant", N_samples >= 3) goes to plnerf_depth_train_step_const
+        # (include/plnerf_hip_conststep.h) and counts in one_call_const_steps, never in one_call_steps.  Either switch moves
+        # the scales' and shifts' Adam to plnerf_depth_ss_adam, as the class docstring says of one_call.
+        self.one_call_const = bool(one_call_const)
+        self.one_call_const_steps = 0
         self._plan = self._plan_key = None
         self._ss_m = self._ss_v = None      # one_call: the scale / shift Adam's moments [2, V] and its step count
         self._ss_steps = 0
@@ -773,7 +779,7 @@ class DepthTrainStep:
         self.depth_scales = (ones * getattr(a, "scale_init", 1.0)).requires_grad_(True)
         self.depth_shifts = (ones * getattr(a, "shift_init", 0.0)).requires_grad_(True)
         self._ss_grad = torch.zeros(2, int(n_views), device=device)
-        if self.one_call:      # plnerf_depth_ss_adam: torch.optim.Adam's defaults, moments and step count kept here
+        if self.one_call or self.one_call_const:      # plnerf_depth_ss_adam: torch.optim.Adam's defaults, moments and step count kept here
             self.optimizer_ss = None
             self._ss_m, self._ss_v, self._ss_steps = torch.zeros_like(self._ss_grad), torch.zeros_like(self._ss_grad), 0
         else:
@@ -818,7 +824,7 @@ class DepthTrainStep:
         if lr is not None:      # train_utils/hyperparameter_update.py:3-5
             for group in self.optimizer.param_groups:
                 group['lr'] = lr
-        if self.one_call:
+        if self.one_call or self.one_call_const:
             done = self._step_view_one_call(views, img_i, n_rand, i)
             if done is not None:
                 return done
@@ -837,14 +843,19 @@ class DepthTrainStep:
         of _step with the merged backward: two native networks in one 16-bit guarded precision and with one density
         activation, piecewise-linear mode with importance sampling, counter-based draws, the kernels' own encoding on an
         identity bounding box, no camera code, a batch that fits one launch per network, one process, nobody watching the
-        stages (STAGE_TAP, functional.KERNEL_TIMER), not `pytest`."""
+        stages (STAGE_TAP, functional.KERNEL_TIMER), not `pytest`.  kw["mode"] == "constant" qualifies the same way for
+        plnerf_depth_train_step_const when one_call_const is set (N_samples >= 3), piecewise-linear mode when one_call is.
+        Returns the networks' input scale, or None."""
         kw = self.kw
         if not (self.merged_backward and self.draws is not None and self.bucket is None and len(self.nets) == 2):
             return None
         if STAGE_TAP is not None or Fn.KERNEL_TIMER is not None or not FUSE_STAGES or not isinstance(views, DepthViews):
             return None
         S, N = int(kw.get("N_samples", 0)), int(kw.get("N_importance", 0))
-        if kw.get("mode") != "linear" or kw.get("color_mode") not in ("midpoint", "left") or kw.get("pytest", False) or \
+        mode = kw.get("mode")
+        if not ((mode == "linear" and self.one_call) or (mode == "constant" and self.one_call_const and S >= 3)):
+            return None
+        if kw.get("color_mode") not in ("midpoint", "left") or kw.get("pytest", False) or \
                 not kw.get("use_viewdirs", False) or N < 1 or S < 2 or S + N > L.DEPTH_STEP_MAX_SAMPLES:
             return None
         if kw.get("precomputed_z_samples") is not None or kw.get("cached_u") is not None:
@@ -893,7 +904,8 @@ class DepthTrainStep:
         if input_scale is None or not 0 <= int(img_i) < views.n_views or self.rank * n_rand + n_rand > views.H * views.W:
             return None
         plan = self._plan_for(views, n_rand, input_scale)
-        adam_step = plan.adam_step() if plan is not None else None
+        mode = self.kw["mode"]
+        adam_step = plan.adam_step() if (plan is not None and mode in plan.modes) else None
         if adam_step is None:
             return None
         a = self.args
@@ -902,10 +914,14 @@ class DepthTrainStep:
         if ss_step:
             self._ss_steps += 1
         loss5 = plan.run(int(img_i), n_rand, self.global_step, self.rank * n_rand, self.optimizer.param_groups[0]['lr'],
-                         adam_step, weight > 0. and i > warm, ss_step, float(getattr(a, "scaleshift_lr", 1e-6)), self._ss_steps)
+                         adam_step, weight > 0. and i > warm, ss_step, float(getattr(a, "scaleshift_lr", 1e-6)), self._ss_steps,
+                         mode=mode)
         self.last_pixels = plan.view_of("pixels", (n_rand, 2), torch.int32)
         self.global_step += 1
-        self.one_call_steps += 1
+        if mode == "constant":
+            self.one_call_const_steps += 1
+        else:
+            self.one_call_steps += 1
         if self.range_check_every and self.global_step % self.range_check_every == 0:
             self.check_range()
         return loss5[0], loss5[1], loss5[3], plan.outputs(n_rand)
@@ -987,7 +1003,7 @@ class DepthTrainStep:
         ss_step = ss is not None and carve
         if ss_step and ss_work is not None:
             ss_work.wait()
-            if not self.one_call:      # (plnerf_depth_ss_adam takes the factor as its grad_scale)
+            if not (self.one_call or self.one_call_const):      # (plnerf_depth_ss_adam takes the factor as its grad_scale)
                 self._ss_grad.mul_(1.0 / self.world)
         if flat_adam:
             # clip_grad_value_(0.1) folded into the step kernel (:1156), applied to the averaged gradient
@@ -997,7 +1013,7 @@ class DepthTrainStep:
         else:
             torch.nn.utils.clip_grad_value_(self.grad_vars, 0.1)
             self.optimizer.step()
-        if ss_step and self.one_call:
+        if ss_step and (self.one_call or self.one_call_const):
             self._ss_steps += 1
             L.check(L.lib().plnerf_depth_ss_adam(
                 L.dptr(self.depth_scales.detach(), "depth_scales"), L.dptr(self.depth_shifts.detach(), "depth_shifts"),

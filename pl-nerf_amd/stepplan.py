@@ -1,4 +1,5 @@
-"""The host side of plnerf_train_step (include/plnerf_hip_step.h): one library call per optimisation step.
+"""The host side of plnerf_train_step (include/plnerf_hip_step.h) and of its piecewise-constant sibling
+plnerf_train_step_const (include/plnerf_hip_conststep.h): one library call per optimisation step.
 
 A `StepPlan` owns what the call needs beyond the networks and their optimizers -- the workspace the library carves up,
 the flat gradient buffer whose slices become the parameters' `.grad`, the two linspace tables -- and the three structs
@@ -156,9 +157,18 @@ class StepPlan:
         cfg.beta1, cfg.beta2, cfg.adam_eps = float(group['betas'][0]), float(group['betas'][1]), float(group['eps'])
         cfg.seed = int(seed)
         cfg.bank_seed = int(bank.seed) if bank is not None else 0
-        nbytes = L.lib().plnerf_train_step_workspace_bytes(ctypes.byref(cfg))
+        # ONE workspace for both entries (plnerf_train_step and its constant-mode sibling plnerf_train_step_const carve it
+        # alike): a constant_init warm-up switches entries between steps on the same memory and the same gradient buffers.
+        # A query answers 0 for the mode its entry does not serve, and for a shape its kernels refuse (N_samples = 2).
+        by_mode = {}
+        for mode, query in (("linear", L.lib().plnerf_train_step_workspace_bytes),
+                            ("constant", L.lib().plnerf_train_step_const_workspace_bytes)):
+            cfg.mode = L.MODE[mode]
+            by_mode[mode] = query(ctypes.byref(cfg))
+        self.modes = tuple(m for m, n in by_mode.items() if n)
+        nbytes = max(by_mode.values())
         if nbytes == 0:
-            raise ValueError("plnerf_train_step refuses this configuration")
+            raise ValueError("plnerf_train_step and plnerf_train_step_const refuse this configuration")
         # zeroed once: the loss kernel's partial sums (every step leaves them zeroed)
         raw = torch.zeros((nbytes + L.STEP_WORKSPACE_ALIGN) // 4 + 1, device=dev, dtype=torch.float32)
         pad = (-raw.data_ptr()) % L.STEP_WORKSPACE_ALIGN
@@ -194,10 +204,11 @@ class StepPlan:
         return None if (c is None or f is None) else (c, f)
 
     def run(self, rays, step, ray_id0, lr_coarse, lr_fine, adam_steps, loss_scale=1.0, c2w=None, image=None, crop=None,
-            epoch=0, pos0=0):
+            epoch=0, pos0=0, mode="linear"):
         """Enqueue one step on the current stream; returns its loss4 = [total, fine, coarse, psnr] (a fresh tensor: an
         earlier step's stays what it was).  c2w: 12 host floats; image: the view's [H, W, 3] fp32 device tensor; crop:
-        (r0, c0, rows, cols)."""
+        (r0, c0, rows, cols).  mode "constant": the step in piecewise-constant mode (plnerf_train_step_const), one of
+        self.modes."""
         a = self.args
         a.rays, a.step, a.ray_id0 = rays, step, ray_id0
         if self.kind == "view":
@@ -212,7 +223,12 @@ class StepPlan:
         loss4 = torch.empty(4, device=self.device)
         self.io.loss4 = loss4.data_ptr()
         cfg, io, args, ws = self._refs
-        L.check(L.lib().plnerf_train_step(cfg, io, args, ws, self.workspace_bytes, L.stream()), "plnerf_train_step")
+        self.config.mode = L.MODE[mode]
+        if mode == "constant":
+            L.check(L.lib().plnerf_train_step_const(cfg, io, args, ws, self.workspace_bytes, L.stream()),
+                    "plnerf_train_step_const")
+        else:
+            L.check(L.lib().plnerf_train_step(cfg, io, args, ws, self.workspace_bytes, L.stream()), "plnerf_train_step")
         self.slots[0].advance()
         self.slots[1].advance()
         return loss4
@@ -275,16 +291,25 @@ class DepthStepPlan:
         cfg.beta1, cfg.beta2, cfg.adam_eps = float(group['betas'][0]), float(group['betas'][1]), float(group['eps'])
         cfg.ss_beta1, cfg.ss_beta2, cfg.ss_adam_eps = float(ss_betas[0]), float(ss_betas[1]), float(ss_eps)
         cfg.seed = int(seed)
-        nbytes = L.lib().plnerf_depth_train_step_workspace_bytes(ctypes.byref(cfg))
+        # one workspace for both entries (plnerf_depth_train_step_const carves it as the linear entry does, so the layout
+        # below serves either); a query answers 0 for a shape its kernels refuse
+        by_mode = {"linear": L.lib().plnerf_depth_train_step_workspace_bytes(ctypes.byref(cfg)),
+                 "constant": L.lib().plnerf_depth_train_step_const_workspace_bytes(ctypes.byref(cfg))}
+        self.modes = tuple(m for m, n in by_mode.items() if n)
+        nbytes = max(by_mode.values())
         if nbytes == 0:
-            raise ValueError("plnerf_depth_train_step refuses this configuration")
+            raise ValueError("plnerf_depth_train_step and plnerf_depth_train_step_const refuse this configuration")
         raw = torch.zeros((nbytes + L.STEP_WORKSPACE_ALIGN) // 4 + 1, device=dev, dtype=torch.float32)
         pad = (-raw.data_ptr()) % L.STEP_WORKSPACE_ALIGN
         self.workspace = raw[pad // 4:]
         self.workspace_bytes = nbytes
         self.layout = L.DepthStepViews()
-        L.check(L.lib().plnerf_depth_train_step_layout(ctypes.byref(cfg), ctypes.byref(self.layout)),
-                "plnerf_depth_train_step_layout")
+        if by_mode["linear"]:
+            L.check(L.lib().plnerf_depth_train_step_layout(ctypes.byref(cfg), ctypes.byref(self.layout)),
+                    "plnerf_depth_train_step_layout")
+        else:
+            L.check(L.lib().plnerf_depth_train_step_const_layout(ctypes.byref(cfg), ctypes.byref(self.layout)),
+                    "plnerf_depth_train_step_const_layout")
         self.t_vals = Fn.cpu_linspace(cfg.n_samples, dev)
         self.u_vals = Fn.cpu_linspace(cfg.n_importance, dev)
         # both networks' gradients back to back in one allocation, a GRAD_TAIL behind each: functional._mlp_backward_launch's
@@ -320,9 +345,10 @@ class DepthStepPlan:
         c, f = self.slots[0].next_adam_step(), self.slots[1].next_adam_step()
         return c if (c is not None and c == f) else None
 
-    def run(self, view, rays, step, ray_id0, lr, adam_step, carve, ss_step=False, ss_lr=0.0, ss_adam_step=0):
+    def run(self, view, rays, step, ray_id0, lr, adam_step, carve, ss_step=False, ss_lr=0.0, ss_adam_step=0, mode="linear"):
         """Enqueue one step on the current stream; returns its loss5 = [total, image, image (coarse), space carving, psnr]
-        (a fresh tensor: an earlier step's stays what it was)."""
+        (a fresh tensor: an earlier step's stays what it was).  mode "constant": plnerf_depth_train_step_const (one of
+        self.modes)."""
         a = self.args
         a.view, a.rays, a.step, a.ray_id0 = view, rays, step, ray_id0
         a.lr, a.adam_step = lr, adam_step
@@ -330,7 +356,12 @@ class DepthStepPlan:
         loss5 = torch.empty(5, device=self.device)
         self.io.loss5 = loss5.data_ptr()
         cfg, io, args, ws = self._refs
-        L.check(L.lib().plnerf_depth_train_step(cfg, io, args, ws, self.workspace_bytes, L.stream()), "plnerf_depth_train_step")
+        if mode == "constant":
+            L.check(L.lib().plnerf_depth_train_step_const(cfg, io, args, ws, self.workspace_bytes, L.stream()),
+                    "plnerf_depth_train_step_const")
+        else:
+            L.check(L.lib().plnerf_depth_train_step(cfg, io, args, ws, self.workspace_bytes, L.stream()),
+                    "plnerf_depth_train_step")
         self.slots[0].advance()
         self.slots[1].advance()
         return loss5

@@ -242,7 +242,7 @@ class TrainStep:
     renders it or N ranks render a shard each.  `counter_rng=False` restores torch.rand."""
 
     def __init__(self, args, render_kwargs_train, optimizer, optimizer_coarse, start=0, distributed=None, seed=0,
-                 counter_rng=True, range_check_every=100, pipeline=None, one_call=False):
+                 counter_rng=True, range_check_every=100, pipeline=None, one_call=False, one_call_const=False):
         """The step runs on ONE stream in the reference's order: render, loss, backward, both optimizers.  (Rounds 3-4
         also carried two-stream schedules -- the coarse network's chain beside the fine pass, and across step boundaries;
         bit-identical, measured +1.4 % / -0.8 % with twice the step jitter, profiles/r04_pipeline_ab.txt -- removed in
@@ -282,6 +282,13 @@ class TrainStep:
         # step that does not qualify takes the route below, silently; one_call_steps counts the ones that did.
         self.one_call = bool(one_call)
         self.one_call_steps = 0
+        # one_call_const=True (on its own or beside one_call): a step that qualifies in every respect but renders in
+        # piecewise-constant mode -- kw["mode"] == "constant" (the vanilla-NeRF baseline), or a constant_init warm-up step --
+        # goes to plnerf_train_step_const (include/plnerf_hip_conststep.h), which needs N_samples >= 3; those steps count in
+        # one_call_const_steps, never in one_call_steps.  Both entries step on the one StepPlan: one workspace, one set of
+        # flat gradient buffers across the warm-up's switch.
+        self.one_call_const = bool(one_call_const)
+        self.one_call_const_steps = 0
         self._plan = self._plan_key = None
         self.bucket = None
         if distributed and self.world > 1:
@@ -304,7 +311,7 @@ class TrainStep:
         """The loop body from the view on (run_plnerf.py:1259-1316): choose this rank's n_rand pixels of the view on
         the device, then the optimisation step.  `image` [H, W, 3] lives on the device."""
         n_rand = int(n_rand if n_rand is not None else self.args.N_rand)
-        if self.one_call:
+        if self.one_call or self.one_call_const:
             out = self._step_view_one_call(H, W, K, c2w, image, near, far, n_rand, precrop)
             if out is not None:
                 return out
@@ -326,13 +333,16 @@ class TrainStep:
         n_rand = int(n_rand if n_rand is not None else self.args.N_rand)
         want_vd = bool(self.kw.get("use_viewdirs", True))
         epoch, p0, n = bank.schedule(self.global_step, n_rand * self.world)
-        if self.one_call and self._one_call_ok(n) and n <= n_rand:      # (one process: the whole batch, weight 1)
+        # (one process: the whole batch, weight 1)
+        mode = self._one_call_mode(n) if ((self.one_call or self.one_call_const) and n <= n_rand) else None
+        if mode is not None:
             plan = self._plan_for("bank", n_rand, bank.H, bank.W, bank.K, bank.near, bank.far, bank)
-            steps = plan.adam_steps() if plan is not None else None
+            steps = plan.adam_steps() if (plan is not None and mode in plan.modes) else None
             if steps is not None:
                 self.last_batch = (epoch, p0, n, 0, n)
                 return self._one_call_done(plan.run(n, self.global_step, 0, self.optimizer_coarse.param_groups[0]['lr'],
-                                                    self.optimizer.param_groups[0]['lr'], steps, epoch=epoch, pos0=p0))
+                                                    self.optimizer.param_groups[0]['lr'], steps, epoch=epoch, pos0=p0,
+                                                    mode=mode), mode)
         begin, end = dp.shard_batch(n, self.rank, self.world)
         self.last_batch = (epoch, p0 + begin, end - begin, begin, n)      # (epoch, first position, rays, offset, global n)
         if end > begin:
@@ -352,30 +362,45 @@ class TrainStep:
         return self._step(H, W, K, batch_rays, target_s, near, far)
 
     def _one_call_ok(self, n_rays):
-        """Can this step go to the library as one call (plnerf_train_step)?  What the entry enqueues is the fused route of
+        """Can this step go to the library as one call of plnerf_train_step (one_call; the piecewise-linear entry)?"""
+        return self._one_call_mode(n_rays) == "linear"
+
+    def _one_call_mode(self, n_rays):
+        """Can this step go to the library as one call, and through which entry: "linear" (plnerf_train_step, with one_call),
+        "constant" (plnerf_train_step_const, with one_call_const) or None?  What an entry enqueues is the fused route of
         _step with the merged backward: the reference's two native networks in one 16-bit precision (merged_backward_ok's
-        conditions, known here before anything runs), piecewise-linear mode with importance sampling, counter-based draws,
-        the kernels' own encoding, a batch that fits one launch per network, one process, nobody watching the stages
-        (render.STAGE_TAP, functional.KERNEL_TIMER) -- and not a constant_init warm-up step."""
+        conditions, known here before anything runs), importance sampling, counter-based draws, the kernels' own encoding,
+        a batch that fits one launch per network, one process, nobody watching the stages (render.STAGE_TAP,
+        functional.KERNEL_TIMER).  The step's mode is the render's: kw["mode"], or constant under the constant_init warm-up;
+        constant mode also needs its one-launch coarse stage (render.FUSE_CONST_EPILOGUE, N_samples >= 3)."""
         kw = self.kw
         if not (self.merged_backward and self.draws is not None and self.bucket is None and len(self.nets) == 2):
-            return False
-        if self.global_step + 1 < getattr(self.args, "constant_init", 0) or Rn.STAGE_TAP is not None or \
-                Fn.KERNEL_TIMER is not None:
-            return False
+            return None
+        if Rn.STAGE_TAP is not None or Fn.KERNEL_TIMER is not None:
+            return None
         S, N = int(kw.get("N_samples", 0)), int(kw.get("N_importance", 0))
-        if kw.get("mode") != "linear" or kw.get("color_mode") not in ("midpoint", "left") or kw.get("pytest", False) or \
+        mode = "constant" if self.global_step + 1 < getattr(self.args, "constant_init", 0) else kw.get("mode")
+        if mode == "linear":
+            if not self.one_call:
+                return None
+        elif mode == "constant":
+            if not (self.one_call_const and Rn.FUSE_CONST_EPILOGUE and S >= 3):
+                return None
+        else:
+            return None
+        if kw.get("color_mode") not in ("midpoint", "left") or kw.get("pytest", False) or \
                 not kw.get("use_viewdirs", False) or N < 1 or S < 2 or S + N > 1024:
-            return False
+            return None
         if not 1 <= n_rays <= getattr(self.args, "chunk", 1024 * 32) or n_rays * (S + N) > Rn.MAX_ROWS_PER_LAUNCH:
-            return False
+            return None
         emb = getattr(kw.get("network_query_fn"), "embedders", None)      # (create_nerf's query function says what it encodes with)
         if emb is None:
-            return False
+            return None
         c, f = self.nets
-        return c is not f and c.precision == f.precision and all(
+        ok = c is not f and c.precision == f.precision and all(
             n.is_native() and n.precision in L.GUARDED_PRECISIONS and n.density_beta == 0.0 and Rn._fusable(n, emb[0], emb[1], True)
             and all(p.is_cuda and p.requires_grad for p in n.param_list()) for n in (c, f))
+        return mode if ok else None
 
     def _plan_for(self, kind, max_rays, H, W, K, near, far, bank):
         """The StepPlan of this configuration: the one in hand while it still describes the live buffers, else a new one
@@ -393,11 +418,13 @@ class TrainStep:
         return self._plan
 
     def _step_view_one_call(self, H, W, K, c2w, image, near, far, n_rand, precrop):
-        """step_view through plnerf_train_step; None when the step does not qualify (nothing has happened then)."""
-        if image is None or not image.is_cuda or not self._one_call_ok(n_rand):
+        """step_view through plnerf_train_step or plnerf_train_step_const; None when the step does not qualify (nothing has
+        happened then)."""
+        mode = self._one_call_mode(n_rand) if (image is not None and image.is_cuda) else None
+        if mode is None:
             return None
         plan = self._plan_for("view", n_rand, H, W, K, near, far, None)
-        steps = plan.adam_steps() if plan is not None else None
+        steps = plan.adam_steps() if (plan is not None and mode in plan.modes) else None
         if steps is None:
             return None
         if precrop is not None:
@@ -409,9 +436,9 @@ class TrainStep:
         img = image.detach().to(torch.float32).contiguous()
         return self._one_call_done(plan.run(n_rand, self.global_step, self.rank * n_rand,
                                             self.optimizer_coarse.param_groups[0]['lr'], self.optimizer.param_groups[0]['lr'],
-                                            steps, c2w=c2w_host, image=img, crop=crop))
+                                            steps, c2w=c2w_host, image=img, crop=crop, mode=mode), mode)
 
-    def _one_call_done(self, loss4):
+    def _one_call_done(self, loss4, mode="linear"):
         """The host state _step leaves behind: both learning rates, the step count, the range poll."""
         new_lrate = self.learning_rate()
         for group in self.optimizer.param_groups:
@@ -419,7 +446,10 @@ class TrainStep:
         for group in self.optimizer_coarse.param_groups:
             group['lr'] = new_lrate                   # sic: the reference uses the fine rate here (line 1315)
         self.global_step += 1
-        self.one_call_steps += 1
+        if mode == "constant":
+            self.one_call_const_steps += 1
+        else:
+            self.one_call_steps += 1
         if self.range_check_every and self.global_step % self.range_check_every == 0:
             self.check_range()
         return loss4[0], loss4[3]
