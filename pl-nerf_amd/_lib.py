@@ -245,6 +245,33 @@ CONSTSTEP_SIGNATURES = {
                                             ctypes.POINTER(DepthStepArgs), c_f, ctypes.c_size_t, c_s]),
 }
 
+# Every header of the C ABI, in binding order: (file under include/, its signatures, its struct mirrors).  A new header is
+# one row here; tests/test_abi_headers.py compares each row with its header and with the library.
+HEADERS = (
+    ("plnerf_hip.h", SIGNATURES, {}),
+    ("plnerf_hip_batching.h", BATCHING_SIGNATURES, {}),
+    ("plnerf_hip_eval.h", EVAL_SIGNATURES, {}),
+    ("plnerf_hip_depthfeed.h", DEPTHFEED_SIGNATURES, {}),
+    ("plnerf_hip_sampleerr.h", SAMPLEERR_SIGNATURES, {}),
+    ("plnerf_hip_constepi.h", CONSTEPI_SIGNATURES, {}),
+    ("plnerf_hip_step.h", STEP_SIGNATURES, STEP_STRUCTS),
+    ("plnerf_hip_depthstep.h", DEPTHSTEP_SIGNATURES, DEPTHSTEP_STRUCTS),
+    ("plnerf_hip_conststep.h", CONSTSTEP_SIGNATURES, {}),
+)
+
+
+def _merge(headers):
+    """name -> (restype, argtypes) over every header; a name declared twice would be bound twice, the later list winning."""
+    merged, owner = {}, {}
+    for header, signatures, _ in headers:
+        for name, signature in signatures.items():
+            if name in merged:
+                raise ValueError(f"{name} is declared by both {owner[name]} and {header}: one entry point, one header")
+            merged[name], owner[name] = signature, header
+    return merged
+
+
+ALL_SIGNATURES = _merge(HEADERS)      # every entry point of the library
 
 _lib = None
 
@@ -260,9 +287,7 @@ def lib():
                 "plnerf_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(BATCHING_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + \
-                list(DEPTHFEED_SIGNATURES.items()) + list(SAMPLEERR_SIGNATURES.items()) + list(CONSTEPI_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + \
-                list(DEPTHSTEP_SIGNATURES.items()) + list(CONSTSTEP_SIGNATURES.items()):
+        for name, (res, args) in ALL_SIGNATURES.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -4,7 +4,7 @@
  * is part of -pedantic -Werror), a symbol missing from the library a link error -- then calls the ones that need no
  * GPU.  Compiled and run by tests/test_host_cpu.py::test_header_is_plain_c_and_links; the same prototypes are parsed
  * from the header and compared with the ctypes signatures of pl-nerf_amd/_lib.py by
- * test_ctypes_signatures_match_the_header. */
+ * tests/test_abi_headers.py. */
 #include <stdio.h>
 #include "plnerf_hip.h"
 

@@ -1,64 +1,16 @@
 """The C ABI of the use_batching ray source (include/plnerf_hip_batching.h), without a GPU: the header is plain C99 and
-links against the library with the declared prototype, its argument validation runs before any device work, and the
-ctypes binding (_lib.BATCHING_SIGNATURES) matches the header argument by argument -- the checks tests/abi_check.c and
-test_host_cpu.py apply to plnerf_hip.h."""
-import ctypes
-import os
-import re
+links against the library with the declared prototype, and its argument validation runs before any device work.  (The
+ctypes binding _lib.BATCHING_SIGNATURES against the header: tests/test_abi_headers.py.)"""
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-HEADER = os.path.join(ROOT, "include", "plnerf_hip_batching.h")
+import abi_support as abi
 
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
-    from plnerf_amd import _lib
-    return _lib
-
-
-def _prototypes(path):
-    code = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"^(int|size_t|const char\*)\s+(plnerf_\w+)\s*\(([^;]*?)\)\s*;", code, flags=re.M | re.S):
-        params = [re.match(r"^(.*?)\b\w+$", a).group(1).strip()
-                  for a in (x.strip() for x in " ".join(args.split()).split(",")) if a != "void"]
-        protos[name] = (ret, params)
-    return protos
-
-
-def _c_class(t):
-    t = t.replace("const ", "").strip()
-    if t.endswith("*") or t == "plnerf_stream_t":
-        return "ptr"
-    return {"int": "i32", "float": "f32", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64", "size_t": "u64",
-            "double": "f64"}[t]
-
-
-def _ct_class(t):
-    if t is ctypes.c_char_p or t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
-        return "ptr"
-    return {ctypes.c_int: "i32", ctypes.c_float: "f32", ctypes.c_uint64: "u64", ctypes.c_uint32: "u32",
-            ctypes.c_int64: "i64", ctypes.c_double: "f64"}[t]
-
-
-def test_ctypes_signatures_match_the_batching_header(L):
-    protos = _prototypes(HEADER)
-    assert set(protos) == set(L.BATCHING_SIGNATURES) == {"plnerf_select_bank_rays"}
-    assert not set(protos) & set(L.SIGNATURES)
-    for name, (ret, params) in protos.items():
-        res, args = L.BATCHING_SIGNATURES[name]
-        assert _ct_class(res) == _c_class(ret)
-        assert [_ct_class(t) for t in args] == [_c_class(c) for c in params], name
-    assert L.ABI_VERSION == 601 and L.lib().plnerf_version() == 601
+    return abi.built_lib()
 
 
 _C = r"""
@@ -95,13 +47,7 @@ int main(void) {
 
 
 def test_batching_header_is_plain_c_and_links(L, tmp_path):
-    src = tmp_path / "batching_abi.c"
-    src.write_text(_C)
-    exe = str(tmp_path / "batching_abi")
-    libdir = os.path.dirname(L.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                    "-o", exe, "-L", libdir, "-lplnerf_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, timeout=120)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert set(L.BATCHING_SIGNATURES) == {"plnerf_select_bank_rays"}
+    out = subprocess.run([abi.compile_c(_C, tmp_path, "batching_abi")], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, (out.returncode, out.stdout, out.stderr)
     assert "batching abi ok" in out.stdout

@@ -1,20 +1,17 @@
 """Piecewise-constant mode's one-launch stages without a GPU: the C ABI of include/plnerf_hip_constepi.h (plain C99, links
-against the library, ctypes binding _lib.CONSTEPI_SIGNATURES argument by argument, both symbols exported) and every refusal
-of its table, which is decided before anything touches a device: the calls below carry NULL device pointers and run on a
-machine without one."""
+against the library, both symbols exported; the signatures themselves are compared in tests/test_abi_headers.py) and every
+refusal of its table, which is decided before anything touches a device: the calls below carry NULL device pointers and run
+on a machine without one."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import abi_support as abi
 
-HEADER = os.path.join(ROOT, "include", "plnerf_hip_constepi.h")
+HEADER = os.path.join(abi.INCLUDE, "plnerf_hip_constepi.h")
 NAMES = {"plnerf_coarse_epilogue_const", "plnerf_fine_epilogue_const"}
 OK, EINVAL, ERANGE = 0, -1, -3
 MAX_SAMPLES = 1022      # PLNERF_MAX_SAMPLES
@@ -22,60 +19,22 @@ MAX_SAMPLES = 1022      # PLNERF_MAX_SAMPLES
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
-    from plnerf_amd import _lib
-    return _lib
+    return abi.built_lib()
 
 
-def _prototypes(path):
-    code = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"^(int|size_t|const char\*)\s+(plnerf_\w+)\s*\(([^;]*?)\)\s*;", code, flags=re.M | re.S):
-        params = [re.match(r"^(.*?)\b\w+$", a).group(1).strip()
-                  for a in (x.strip() for x in " ".join(args.split()).split(",")) if a != "void"]
-        protos[name] = (ret, params)
-    return protos
-
-
-def _c_class(t):
-    t = t.replace("const ", "").strip()
-    if t.endswith("*") or t == "plnerf_stream_t":
-        return "ptr"
-    return {"int": "i32", "float": "f32", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64", "size_t": "u64"}[t]
-
-
-def _ct_class(t):
-    if t is ctypes.c_char_p or t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
-        return "ptr"
-    return {ctypes.c_int: "i32", ctypes.c_float: "f32", ctypes.c_uint64: "u64", ctypes.c_uint32: "u32",
-            ctypes.c_int64: "i64"}[t]
-
-
-def test_ctypes_signatures_match_the_constepi_header(L):
-    protos = _prototypes(HEADER)
+def test_constepi_names_and_argument_counts_match_the_header(L):
+    protos = abi.prototypes(HEADER)
     assert set(protos) == set(L.CONSTEPI_SIGNATURES) == NAMES
-    assert not NAMES & (set(L.SIGNATURES) | set(L.BATCHING_SIGNATURES) | set(L.EVAL_SIGNATURES) |
-                        set(L.DEPTHFEED_SIGNATURES) | set(L.SAMPLEERR_SIGNATURES) | set(L.STEP_SIGNATURES) |
-                        set(L.DEPTHSTEP_SIGNATURES))
-    for name, (ret, params) in protos.items():
-        res, args = L.CONSTEPI_SIGNATURES[name]
-        assert _ct_class(res) == _c_class(ret)
-        assert [_ct_class(t) for t in args] == [_c_class(c) for c in params], name
     assert len(protos["plnerf_coarse_epilogue_const"][1]) == 25 and len(protos["plnerf_fine_epilogue_const"][1]) == 26
-    assert L.ABI_VERSION == 601 and L.lib().plnerf_version() == 601
     # the main header and its restatement are what they were: the new entries live in the companion header only
-    main = open(os.path.join(ROOT, "include", "plnerf_hip.h")).read()
-    assert "_epilogue_const" not in main and "_epilogue_const" not in open(os.path.join(ROOT, "tests", "abi_check.c")).read()
+    main = open(os.path.join(abi.INCLUDE, "plnerf_hip.h")).read()
+    assert "_epilogue_const" not in main and "_epilogue_const" not in open(os.path.join(abi.ROOT, "tests", "abi_check.c")).read()
 
 
 def test_both_symbols_are_exported_and_bound(L):
-    lib = L.lib()
-    raw = ctypes.CDLL(L.LIB_PATH)
+    assert NAMES <= abi.exported_symbols(L.LIB_PATH)
     for name in NAMES:
-        assert getattr(raw, name) is not None
-        fn = getattr(lib, name)
+        fn = getattr(L.lib(), name)
         assert fn.restype is ctypes.c_int and list(fn.argtypes) == L.CONSTEPI_SIGNATURES[name][1]
 
 
@@ -174,14 +133,7 @@ int main(void) {
 
 
 def test_constepi_header_is_plain_c_and_links(L, tmp_path):
-    src = tmp_path / "constepi_abi.c"
-    src.write_text(_C)
-    exe = str(tmp_path / "constepi_abi")
-    libdir = os.path.dirname(L.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                    "-o", exe, "-L", libdir, "-lplnerf_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, timeout=120)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([abi.compile_c(_C, tmp_path, "constepi_abi")], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "constepi abi ok" in out.stdout, (out.returncode, out.stdout, out.stderr)
 
 

@@ -1,19 +1,13 @@
 """The C ABI of the piecewise-constant one-call steps (include/plnerf_hip_conststep.h), without a GPU: the header is plain
-C99 and links against the library, the library exports the six entry points, the ctypes signatures
-(_lib.CONSTSTEP_SIGNATURES) match the header, and every refusal comes before any device work -- the checks
-tests/test_step_abi.py applies to plnerf_hip_step.h."""
+C99 and links against the library, the library exports the six entry points, and every refusal comes before any device
+work.  (_lib.CONSTSTEP_SIGNATURES against the header: tests/test_abi_headers.py.)"""
 import ctypes
-import os
-import re
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-HEADER = os.path.join(ROOT, "include", "plnerf_hip_conststep.h")
+import abi_support as abi
+
 ENTRIES = {"plnerf_fine_epilogue_const_bwd", "plnerf_train_step_const_workspace_bytes", "plnerf_train_step_const",
            "plnerf_depth_train_step_const_workspace_bytes", "plnerf_depth_train_step_const_layout",
            "plnerf_depth_train_step_const"}
@@ -21,55 +15,12 @@ ENTRIES = {"plnerf_fine_epilogue_const_bwd", "plnerf_train_step_const_workspace_
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
-    from plnerf_amd import _lib
-    return _lib
-
-
-def _prototypes():
-    code = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"^(int|size_t)\s+(plnerf_\w+)\s*\(([^;]*?)\)\s*;", code, flags=re.M | re.S):
-        protos[name] = (ret, [re.match(r"^(.*?)\b\w+$", a).group(1).strip() for a in (x.strip() for x in " ".join(args.split()).split(","))])
-    return protos
-
-
-_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "uint32_t": ctypes.c_uint32,
-            "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
-
-
-def test_signatures_match_the_header(L):
-    protos = _prototypes()
-    assert set(protos) == set(L.CONSTSTEP_SIGNATURES) == ENTRIES
-    others = set(L.SIGNATURES) | set(L.CONSTEPI_SIGNATURES) | set(L.STEP_SIGNATURES) | set(L.DEPTHSTEP_SIGNATURES)
-    assert not set(protos) & others
-    structs = dict(L.STEP_STRUCTS)
-    structs.update(L.DEPTHSTEP_STRUCTS)
-    for name, (ret, params) in protos.items():
-        res, args = L.CONSTSTEP_SIGNATURES[name]
-        assert res is _SCALARS[ret], name
-        assert len(args) == len(params), name
-        for a, p in zip(args, params):
-            t = p.replace("const ", "").strip()
-            if t.endswith("*") and t.rstrip("*").strip() in structs:
-                assert issubclass(a, ctypes._Pointer) and a._type_ is structs[t.rstrip("*").strip()], (name, p)
-            elif t.endswith("*") or t == "plnerf_stream_t":
-                assert a is ctypes.c_void_p, (name, p)
-            else:
-                assert a is _SCALARS[t], (name, p)
-    assert L.ABI_VERSION == 601 and L.lib().plnerf_version() == 601
+    return abi.built_lib()
 
 
 def test_library_exports_the_const_entries(L):
     """Fails on a library built without csrc/epilogue_bwd.hip or the const entries of the step sources."""
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True, timeout=120).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert ENTRIES <= exported
-    handle = ctypes.CDLL(L.LIB_PATH)
-    for name in L.CONSTSTEP_SIGNATURES:
-        assert getattr(handle, name) is not None
+    assert set(L.CONSTSTEP_SIGNATURES) == ENTRIES <= abi.exported_symbols(L.LIB_PATH)
 
 
 _C = r"""
@@ -242,15 +193,7 @@ int main(void) {
 
 @pytest.fixture(scope="module")
 def c_host(L, tmp_path_factory):
-    d = tmp_path_factory.mktemp("conststep_abi")
-    src = d / "conststep_abi.c"
-    src.write_text(_C)
-    exe = str(d / "conststep_abi")
-    libdir = os.path.dirname(L.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                    "-o", exe, "-L", libdir, "-lplnerf_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, timeout=120)
-    return exe
+    return abi.compile_c(_C, tmp_path_factory.mktemp("conststep_abi"), "conststep_abi")
 
 
 def test_header_is_plain_c_and_the_checks_come_first(c_host):

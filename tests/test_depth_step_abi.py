@@ -1,19 +1,17 @@
 """The C ABI of the depth-supervised one-call step (include/plnerf_hip_depthstep.h), without a GPU: the header is plain C99
-and links against the library, the library exports the four entry points, the ctypes mirror (_lib.DEPTHSTEP_SIGNATURES and
-the four Structures) matches the header field by field and size by size, and plnerf_depth_train_step's argument checks run
-before any device work -- the checks tests/test_step_abi.py applies to plnerf_hip_step.h."""
+and links against the library, the library exports the four entry points, the four ctypes Structures have the compiler's
+sizes, and plnerf_depth_train_step's argument checks run before any device work.  (_lib.DEPTHSTEP_SIGNATURES and the
+Structures against the header, field by field: tests/test_abi_headers.py.)"""
 import ctypes
 import os
 import re
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-HEADER = os.path.join(ROOT, "include", "plnerf_hip_depthstep.h")
+import abi_support as abi
+
+HEADER = os.path.join(abi.INCLUDE, "plnerf_hip_depthstep.h")
 STRUCTS = ("plnerf_depth_step_config", "plnerf_depth_step_io", "plnerf_depth_step_args", "plnerf_depth_step_views")
 ENTRIES = {"plnerf_depth_train_step_workspace_bytes", "plnerf_depth_train_step_layout", "plnerf_depth_train_step",
            "plnerf_depth_ss_adam"}
@@ -22,102 +20,26 @@ EINVAL, ERANGE, ENOSYS = -1, -3, -4      # PLNERF_E* of include/plnerf_hip.h
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
-    from plnerf_amd import _lib
-    return _lib
-
-
-def _code():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _prototypes():
-    protos = {}
-    for ret, name, args in re.findall(r"^(int|size_t)\s+(plnerf_\w+)\s*\(([^;]*?)\)\s*;", _code(), flags=re.M | re.S):
-        protos[name] = (ret, [re.match(r"^(.*?)\b\w+$", a).group(1).strip() for a in (x.strip() for x in " ".join(args.split()).split(","))])
-    return protos
-
-
-def _structs():
-    """name -> [(field type, field name)], in declaration order."""
-    out = {}
-    for body, name in re.findall(r"typedef struct \w+ \{(.*?)\}\s*(\w+);", _code(), flags=re.S):
-        fields = []
-        for decl in (d.strip() for d in body.split(";")):
-            if decl:
-                m = re.match(r"^(.*?)\b(\w+)$", " ".join(decl.split()))
-                fields.append((m.group(1).strip(), m.group(2)))
-        out[name] = fields
-    return out
-
-
-_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "uint32_t": ctypes.c_uint32,
-            "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
-
-
-def _expected_ctype(L, ctype):
-    ctype = ctype.replace("const ", "").strip()
-    if ctype == "plnerf_step_net":
-        return L.StepNet
-    if ctype.endswith("*") or ctype == "plnerf_stream_t":
-        return ctypes.c_void_p
-    return _SCALARS[ctype]
+    return abi.built_lib()
 
 
 def test_error_codes_are_the_headers():
-    main = open(os.path.join(ROOT, "include", "plnerf_hip.h")).read()
+    main = open(os.path.join(abi.INCLUDE, "plnerf_hip.h")).read()
     for name, want in (("PLNERF_EINVAL", EINVAL), ("PLNERF_ERANGE", ERANGE), ("PLNERF_ENOSYS", ENOSYS)):
         assert int(re.search(r"#define\s+" + name + r"\s+\(?(-?\d+)\)?", main).group(1)) == want
 
 
-def test_structures_match_the_header_field_for_field(L):
-    structs = _structs()
+def test_struct_names_and_view_fields_are_the_headers(L):
+    structs = abi.structs(HEADER)
     assert set(structs) == set(STRUCTS) == set(L.DEPTHSTEP_STRUCTS)
-    for name, fields in structs.items():
-        mirror = L.DEPTHSTEP_STRUCTS[name]._fields_
-        assert [f[0] for f in mirror] == [f[1] for f in fields], name
-        for (fname, ftype), (ctype, _) in zip(mirror, fields):
-            assert ftype is _expected_ctype(L, ctype), (name, fname, ftype)
     # the layout query reports at least what a caller inspects after a step
     assert {"rgb", "rgb0", "depth", "depth0", "acc", "acc0", "disp", "disp0", "z_std", "pred_hyp", "z_vals", "z_vals0", "pixels",
             "target_h", "mask"} <= {f[1] for f in structs["plnerf_depth_step_views"]}
 
 
-def test_signatures_match_the_header(L):
-    protos = _prototypes()
-    assert set(protos) == set(L.DEPTHSTEP_SIGNATURES) == ENTRIES
-    assert not set(protos) & (set(L.SIGNATURES) | set(L.STEP_SIGNATURES) | set(L.DEPTHFEED_SIGNATURES))
-
-    def cls(t):
-        t = t.replace("const ", "").strip()
-        if t.endswith("*") or t == "plnerf_stream_t":
-            return ("ptr", t.rstrip("*").strip() if t.rstrip("*").strip() in STRUCTS else None)
-        return (_SCALARS[t], None)
-    for name, (ret, params) in protos.items():
-        res, args = L.DEPTHSTEP_SIGNATURES[name]
-        assert res is _SCALARS[ret], name
-        assert len(args) == len(params), name
-        for a, p in zip(args, params):
-            kind, struct = cls(p)
-            if kind == "ptr" and struct:
-                assert issubclass(a, ctypes._Pointer) and a._type_ is L.DEPTHSTEP_STRUCTS[struct], (name, p)
-            elif kind == "ptr":
-                assert a is ctypes.c_void_p, (name, p)
-            else:
-                assert a is kind, (name, p)
-    assert L.ABI_VERSION == 601 and L.lib().plnerf_version() == 601
-
-
 def test_library_exports_the_depth_step_entries(L):
     """Fails on a library built without csrc/depth_train_step.hip."""
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True, timeout=120).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert ENTRIES <= exported
-    handle = ctypes.CDLL(L.LIB_PATH)
-    for name in ENTRIES:
-        assert getattr(handle, name) is not None
+    assert set(L.DEPTHSTEP_SIGNATURES) == ENTRIES <= abi.exported_symbols(L.LIB_PATH)
 
 
 _C = r"""
@@ -227,15 +149,7 @@ int main(int argc, char** argv) {
 
 @pytest.fixture(scope="module")
 def c_host(L, tmp_path_factory):
-    d = tmp_path_factory.mktemp("depth_step_abi")
-    src = d / "depth_step_abi.c"
-    src.write_text(_C)
-    exe = str(d / "depth_step_abi")
-    libdir = os.path.dirname(L.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                    "-o", exe, "-L", libdir, "-lplnerf_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, timeout=120)
-    return exe
+    return abi.compile_c(_C, tmp_path_factory.mktemp("depth_step_abi"), "depth_step_abi")
 
 
 def test_depth_step_header_is_plain_c_and_the_checks_come_first(c_host):

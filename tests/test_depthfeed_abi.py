@@ -1,68 +1,32 @@
 """The depth-supervised loop's data feed without a GPU: the C ABI of include/plnerf_hip_depthfeed.h (plain C99, linked
-against the library, argument validation before any device work, ctypes signatures parsed from the header -- the checks
-test_batching_abi.py applies to its header), the learning-rate schedule and the scale / shift stepping rule of
+against the library, argument validation before any device work; the signatures themselves are compared in
+tests/test_abi_headers.py), the learning-rate schedule and the scale / shift stepping rule of
 run_nerf_sample_based_depth.py:1104-1161, and the depth checkpoint's wire format."""
-import ctypes
 import os
 import re
 import subprocess
-import sys
 from argparse import Namespace
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-HEADER = os.path.join(ROOT, "include", "plnerf_hip_depthfeed.h")
+import abi_support as abi
+
+HEADER = os.path.join(abi.INCLUDE, "plnerf_hip_depthfeed.h")
 
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
-    from plnerf_amd import _lib
-    return _lib
+    return abi.built_lib()
 
 
-def _prototypes(path):
-    code = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"^(int|size_t|const char\*)\s+(plnerf_\w+)\s*\(([^;]*?)\)\s*;", code, flags=re.M | re.S):
-        params = [re.match(r"^(.*?)\b\w+$", a).group(1).strip()
-                  for a in (x.strip() for x in " ".join(args.split()).split(",")) if a != "void"]
-        protos[name] = (ret, params)
-    return protos
-
-
-def _c_class(t):
-    t = t.replace("const ", "").strip()
-    if t.endswith("*") or t == "plnerf_stream_t":
-        return "ptr"
-    return {"int": "i32", "float": "f32", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64", "size_t": "u64",
-            "double": "f64"}[t]
-
-
-def _ct_class(t):
-    if t is ctypes.c_char_p or t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
-        return "ptr"
-    return {ctypes.c_int: "i32", ctypes.c_float: "f32", ctypes.c_uint64: "u64", ctypes.c_uint32: "u32",
-            ctypes.c_int64: "i64", ctypes.c_double: "f64"}[t]
-
-
-def test_ctypes_signatures_match_the_depthfeed_header(L):
-    protos = _prototypes(HEADER)
-    assert set(protos) == set(L.DEPTHFEED_SIGNATURES) == {"plnerf_select_depth_rays", "plnerf_depth_scale_shift_grad"}
-    assert not set(protos) & (set(L.SIGNATURES) | set(L.BATCHING_SIGNATURES) | set(L.EVAL_SIGNATURES))
-    for name, (ret, params) in protos.items():
-        res, args = L.DEPTHFEED_SIGNATURES[name]
-        assert _ct_class(res) == _c_class(ret)
-        assert [_ct_class(t) for t in args] == [_c_class(c) for c in params], name
+def test_depthfeed_names_and_constants_match_the_header(L):
+    """The header's entry points are this table's, and the workspace size the binding restates are the header's.
+    (Argument by argument: tests/test_abi_headers.py.)"""
+    assert set(abi.prototypes(HEADER)) == set(L.DEPTHFEED_SIGNATURES) == {"plnerf_select_depth_rays",
+                                                                          "plnerf_depth_scale_shift_grad"}
     ws = int(re.search(r"#define\s+PLNERF_DEPTH_SS_WORKSPACE_BYTES\s+(\d+)", open(HEADER).read()).group(1))
     assert L.DEPTH_SS_WORKSPACE_BYTES == ws
-    assert L.ABI_VERSION == 601 and L.lib().plnerf_version() == 601
 
 
 _C = r"""
@@ -104,14 +68,7 @@ int main(void) {
 
 
 def test_depthfeed_header_is_plain_c_and_links(L, tmp_path):
-    src = tmp_path / "depthfeed_abi.c"
-    src.write_text(_C)
-    exe = str(tmp_path / "depthfeed_abi")
-    libdir = os.path.dirname(L.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                    "-o", exe, "-L", libdir, "-lplnerf_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, timeout=120)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([abi.compile_c(_C, tmp_path, "depthfeed_abi")], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, (out.returncode, out.stdout, out.stderr)
     assert "depthfeed abi ok" in out.stdout
 

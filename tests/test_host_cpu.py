@@ -9,33 +9,27 @@ import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_support as abi
+
+ROOT = abi.ROOT
+MAIN_HEADER = os.path.join(abi.INCLUDE, "plnerf_hip.h")
 
 
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
+    abi.built_lib()
     import plnerf_amd
     return plnerf_amd
 
 
 def test_library_exports_every_declared_symbol(built):
-    import ctypes
+    """The product library behind include/plnerf_hip.h: its entry points, its version, no tools-only build switches.  (Every
+    header's names against its table and the exports: tests/test_abi_headers.py.)"""
     from plnerf_amd import _lib
-    header = open(os.path.join(ROOT, "include", "plnerf_hip.h")).read()
-    declared = set(re.findall(r"\b(plnerf_[a-z0-9_]+)\s*\(", header))
-    declared.discard("plnerf_stream_t")
-    assert declared, "no declarations parsed"
-    handle = ctypes.CDLL(_lib.LIB_PATH)
-    for name in sorted(declared):
-        assert hasattr(handle, name), f"{name} declared in plnerf_hip.h but not exported"
-    assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
-    declared = int(re.search(r"#define\s+PLNERF_VERSION\s+(\d+)", open(os.path.join(ROOT, "include", "plnerf_hip.h")).read()).group(1))
+    assert set(abi.prototypes(MAIN_HEADER)) == set(_lib.SIGNATURES) <= abi.exported_symbols(_lib.LIB_PATH)
+    declared = int(re.search(r"#define\s+PLNERF_VERSION\s+(\d+)", open(MAIN_HEADER).read()).group(1))
     assert built.library_version() == declared >= 230
-    from plnerf_amd import _lib as _L
-    assert _L.lib().plnerf_build_flags() == 0      # no ablation / trace switches in the product library
+    assert _lib.lib().plnerf_build_flags() == 0      # no ablation / trace switches in the product library
     assert _lib.lib().plnerf_error_string(-3).decode().startswith("size outside")
 
 
@@ -43,70 +37,23 @@ def test_header_is_plain_c_and_links(built, tmp_path):
     """include/plnerf_hip.h compiled as C99 by gcc, every entry point referenced with its declared prototype, linked
     against the built library, and the GPU-free calls executed (tests/abi_check.c): the boundary a cgo / JNI / ctypes
     binding would bind."""
-    import re
     from plnerf_amd import _lib
-    header = open(os.path.join(ROOT, "include", "plnerf_hip.h")).read()
-    declared = set(re.findall(r"^(?:int|size_t|const char\*)\s+(plnerf_\w+)\s*\(", header, flags=re.M))
+    declared = set(abi.prototypes(MAIN_HEADER))
     listed = set(re.findall(r"\)\s*=\s*(plnerf_\w+);", open(os.path.join(ROOT, "tests", "abi_check.c")).read()))
     assert declared == listed == set(_lib.SIGNATURES), (declared ^ listed, declared ^ set(_lib.SIGNATURES))
-    exe = str(tmp_path / "abi_check")
-    libdir = os.path.dirname(_lib.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "abi_check.c"), "-o", exe, "-L", libdir, "-lplnerf_hip",
-                    "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    exe = abi.compile_c(os.path.join(ROOT, "tests", "abi_check.c"), tmp_path, "abi_check")
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, (out.returncode, out.stdout, out.stderr)
     assert f"{len(declared)} entry points" in out.stdout
 
 
-def _header_prototypes():
-    """{name: (return type, [parameter types])} parsed from include/plnerf_hip.h (comments stripped)."""
-    import re
-    header = open(os.path.join(ROOT, "include", "plnerf_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"^(int|size_t|const char\*)\s+(plnerf_\w+)\s*\(([^;]*?)\)\s*;", code, flags=re.M | re.S):
-        params = []
-        for a in (x.strip() for x in " ".join(args.split()).split(",")):
-            if a == "void":
-                continue
-            params.append(re.match(r"^(.*?)\b\w+$", a).group(1).strip())
-        protos[name] = (ret, params)
-    return protos
-
-
-def test_ctypes_signatures_match_the_header(built):
-    """_lib.SIGNATURES restates the header's argument lists by hand; a swapped c_int / c_float in a 30-argument call would
-    be silent undefined behaviour.  Parse every prototype of include/plnerf_hip.h into its ABI class per argument
-    (pointer, 32-bit int, 32-bit unsigned, 64-bit int, 64-bit unsigned / size_t, float) and compare with the ctypes
-    declaration's, argument by argument, return type included."""
+def test_host_arrays_are_typed_pointers(built):
+    """_lib.SIGNATURES against the header, argument by argument: tests/test_abi_headers.py.  Here what only this header has:
+    host-side pointer arguments are declared as typed ctypes pointers (not void*), the binding passes arrays there."""
     import ctypes
     from plnerf_amd import _lib
-
-    def c_class(t):
-        t = t.replace("const ", "").strip()
-        if t.endswith("*") or t == "plnerf_stream_t":
-            return "ptr"
-        return {"int": "i32", "float": "f32", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64", "size_t": "u64",
-                "unsigned": "u32", "double": "f64"}[t]      # (size_t and uint64_t are one ctypes object on LP64)
-
-    def ct_class(t):
-        if t is ctypes.c_char_p or t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_float: "f32", ctypes.c_uint64: "u64", ctypes.c_uint32: "u32",
-                ctypes.c_int64: "i64", ctypes.c_size_t: "u64", ctypes.c_double: "f64"}[t]
-    protos = _header_prototypes()
-    assert set(protos) == set(_lib.SIGNATURES)
-    for name, (ret, params) in protos.items():
-        res, args = _lib.SIGNATURES[name]
-        want_ret = "ptr" if ret.endswith("*") else c_class(ret)
-        assert ct_class(res) == want_ret, (name, "return", ret, res)
-        assert len(args) == len(params), (name, len(args), len(params))
-        for k, (c, t) in enumerate(zip(params, args)):
-            assert ct_class(t) == c_class(c), (name, k, c, t)
-    # host-side pointer arguments are declared as typed ctypes pointers (not void*): the binding passes arrays there
-    assert _lib.SIGNATURES["plnerf_select_rays"][1][6] is not ctypes.c_void_p
-    assert _lib.SIGNATURES["plnerf_embed_rows"][1][9] is not ctypes.c_void_p
+    assert _lib.SIGNATURES["plnerf_select_rays"][1][6] is ctypes.POINTER(ctypes.c_float)
+    assert _lib.SIGNATURES["plnerf_embed_rows"][1][9] is ctypes.POINTER(ctypes.c_float)
 
 
 def test_pe_sincos_reduction_on_host(tmp_path):

@@ -1,70 +1,31 @@
 """Importance-sampling error without a GPU: the C ABI of include/plnerf_hip_sampleerr.h (plain C99, links against the
-library, argument validation before any device work, ctypes binding _lib.SAMPLEERR_SIGNATURES argument by argument,
-the workspace size), and the fp64 restatement the GPU tests compare the kernel with, pinned to closed forms and to the
-reference's fp32 expression."""
-import ctypes
+library, argument validation before any device work, the constants _lib restates, the workspace size; the signatures
+themselves are compared in tests/test_abi_headers.py), and the fp64 restatement the GPU tests compare the kernel with,
+pinned to closed forms and to the reference's fp32 expression."""
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-import sampleerr_fp64 as ref      # noqa: E402
+import abi_support as abi
+import sampleerr_fp64 as ref
 
-HEADER = os.path.join(ROOT, "include", "plnerf_hip_sampleerr.h")
+HEADER = os.path.join(abi.INCLUDE, "plnerf_hip_sampleerr.h")
 
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
-    from plnerf_amd import _lib
-    return _lib
+    return abi.built_lib()
 
 
-def _prototypes(path):
-    code = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"^(int|size_t|const char\*)\s+(plnerf_\w+)\s*\(([^;]*?)\)\s*;", code, flags=re.M | re.S):
-        params = [re.match(r"^(.*?)\b\w+$", a).group(1).strip()
-                  for a in (x.strip() for x in " ".join(args.split()).split(",")) if a != "void"]
-        protos[name] = (ret, params)
-    return protos
-
-
-def _c_class(t):
-    t = t.replace("const ", "").strip()
-    if t.endswith("*") or t == "plnerf_stream_t":
-        return "ptr"
-    return {"int": "i32", "float": "f32", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64", "size_t": "u64",
-            "double": "f64"}[t]
-
-
-def _ct_class(t):
-    if t is ctypes.c_char_p or t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
-        return "ptr"
-    return {ctypes.c_int: "i32", ctypes.c_float: "f32", ctypes.c_uint64: "u64", ctypes.c_uint32: "u32",
-            ctypes.c_int64: "i64", ctypes.c_double: "f64"}[t]
-
-
-def test_ctypes_signatures_match_the_sampleerr_header(L):
-    protos = _prototypes(HEADER)
-    assert set(protos) == set(L.SAMPLEERR_SIGNATURES) == {"plnerf_sample_error", "plnerf_sample_error_workspace_bytes"}
-    assert not set(protos) & (set(L.SIGNATURES) | set(L.BATCHING_SIGNATURES) | set(L.EVAL_SIGNATURES) |
-                              set(L.DEPTHFEED_SIGNATURES))
-    for name, (ret, params) in protos.items():
-        res, args = L.SAMPLEERR_SIGNATURES[name]
-        assert _ct_class(res) == _c_class(ret)
-        assert [_ct_class(t) for t in args] == [_c_class(c) for c in params], name
-    assert L.ABI_VERSION == 601 and L.lib().plnerf_version() == 601
+def test_sampleerr_names_and_constants_match_the_header(L):
+    """The header's entry points are this table's, and the row layout and limits the binding restates are the header's.
+    (Argument by argument: tests/test_abi_headers.py.)"""
+    assert set(abi.prototypes(HEADER)) == set(L.SAMPLEERR_SIGNATURES) == {"plnerf_sample_error",
+                                                                          "plnerf_sample_error_workspace_bytes"}
     code = open(HEADER).read()
     consts = {k: int(v) for k, v in re.findall(r"#define\s+PLNERF_SAMPLEERR_(\w+)\s+(\d+)\b", code)}
     assert consts == {"ROW": L.SAMPLEERR_ROW, "SUM": L.SAMPLEERR_SUM, "COUNT": L.SAMPLEERR_COUNT,
@@ -108,14 +69,7 @@ int main(void) {
 
 
 def test_sampleerr_header_is_plain_c_and_links(L, tmp_path):
-    src = tmp_path / "sampleerr_abi.c"
-    src.write_text(_C)
-    exe = str(tmp_path / "sampleerr_abi")
-    libdir = os.path.dirname(L.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                    "-o", exe, "-L", libdir, "-lplnerf_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, timeout=120)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([abi.compile_c(_C, tmp_path, "sampleerr_abi")], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, (out.returncode, out.stdout, out.stderr)
     sizes = [int(x) for x in out.stdout.split("sampleerr abi ok")[1].split()]
     assert sizes == [L.sample_error_workspace_bytes(R) for R in (0, 1, 65, 640000)] == [0, 16, 32, 160000]

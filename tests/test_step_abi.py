@@ -1,121 +1,27 @@
 """The C ABI of the one-call training step (include/plnerf_hip_step.h), without a GPU: the header is plain C99 and links
-against the library, the library exports the two entry points, the ctypes mirror (_lib.STEP_SIGNATURES and the four
-Structures) matches the header field by field and size by size, and plnerf_train_step's argument checks run before any
-device work -- the checks tests/test_batching_abi.py applies to plnerf_hip_batching.h."""
+against the library, the library exports the two entry points, the four ctypes Structures have the compiler's sizes, and
+plnerf_train_step's argument checks run before any device work.  (_lib.STEP_SIGNATURES and the Structures against the
+header, field by field: tests/test_abi_headers.py.)"""
 import ctypes
-import os
-import re
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-HEADER = os.path.join(ROOT, "include", "plnerf_hip_step.h")
+import abi_support as abi
+
 STRUCTS = ("plnerf_step_config", "plnerf_step_net", "plnerf_step_io", "plnerf_step_args")
 
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
-    from plnerf_amd import _lib
-    return _lib
-
-
-def _code():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-def _prototypes():
-    protos = {}
-    for ret, name, args in re.findall(r"^(int|size_t)\s+(plnerf_\w+)\s*\(([^;]*?)\)\s*;", _code(), flags=re.M | re.S):
-        protos[name] = (ret, [re.match(r"^(.*?)\b\w+$", a).group(1).strip() for a in (x.strip() for x in " ".join(args.split()).split(","))])
-    return protos
-
-
-def _structs():
-    """name -> [(field type, field name, array length or None)], in declaration order."""
-    out = {}
-    for body, name in re.findall(r"typedef struct \w+ \{(.*?)\}\s*(\w+);", _code(), flags=re.S):
-        fields = []
-        for decl in (d.strip() for d in body.split(";")):
-            if not decl:
-                continue
-            m = re.match(r"^(.*?)\b(\w+)(?:\[(\w+)\])?$", " ".join(decl.split()))
-            fields.append((m.group(1).strip(), m.group(2), m.group(3)))
-        out[name] = fields
-    return out
-
-
-_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "uint32_t": ctypes.c_uint32,
-            "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
-
-
-def _expected_ctype(L, ctype, length):
-    ctype = ctype.replace("const ", "").strip()
-    if ctype in L.STEP_STRUCTS:
-        base = L.STEP_STRUCTS[ctype]
-    elif ctype.endswith("*") or ctype == "plnerf_stream_t":
-        base = ctypes.c_void_p
-    else:
-        base = _SCALARS[ctype]
-    if length is None:
-        return base
-    n = {"PLNERF_N_PARAM_TENSORS": L.N_PARAM_TENSORS}.get(length) or int(length)
-    return base * n
-
-
-def test_structures_match_the_header_field_for_field(L):
-    structs = _structs()
-    assert set(structs) == set(STRUCTS) == set(L.STEP_STRUCTS)
-    for name, fields in structs.items():
-        mirror = L.STEP_STRUCTS[name]._fields_
-        assert [f[0] for f in mirror] == [f[1] for f in fields], name
-        for (fname, ftype), (ctype, _, length) in zip(mirror, fields):
-            want = _expected_ctype(L, ctype, length)
-            if length is None:
-                assert ftype is want, (name, fname, ftype, want)
-            else:      # (ctypes array types are cached per (element, length))
-                assert ftype._type_ is want._type_ and ftype._length_ == want._length_, (name, fname)
-
-
-def test_signatures_match_the_header(L):
-    protos = _prototypes()
-    assert set(protos) == set(L.STEP_SIGNATURES) == {"plnerf_train_step", "plnerf_train_step_workspace_bytes"}
-    assert not set(protos) & (set(L.SIGNATURES) | set(L.BATCHING_SIGNATURES))
-
-    def cls(t):
-        t = t.replace("const ", "").strip()
-        if t.endswith("*") or t == "plnerf_stream_t":
-            return ("ptr", t.rstrip("*").strip() if t.rstrip("*").strip() in STRUCTS else None)
-        return (_SCALARS[t], None)
-    for name, (ret, params) in protos.items():
-        res, args = L.STEP_SIGNATURES[name]
-        assert res is _SCALARS[ret], name
-        assert len(args) == len(params), name
-        for a, p in zip(args, params):
-            kind, struct = cls(p)
-            if kind == "ptr" and struct:
-                assert issubclass(a, ctypes._Pointer) and a._type_ is L.STEP_STRUCTS[struct], (name, p)
-            elif kind == "ptr":
-                assert a is ctypes.c_void_p, (name, p)
-            else:
-                assert a is kind, (name, p)
-    assert L.ABI_VERSION == 601 and L.lib().plnerf_version() == 601
+    return abi.built_lib()
 
 
 def test_library_exports_the_step_entries(L):
     """Fails on a library built without csrc/train_step.hip."""
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True, timeout=120).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert {"plnerf_train_step", "plnerf_train_step_workspace_bytes"} <= exported
-    handle = ctypes.CDLL(L.LIB_PATH)
-    for name in L.STEP_SIGNATURES:
-        assert getattr(handle, name) is not None
+    entries = {"plnerf_train_step", "plnerf_train_step_workspace_bytes"}
+    assert set(L.STEP_SIGNATURES) == entries <= abi.exported_symbols(L.LIB_PATH)
+    assert set(L.STEP_STRUCTS) == set(STRUCTS)
 
 
 _C = r"""
@@ -205,15 +111,7 @@ int main(int argc, char** argv) {
 
 @pytest.fixture(scope="module")
 def c_host(L, tmp_path_factory):
-    d = tmp_path_factory.mktemp("step_abi")
-    src = d / "step_abi.c"
-    src.write_text(_C)
-    exe = str(d / "step_abi")
-    libdir = os.path.dirname(L.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src),
-                    "-o", exe, "-L", libdir, "-lplnerf_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"],
-                   check=True, timeout=120)
-    return exe
+    return abi.compile_c(_C, tmp_path_factory.mktemp("step_abi"), "step_abi")
 
 
 def test_step_header_is_plain_c_and_the_checks_come_first(c_host):
