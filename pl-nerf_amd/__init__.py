@@ -14,12 +14,14 @@ from .train import (RayBank, TrainStep, batch_schedule, checkpoint_path, img2mse
 from .raybatch import RayColumns
 from .functional import DrawSource, set_draw_source
 from .evaluate import (MeanTracker, compute_rmse, image_metrics, metric_rows, render_images_with_metrics,
-                       sample_error_rows)
+                       sample_error_rows, write_images_with_metrics, write_images_with_metrics_testdist)
 from . import depth   # depth-supervised variant of the path (depth_supervised_exps/)
 from .depth import DepthTrainStep, DepthViews
 from .render import (batchify, batchify_rays, compute_weights, compute_weights_piecewise_linear, create_nerf,
                      raw2outputs, render, render_path, render_rays, run_network, sample_pdf,
                      sample_pdf_reformulation)
+from .png import read_png, write_png
+from .view import ViewRenderer, render_path_frames
 
 
 
@@ -37,5 +39,6 @@ __all__ = [
     "render_rays", "run_network", "sample_pdf", "sample_pdf_reformulation", "img2mse", "library_path",
     "library_version", "depth", "FlatAdam", "TrainStep", "save_checkpoint", "checkpoint_path", "select_rays", "select_view_rays", "RayBank", "batch_schedule", "RayColumns", "DrawSource",
     "set_draw_source", "MeanTracker", "compute_rmse", "image_metrics", "metric_rows", "render_images_with_metrics",
-    "sample_error_rows", "DepthViews", "DepthTrainStep",
+    "sample_error_rows", "DepthViews", "DepthTrainStep", "ViewRenderer", "render_path_frames", "write_png", "read_png",
+    "write_images_with_metrics", "write_images_with_metrics_testdist",
 ]

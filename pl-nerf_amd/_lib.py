@@ -245,6 +245,39 @@ CONSTSTEP_SIGNATURES = {
                                             ctypes.POINTER(DepthStepArgs), c_f, ctypes.c_size_t, c_s]),
 }
 
+# ... and include/plnerf_hip_view.h (ABI 601): one call = one rendered view (on plnerf_step_config), the rays of a view's
+# consecutive pixels and the 8 / 16-bit export of a frame's planes
+
+
+class ViewNet(ctypes.Structure):
+    """plnerf_view_net."""
+    _fields_ = [("params", ctypes.c_void_p * N_PARAM_TENSORS), ("packed", c_f)]
+
+
+VIEW_PLANES = ("rgb", "disp", "acc", "depth", "rgb0", "disp0", "acc0", "depth0", "z_std")      # fp32 frame planes of plnerf_view_io
+
+
+class ViewIo(ctypes.Structure):
+    """plnerf_view_io."""
+    _fields_ = [("coarse", ViewNet), ("fine", ViewNet), ("t_vals", c_f), ("u_vals", c_f)] + \
+               [(name, c_f) for name in VIEW_PLANES] + [("rgb8", c_f), ("depth16", c_f)]
+
+
+class ViewArgs(ctypes.Structure):
+    """plnerf_view_args."""
+    _fields_ = [("c2w", ctypes.c_float * 12), ("step", ctypes.c_uint32), ("pix0", c_i), ("n_pix", c_i), ("pack_weights", c_i),
+                ("depth16_scale", c_fl)]
+
+
+VIEW_STRUCTS = {"plnerf_view_net": ViewNet, "plnerf_view_io": ViewIo, "plnerf_view_args": ViewArgs}
+VIEW_SIGNATURES = {
+    "plnerf_view_rays": (c_i, [c_i, c_i] + [c_fl] * 4 + [ctypes.POINTER(ctypes.c_float), c_i, c_i, c_fl, c_fl] + [c_f] * 5 + [c_s]),
+    "plnerf_frame_export": (c_i, [c_f, c_f, c_f, c_fl, c_f, c_i, c_s]),
+    "plnerf_render_view_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(StepConfig)]),
+    "plnerf_render_view": (c_i, [ctypes.POINTER(StepConfig), ctypes.POINTER(ViewIo), ctypes.POINTER(ViewArgs), c_f,
+                                 ctypes.c_size_t, c_s]),
+}
+
 # Every header of the C ABI, in binding order: (file under include/, its signatures, its struct mirrors).  A new header is
 # one row here; tests/test_abi_headers.py compares each row with its header and with the library.
 HEADERS = (
@@ -257,6 +290,7 @@ HEADERS = (
     ("plnerf_hip_step.h", STEP_SIGNATURES, STEP_STRUCTS),
     ("plnerf_hip_depthstep.h", DEPTHSTEP_SIGNATURES, DEPTHSTEP_STRUCTS),
     ("plnerf_hip_conststep.h", CONSTSTEP_SIGNATURES, {}),
+    ("plnerf_hip_view.h", VIEW_SIGNATURES, VIEW_STRUCTS),
 )
 
 

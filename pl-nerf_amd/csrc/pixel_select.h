@@ -82,6 +82,14 @@ __device__ __forceinline__ float pixel_ray(const int row, const int col, const f
     return rotate_ray(((float)col - cx) / fx, -((float)row - cy) / fy, c2w, d);
 }
 
+// pixel_ray's convention in the arithmetic torch's DEVICE kernels give rays.get_rays (which render() evaluates on the GPU for a
+// full view whose pose lives there): `x / python_float` is a multiply by the fp32 reciprocal there (inv_fx = 1.0f / fx, computed
+// by the caller), and a reduction over a trailing axis of 3 associates as ThreeTermOrder::device.  One ulp from pixel_ray.
+__device__ __forceinline__ float pixel_ray_device(const int row, const int col, const float inv_fx, const float inv_fy,
+                                                  const float cx, const float cy, const float* c2w, float d[3]) {
+    return rotate_ray<ThreeTermOrder::device>(((float)col - cx) * inv_fx, -((float)row - cy) * inv_fy, c2w, d);
+}
+
 // the depth script's convention (depth_supervised_exps/model/run_nerf_helpers.py:243-257): pixel CENTRES and a
 // flipped row, dirs = (((i + 0.5) - cx) / fx, ((H - (j + 0.5)) - cy) / fy, -1); summed as torch sums on the GPU, where
 // that script builds its rays

@@ -6,14 +6,19 @@ come from one launch of plnerf_eval_metrics (csrc/metrics.hip) on the frame wher
 copies the frame to the host and runs skimage's SSIM on the CPU; here each frame's fp64 row stays on the device until
 the loop ends and is read back once.  LPIPS is a network the caller supplies (`lpips_alex`), as in the reference; this
 package ships no LPIPS weights.
+
+The frames an evaluation keeps (`res`) are written by write_images_with_metrics / write_images_with_metrics_testdist
+(run_plnerf.py:365-415) as 8-bit RGB and 16-bit depth PNGs through png.py.
 """
 import math
+import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import raybatch as RB
+from .png import write_png
 from .nerf import NeRF
 from .render import render
 
@@ -267,3 +272,57 @@ def render_images_with_metrics(count, indices, images, depths, valid_depths, pos
     with_depth = args.dataset == "scannet"
     return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
                         render_kwargs_test, render, lambda img_idx: K, with_depth, lambda img_idx: None, keep_images)
+
+
+def to8b(x):
+    """run_nerf_helpers.py:19: [0, 1] floats -> 8-bit codes, truncating."""
+    return (255 * np.clip(x, 0, 1)).astype(np.uint8)
+
+
+def to16b(x):
+    """run_nerf_helpers.py:20: [0, 1] floats -> 16-bit codes, truncating."""
+    return (65535 * np.clip(x, 0, 1)).astype(np.uint16)
+
+
+def _write_result_dir(result_dir, images, mean_metrics):
+    """run_plnerf.py:372-386: {n}_rgb.png, {n}_gt.png (8-bit RGB), {n}_d.png (16-bit grey) per frame and metrics.txt.
+    (The reference hands OpenCV a BGR copy of each colour frame, which stores it as RGB: the files hold RGB.)"""
+    os.makedirs(result_dir, exist_ok=True)
+    planes = [images[k].permute(0, 2, 3, 1).cpu().numpy() for k in ("rgbs", "depths", "target_rgbs")]
+    for n, (rgb, depth, gt_rgb) in enumerate(zip(*planes)):
+        write_png(os.path.join(result_dir, f"{n}_rgb.png"), to8b(rgb))
+        write_png(os.path.join(result_dir, f"{n}_gt.png"), to8b(gt_rgb))
+        write_png(os.path.join(result_dir, f"{n}_d.png"), to16b(depth))
+    with open(os.path.join(result_dir, "metrics.txt"), "w") as f:
+        mean_metrics.print(f)
+    mean_metrics.print()
+    return result_dir
+
+
+def _optimization_tag(with_test_time_optimization):
+    return "with_optimization_" if with_test_time_optimization else ""
+
+
+def write_images_with_metrics(images, mean_metrics, far, args, with_test_time_optimization=False, test_samples=False):
+    """run_plnerf.py:365-386: write `images` (render_images_with_metrics' res: CPU fp32 frames already clamped, depths
+    already divided by far) under args.ckpt_dir / args.expname.  The directory name is the reference's, as it builds it:
+    the sample counts appear twice with test_samples, and nothing separates "samples" from the mode there.  `far` is
+    accepted and unused, as in the reference.  Returns the directory (extension)."""
+    counts = f"{args.N_samples}_{args.N_importance}"
+    tag = _optimization_tag(with_test_time_optimization)
+    if not test_samples:
+        name = f"test_images_{args.mode}_{counts}{tag}{args.scene_id}"
+    else:
+        name = f"test_images_samples{args.mode}_{counts}{tag}{counts}{args.scene_id}"
+    return _write_result_dir(os.path.join(args.ckpt_dir, args.expname, name), images, mean_metrics)
+
+
+def write_images_with_metrics_testdist(images, mean_metrics, far, args, test_dist, with_test_time_optimization=False,
+                                       test_samples=False):
+    """run_plnerf.py:388-415: the same files under a directory named after the test distance."""
+    tag = _optimization_tag(with_test_time_optimization)
+    if not test_samples:
+        name = f"test_images_dist{test_dist}_{tag}{args.scene_id}"
+    else:
+        name = f"test_images_samples_dist{test_dist}_{tag}{args.N_samples}_{args.N_importance}{args.scene_id}"
+    return _write_result_dir(os.path.join(args.ckpt_dir, args.expname, name), images, mean_metrics)
