@@ -13,6 +13,14 @@
  *
  * Row-major contiguous layouts throughout.  R = rays, S = samples per ray in this
  * pass, N = number of new samples to draw.
+ *
+ * Memory.  A buffer may be exactly as large as stated and packed against its neighbours: no entry writes outside the bytes
+ * it is given, const inputs stay bit-identical, a workspace that needs no initialisation may hold anything, and one that
+ * is "zeroed once" is all zero again after every call ("The memory contract").  Alignment: a pointer is
+ * aligned to its element type (4 bytes for float / int32, 8 for double / int64), a void* workspace to 8 bytes, the opaque
+ * MLP buffers (packed, saved, the backward workspace) to 256 bytes.  The arrays the kernels access as float4 -- raw,
+ * g_raw and raw_out [n,4], and feature_linear.weight / .bias among the 24 parameter tensors -- must be 16-byte aligned:
+ * an entry handed one that is not returns PLNERF_EINVAL before it launches anything.
  */
 #ifndef PLNERF_HIP_H
 #define PLNERF_HIP_H
@@ -88,7 +96,8 @@ const char* plnerf_error_string(int code);
  * Quadrature -- raw2outputs (run_plnerf.py:553-624) with compute_weights_piecewise_linear
  * (:516-550) or compute_weights (:504-513) fused in.  One wavefront per ray.
  *
- *   raw    [R,S,4]  (r,g,b,sigma) pre-activation          z      [R,S] sample depths
+ *   raw    [R,S,4]  (r,g,b,sigma) pre-activation, 16-byte aligned (here and in every entry that takes it)
+ *   z      [R,S] sample depths
  *   near   [R], far [R]                                    rays_d [R,3]
  *   noise  [R,S] or NULL (added to sigma before the relu)
  * outputs (any of weights/tau/T may be NULL):
@@ -107,7 +116,7 @@ int plnerf_quad_fwd(const float* raw, const float* z, const float* near, const f
  * callers that differentiate through the sampler
  * (depth_supervised_exps/run_nerf_sample_based_depth.py:923-934) -- g_tau, g_T [R,S+2]
  * (each may be NULL = zero).  disp_map's gradient is folded into g_depth/g_acc by the
- * caller.  g_raw [R,S,4].
+ * caller.  g_raw [R,S,4], 16-byte aligned.
  * absmax_out (may be NULL; ABI 500): max |g_raw| as a by-product, for the consumer that scales by it (plnerf_mlp_bwd's
  * g_absmax: the half dz planes' launch scale): [ceil(R / PLNERF_QUAD_RAYS_PER_GROUP)] uint32, one per workgroup of the
  * launch = the fp32 bit pattern of the largest |g_raw| among that workgroup's rays (plain stores, every entry written; a
@@ -299,7 +308,8 @@ int plnerf_coarse_samples(const float* rays_o, const float* rays_d, const float*
  * rgb0 may be NULL (single-pass configuration).  coarse_loss (NULL, or the loss3 of an earlier call on the coarse
  * image alone; needs rgb0 == NULL): its [1] is taken as the coarse term -- a caller that runs the coarse network's
  * loss and backward ahead of the fine pass (the two sums of :1296 are independent) still gets the reference's total.
- * workspace: PLNERF_IMAGE_LOSS_WORKSPACE_BYTES, zeroed by the caller ONCE (each launch leaves it zeroed; one per
+ * workspace: PLNERF_IMAGE_LOSS_WORKSPACE_BYTES, 8-byte aligned, zeroed by the caller ONCE (each launch leaves every
+ * byte of it zeroed; one per
  * stream that launches concurrently, and not shared with plnerf_depth_loss, which lays its own out differently).  Deterministic (fp64 partial sums added in workgroup order). */
 #define PLNERF_IMAGE_LOSS_WORKSPACE_BYTES 4096
 int plnerf_image_loss(const float* rgb, const float* rgb0, const float* target, int R, float* loss3,
@@ -321,7 +331,8 @@ int plnerf_image_loss(const float* rgb, const float* rgb0, const float* target, 
  * loss5 [5] = {total, image (fine), image (coarse), space carving (unweighted), psnr of the fine image term};
  * g_rgb, g_rgb0 [R, 3], g_hyp [R, n_points] = d total / d (rgb, rgb0, pred_hyp).  rgb0 and pred_hyp may be NULL
  * (single-pass configuration; warm-up iterations without the depth term).  workspace: PLNERF_DEPTH_LOSS_WORKSPACE_BYTES
- * of device memory, 8-byte aligned, ZEROED ONCE by the caller (the kernel leaves it zeroed; one workspace per stream that
+ * of device memory, 8-byte aligned, ZEROED ONCE by the caller (the kernel leaves every byte of it zeroed; one workspace
+ * per stream that
  * may run this call concurrently).  fp64 partial sums added in a fixed order: deterministic. */
 #define PLNERF_DEPTH_LOSS_WORKSPACE_BYTES 4096
 int plnerf_depth_loss(const float* rgb, const float* rgb0, const float* target, const float* pred_hyp,
@@ -358,7 +369,8 @@ int plnerf_embed_rows(const float* pts, const float* viewdirs, const float* cam,
  * gradient as an extra column of dW = gate(G)^T [X | 1]).  fp32 accumulation, k ascending: deterministic.  M <= 4,194,240.
  * k_splits > 1 (a product with few output tiles and a long k, i.e. a weight gradient): the k range is dealt out over up to
  * k_splits workgroups per tile, partial products in `partials` (k_splits * M * N floats, caller-owned), added in order by a
- * second launch; k_splits <= 1: partials may be NULL. */
+ * second launch; k_splits <= 1: partials may be NULL.  The columns N .. ldc - 1 of C are not touched; partials needs no
+ * initialisation. */
 int plnerf_gemm_f32(const float* a, int64_t a_row_stride, int64_t a_col_stride, const float* b, int64_t b_row_stride,
                     int64_t b_col_stride, const float* bias, const float* gate, int M, int N, int K, int relu, int accumulate,
                     int ones_col, float* c, int64_t ldc, int k_splits, float* partials, plnerf_stream_t stream);
@@ -371,7 +383,9 @@ int plnerf_gemm_f32(const float* a, int64_t a_row_stride, int64_t a_col_stride, 
  * params[24]: DEVICE pointers to the fp32 parameter tensors in state_dict order
  *   pts_linears.{0..7}.{weight,bias}, views_linears.0.{weight,bias},
  *   feature_linear.{weight,bias}, alpha_linear.{weight,bias}, rgb_linear.{weight,bias}
- * (the host array itself lives in host memory and is read during the call).
+ * (the host array itself lives in host memory and is read during the call).  feature_linear.weight and .bias must be
+ * 16-byte aligned (they are copied as float4); the other tensors 4.  optim.FlatAdam's flat buffer in this order keeps
+ * them so: every tensor ahead of them is a multiple of four floats long.
  */
 
 /* Size in bytes of the packed-weight buffer for a precision mode (weight sections + a 16-byte status block). */
@@ -384,7 +398,10 @@ int plnerf_mlp_pack_weights(const float* const* params, int precision, int input
                             int input_ch_views, void* packed, plnerf_stream_t stream);
 
 /* Bytes of forward state saved for the backward pass (activations of every layer) and of
- * backward scratch (per-layer pre-activation gradients, split-K partial sums). */
+ * backward scratch (per-layer pre-activation gradients, split-K partial sums).  Both buffers 256-byte aligned; the
+ * scratch needs no initialisation.  fp32 mode: exactly n_rows rows of 2528 fp32 plane elements, followed by 272 bytes per
+ * row that the 16-bit kernels' ReLU bit masks occupy in their layout and the fp32 kernels neither write nor read.
+ * 16-bit modes: rows padded to a multiple of 256; the rows past n_rows are written by the forward and never read. */
 size_t plnerf_mlp_saved_bytes(int n_rows, int precision);
 size_t plnerf_mlp_bwd_workspace_bytes(int n_rows, int precision);
 /* Layout tag of the saved state the forward of this configuration writes (has_embedded: the call passes `embedded`
@@ -409,7 +426,8 @@ int plnerf_mlp_saved_layout(int precision, int has_embedded, int fwd_kernel);
  * (M <= 4), s = input_scale (1: run_nerf_helpers.py:24-54; pi: the Embedder of
  * depth_supervised_exps/model/run_nerf_helpers.py:100-130, arguments evaluated as fl(fl(x pi) 2^k)) -- or
  * embedded [n_rows, input_ch + input_ch_views] (a caller-supplied encoding; NeRF.forward's
- * own signature).  saved == NULL for inference.  raw_out [n_rows,4].  fwd_kernel: PLNERF_FWD_KERNEL_* (pass the same
+ * own signature).  saved == NULL for inference.  raw_out [n_rows,4], 16-byte aligned.  fwd_kernel: PLNERF_FWD_KERNEL_*
+ * (pass the same
  * value to plnerf_mlp_saved_layout).
  * density_beta: 0 = the four channels leave as the network computes them (run_nerf_helpers.py:124); > 0 = the density
  * channel leaves as softplus_beta(sigma) = log(1 + exp(beta sigma)) / beta (beta sigma > 20: sigma) -- the NeRF of the
@@ -420,7 +438,8 @@ int plnerf_mlp_fwd(const void* packed, int precision, const float* pts, const fl
                    int samples_per_ray, float input_scale, float density_beta, float* raw_out, void* saved,
                    int fwd_kernel, plnerf_stream_t stream);
 
-/* Backward: g_raw [n_rows,4] -> gradients of all 24 parameter tensors, written (not
+/* Backward: g_raw [n_rows,4] (16-byte aligned, as raw_out when it is given) -> gradients of all 24 parameter tensors,
+ * written (not
  * accumulated) to grads[24] (device pointers, same shapes as params).  Needs the `saved`
  * buffer of the matching forward call and a workspace of
  * plnerf_mlp_bwd_workspace_bytes().  Inputs (pts / viewdirs) receive no gradient, as on

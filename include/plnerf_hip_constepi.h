@@ -34,7 +34,8 @@ extern "C" {
  * Bit-identical to the sequence plnerf_quad_fwd (PLNERF_MODE_CONSTANT), z_mid = .5 * (z[1:] + z[:-1]) in torch,
  * plnerf_sample_const on (z_mid, weights[:, 1:-1]), plnerf_merge_sort, plnerf_ray_points on the same inputs -- except
  * z_std, which is the fp64 two-pass value where torch.std works in fp32.  The weights, the bins and the cdf stay on chip.
- *   raw [R,S,4], z [R,S], near, far [R], rays_o, rays_d [R,3], noise [R,S] or NULL.
+ *   raw [R,S,4] (16-byte aligned, as plnerf_hip.h demands of it: else PLNERF_EINVAL), z [R,S], near, far [R],
+ *   rays_o, rays_d [R,3], noise [R,S] or NULL.
  *   u: [R,N] draws (u_row_stride == N), one shared row (0), or NULL = drawn in the kernel from the counter-based
  *      generator of plnerf_hip.h (stream id 1) for global ray ids ray_id0 .. ray_id0 + R - 1.
  *   outputs: rgb_map [R,3], disp_map, acc_map, depth_map [R] (the coarse maps rgb0, ...), weights [R,S] or NULL,

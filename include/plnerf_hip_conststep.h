@@ -39,7 +39,8 @@ extern "C" {
  *     draws u ([R,N] with u_row_stride == N, or one shared row with 0), inds int64 [R,N];
  *   upstream: g_rgb [R,3]; g_depth [R], g_acc [R], g_weights [R,S], g_hyp [R,N] each NULL = zero.  With g_hyp NULL the call
  *     is plnerf_quad_bwd in constant mode and weights, bins, u, inds are not read;
- *   outputs: g_raw [R,S,4]; absmax_out NULL or ceil(R / PLNERF_QUAD_RAYS_PER_GROUP) words, every entry written with plain
+ *   outputs: g_raw [R,S,4] (16-byte aligned, like raw: else PLNERF_EINVAL);
+ *     absmax_out NULL or ceil(R / PLNERF_QUAD_RAYS_PER_GROUP) words, every entry written with plain
  *     stores: plnerf_quad_bwd's contract.
  * Refused before anything touches a device: PLNERF_EINVAL for R < 0, S < 3, N < 1, a stride other than 0 or N, g_hyp given
  * without weights, bins, u or inds, a required pointer NULL (with R > 0); PLNERF_ERANGE for S > PLNERF_MAX_SAMPLES, N > 1024

@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-/* Caller-owned workspace of plnerf_depth_scale_shift_grad (no initialisation needed). */
+/* Caller-owned workspace of plnerf_depth_scale_shift_grad (8-byte aligned, no initialisation needed). */
 #define PLNERF_DEPTH_SS_WORKSPACE_BYTES 4096
 
 /* The training rays of one step of the depth-supervised loop (depth_supervised_exps/run_nerf_sample_based_depth.py:

@@ -39,7 +39,8 @@ extern "C" {
  * (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), moments of 7x7 windows, covariances scaled by
  * 49/48, C1 = 1e-4, C2 = 9e-4; then the mean over the channels.  Moments and sums are fp64.
  * Deterministic: no atomics; each workgroup writes its tile's partial row to `workspace`
- * (PLNERF_EVAL_WORKSPACE_BYTES(n, H, W), no initialisation needed) and a second launch adds the tiles of a frame in a
+ * (PLNERF_EVAL_WORKSPACE_BYTES(n, H, W), 8-byte aligned, no initialisation needed)
+ * and a second launch adds the tiles of a frame in a
  * fixed order, so a row does not depend on n or on the other frames of the call.
  * PLNERF_EINVAL: n < 1, H < 7 or W < 7 (smaller than one window), a NULL required pointer, a partial depth triple.
  * PLNERF_ERANGE: n > 65535 or H*W > 2^28. */

@@ -38,7 +38,8 @@ size_t plnerf_sample_error_workspace_bytes(int R);
  * scored chunk by chunk in stream order with no host read in between.  R = 0 writes zeros (accumulate = 0) or leaves
  * the row untouched (accumulate != 0).
  * Deterministic: no atomics; each workgroup of PLNERF_SAMPLEERR_RAYS_PER_GROUP rays writes its partial row to
- * `workspace` (plnerf_sample_error_workspace_bytes(R), no initialisation needed) and a second launch adds the partials
+ * `workspace` (plnerf_sample_error_workspace_bytes(R), 8-byte aligned, no initialisation needed)
+ * and a second launch adds the partials
  * in a fixed order, so the row is bit-identical from run to run.
  * PLNERF_EINVAL: row NULL, or pred_hyp, depth or workspace NULL with R > 0.
  * PLNERF_ERANGE: R < 0, N < 1 or N > PLNERF_SAMPLEERR_MAX_N. */

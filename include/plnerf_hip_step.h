@@ -69,8 +69,10 @@ typedef struct plnerf_step_config {
 } plnerf_step_config;
 
 /* One network with its optimizer state.  The 24 parameter tensors are slices of param_flat [n_params], in any order
- * (optim.FlatAdam's layout); gradient k is written at the same offset of grad_flat.  grad_flat holds n_params + 4
- * floats: [n_params] receives the network's range status as plnerf_mlp_bwd's status_out leaves it. */
+ * (optim.FlatAdam's layout) that leaves feature_linear.weight and .bias (params[18], [19]) 16-byte aligned, as
+ * plnerf_mlp_pack_weights demands (else PLNERF_EINVAL, before the first launch); gradient k is written at the same offset
+ * of grad_flat.  grad_flat holds n_params + 4 floats: [n_params] receives the network's range status as plnerf_mlp_bwd's
+ * status_out leaves it; the three floats behind it are not touched. */
 typedef struct plnerf_step_net {
     const float* params[PLNERF_N_PARAM_TENSORS];
     float* param_flat;

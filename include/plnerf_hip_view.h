@@ -56,8 +56,9 @@ int plnerf_view_rays(int H, int W, float fx, float fy, float cx, float cy, const
 int plnerf_frame_export(const float* rgb, uint8_t* rgb8, const float* gray, float gray_scale, uint16_t* gray16, int n,
                         plnerf_stream_t stream);
 
-/* One network as the view call reads it: its 24 parameter tensors (plnerf_mlp_pack_weights' order) and its packed buffer
- * (plnerf_mlp_packed_bytes(precision); status word zeroed by the caller once). */
+/* One network as the view call reads it: its 24 parameter tensors (plnerf_mlp_pack_weights' order and alignment:
+ * feature_linear.weight and .bias 16 bytes, else PLNERF_EINVAL) and its packed buffer (plnerf_mlp_packed_bytes(precision),
+ * 256-byte aligned; status word zeroed by the caller once). */
 typedef struct plnerf_view_net {
     const float* params[PLNERF_N_PARAM_TENSORS];
     void* packed;

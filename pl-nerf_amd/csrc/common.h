@@ -15,6 +15,11 @@
 
 namespace plnerf {
 
+// The [n,4] arrays of the ABI (raw, g_raw, raw_out) and feature_linear's weight / bias are accessed as float4: the headers
+// demand 16-byte alignment and every host entry refuses a pointer without it (PLNERF_EINVAL) before its first launch.
+// NULL counts as aligned: whether a pointer may be NULL is each entry's own check.
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 // torch.max / torch.min / torch.clamp semantics: NaN propagates (fmaxf would drop it).

@@ -168,6 +168,7 @@ int depth_train_step(const plnerf_depth_step_config* c, const plnerf_depth_step_
     if (workspace_bytes < p.bytes) return PLNERF_EINVAL;
     const int layout = plnerf_mlp_saved_layout(c->precision, 0, c->fwd_kernel);
     if (layout < 0) return layout;
+    if ((rc = check_params_aligned(io->coarse.params)) || (rc = check_params_aligned(io->fine.params))) return rc;
 
     hipStream_t st = (hipStream_t)stream;
     const int R = a->rays, S = c->n_samples, N = c->n_importance, F = S + N;

@@ -361,6 +361,7 @@ extern "C" int plnerf_coarse_epilogue(const float* raw, const float* z, const fl
     if (!raw || !z || !near || !far || !rays_o || !rays_d || !rgb_map || !disp_map || !acc_map || !depth_map ||
         !z_fine || !pts || !z_std)
         return PLNERF_EINVAL;
+    if (!plnerf::aligned16(raw)) return PLNERF_EINVAL;      // read as float4
     EpiArgs a{};
     a.in = RayIn{raw, z, near, far, rays_d, noise, S};
     a.rays_o = rays_o; a.u = u; a.u_row_stride = u_row_stride;
@@ -391,6 +392,7 @@ extern "C" int plnerf_fine_epilogue(const float* raw, const float* z, const floa
     if (!raw || !z || !near || !far || !rays_d || !rgb_map || !disp_map || !acc_map || !depth_map || !weights || !tau ||
         !T || !samples || !inds || !z_std)
         return PLNERF_EINVAL;
+    if (!plnerf::aligned16(raw)) return PLNERF_EINVAL;      // read as float4
     EpiArgs a{};
     a.in = RayIn{raw, z, near, far, rays_d, noise, S};
     a.u = u; a.u_row_stride = u_row_stride;
@@ -422,6 +424,7 @@ extern "C" int plnerf_coarse_epilogue_const(const float* raw, const float* z, co
     if (!raw || !z || !near || !far || !rays_o || !rays_d || !rgb_map || !disp_map || !acc_map || !depth_map ||
         !z_fine || !pts || !z_std)
         return PLNERF_EINVAL;
+    if (!plnerf::aligned16(raw)) return PLNERF_EINVAL;      // read as float4
     EpiArgs a{};
     a.in = RayIn{raw, z, near, far, rays_d, noise, S};
     a.rays_o = rays_o; a.u = u; a.u_row_stride = u_row_stride;
@@ -448,6 +451,7 @@ extern "C" int plnerf_fine_epilogue_const(const float* raw, const float* z, cons
     if (!raw || !z || !near || !far || !rays_d || !rgb_map || !disp_map || !acc_map || !depth_map || !weights ||
         !samples || !inds || !z_std)
         return PLNERF_EINVAL;
+    if (!plnerf::aligned16(raw)) return PLNERF_EINVAL;      // read as float4
     EpiArgs a{};
     a.in = RayIn{raw, z, near, far, rays_d, noise, S};
     a.u = u; a.u_row_stride = u_row_stride;

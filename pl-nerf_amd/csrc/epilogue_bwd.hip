@@ -63,6 +63,7 @@ extern "C" int plnerf_fine_epilogue_const_bwd(const float* raw, const float* z, 
     if (lds > 160 * 1024) return PLNERF_ERANGE;
     if (R == 0) return PLNERF_OK;
     if (!raw || !z || !near || !far || !rays_d || !g_rgb || !g_raw) return PLNERF_EINVAL;
+    if (!plnerf::aligned16(raw) || !plnerf::aligned16(g_raw)) return PLNERF_EINVAL;      // read / stored as float4
     if (!g_hyp)      // nothing comes through the sampler: the quadrature's backward alone
         return plnerf_quad_bwd(raw, z, near, far, rays_d, noise, R, S, PLNERF_MODE_CONSTANT, PLNERF_COLOR_MIDPOINT, white_bkgd, 0,
                                g_rgb, g_depth, g_acc, g_weights, nullptr, nullptr, g_raw, absmax_out, stream);

@@ -66,6 +66,7 @@ extern "C" int plnerf_mlp_pack_weights(const float* const* params, int precision
     if (!known(precision)) return PLNERF_ENOSYS;
     for (int i = 0; i < PLNERF_N_PARAM_TENSORS; ++i)
         if (!params[i]) return PLNERF_EINVAL;
+    if (!aligned16(params[lay::P_WF]) || !aligned16(params[lay::P_BF])) return PLNERF_EINVAL;      // copied as float4 (mlp_compose.hip)
     if (precision == PLNERF_PREC_FP32) return impl::f32_pack(params, input_ch, input_ch_views, packed, (hipStream_t)stream);
     // 16-bit modes: the composed view layer first (W_c = W_vf W_f, b_c; mlp_layout.h) -- the operand sections are packed from it
     float* cb = compose_block(packed, precision);
@@ -118,7 +119,7 @@ extern "C" int plnerf_mlp_fwd(const void* packed, int precision, const float* pt
                       input_ch_views < 3 || input_ch_views > lay::DIR_CH || !(input_scale > 0.0f) || !(input_scale < 1e6f)))
         return PLNERF_EINVAL;
     if (n_rows == 0) return PLNERF_OK;
-    if (!packed || !raw_out) return PLNERF_EINVAL;
+    if (!packed || !raw_out || !aligned16(raw_out)) return PLNERF_EINVAL;      // (raw_out is stored as float4)
     if (!embedded && (!pts || !viewdirs || samples_per_ray < 1)) return PLNERF_EINVAL;
     if (precision == PLNERF_PREC_FP32)
         return impl::f32_fwd(packed, pts, viewdirs, embedded, input_ch, input_ch_views, n_rows, samples_per_ray,
@@ -157,6 +158,7 @@ extern "C" int plnerf_mlp_bwd_multi(int n_jobs, const void* const* packed, int p
         if (saved_layout[j] == lay::SV_LAYOUT_TILED && !ns_of(precision)) return PLNERF_EINVAL;
         if (!packed[j] || !g_raw[j] || !saved[j] || !workspace[j] || n_rows[j] < 1) return PLNERF_EINVAL;
         if (act && (!raw_out || !raw_out[j])) return PLNERF_EINVAL;
+        if (!aligned16(g_raw[j]) || (act && !aligned16(raw_out[j]))) return PLNERF_EINVAL;      // read as float4
         for (int i = 0; i < PLNERF_N_PARAM_TENSORS; ++i)
             if (!grads[j * PLNERF_N_PARAM_TENSORS + i]) return PLNERF_EINVAL;
     }

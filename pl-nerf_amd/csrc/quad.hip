@@ -95,6 +95,7 @@ int check_common(const float* raw, const float* z, const float* near, const floa
                  const float* rays_d, int R, int S, int mode, int color_mode) {
     if (R < 0 || S < 2) return PLNERF_EINVAL;
     if (R > 0 && (!raw || !z || !near || !far || !rays_d)) return PLNERF_EINVAL;
+    if (!plnerf::aligned16(raw)) return PLNERF_EINVAL;      // read as float4
     if (S > PLNERF_MAX_SAMPLES) return PLNERF_ERANGE;
     if (mode != PLNERF_MODE_LINEAR && mode != PLNERF_MODE_CONSTANT) return PLNERF_EINVAL;
     if (color_mode != PLNERF_COLOR_MIDPOINT && color_mode != PLNERF_COLOR_LEFT) return PLNERF_EINVAL;
@@ -147,7 +148,7 @@ int quad_bwd_launch(const float* raw, const float* z, const float* near, const f
     int rc = check_common(raw, z, near, far, rays_d, R, S, mode, color_mode);
     if (rc) return rc;
     if (R == 0) return PLNERF_OK;
-    if (!g_rgb || !g_raw) return PLNERF_EINVAL;
+    if (!g_rgb || !g_raw || !plnerf::aligned16(g_raw)) return PLNERF_EINVAL;      // (g_raw is stored as float4)
     if ((g_tau || g_T) && mode != PLNERF_MODE_LINEAR) return PLNERF_EINVAL;
     QuadArgs a{};
     a.raw = raw; a.z = z; a.near = near; a.far = far; a.rays_d = rays_d; a.noise = noise;

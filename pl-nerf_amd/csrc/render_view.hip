@@ -86,6 +86,8 @@ extern "C" int plnerf_render_view(const plnerf_step_config* c, const plnerf_view
     if (!io->t_vals || !io->rgb || (!c->perturb && !io->u_vals) || (io->depth16 && !io->depth)) return PLNERF_EINVAL;
     const Plan p = carve(c, workspace);
     if (workspace_bytes < p.bytes) return PLNERF_EINVAL;
+    if ((rc = plnerf_step::check_params_aligned(io->coarse.params)) || (rc = plnerf_step::check_params_aligned(io->fine.params)))
+        return rc;
 
     hipStream_t st = (hipStream_t)stream;
     const int S = c->n_samples, N = c->n_importance, F = S + N, mode = c->mode;

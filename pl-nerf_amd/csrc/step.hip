@@ -309,20 +309,26 @@ __global__ __launch_bounds__(IL_THREADS) void image_loss_kernel(const float* __r
         last = atomicAdd(ticket, 1u) == IL_BLOCKS - 1 ? 1u : 0u;
     }
     __syncthreads();
-    if (!last || tid != 0) return;
-    __threadfence();
-    double a1 = 0.0, a0 = 0.0;
-    for (int w = 0; w < IL_BLOCKS; ++w) {
-        a1 += __builtin_nontemporal_load(partial + 2 * w + 0);
-        a0 += __builtin_nontemporal_load(partial + 2 * w + 1);
+    if (!last) return;
+    if (tid == 0) {
+        __threadfence();
+        double a1 = 0.0, a0 = 0.0;
+        for (int w = 0; w < IL_BLOCKS; ++w) {
+            a1 += __builtin_nontemporal_load(partial + 2 * w + 0);
+            a0 += __builtin_nontemporal_load(partial + 2 * w + 1);
+        }
+        *ticket = 0u;      // left as the next launch expects it
+        const float fine = (float)(a1 / (double)n);
+        const float coarse = coarse_in ? coarse_in[1] : (float)(a0 / (double)n);
+        loss3[0] = fine + coarse;
+        loss3[1] = fine;
+        loss3[2] = coarse;
+        loss3[3] = -10.0f * log10f(fine);      // mse2psnr(img_loss) (run_nerf_helpers.py:18, run_plnerf.py:1290)
     }
-    *ticket = 0u;      // left as the next launch expects it
-    const float fine = (float)(a1 / (double)n);
-    const float coarse = coarse_in ? coarse_in[1] : (float)(a0 / (double)n);
-    loss3[0] = fine + coarse;
-    loss3[1] = fine;
-    loss3[2] = coarse;
-    loss3[3] = -10.0f * log10f(fine);      // mse2psnr(img_loss) (run_nerf_helpers.py:18, run_plnerf.py:1290)
+    // "each launch leaves the workspace zeroed" (plnerf_hip.h) is about every byte, not the ticket alone: once the sums are
+    // read, the last workgroup clears the partials too (tests/test_gpu_containment.py holds the header to its word)
+    __syncthreads();
+    for (int i = tid; i < 2 * IL_BLOCKS; i += IL_THREADS) partial[i] = 0.0;
 }
 
 // ---- depth-supervised loss: DL_BLOCKS workgroups over contiguous slices, fp64 partial sums per workgroup in a fixed
@@ -467,6 +473,10 @@ __global__ __launch_bounds__(DL_THREADS) void depth_loss_kernel(const DepthLossA
         a.loss5[2] = coarse;
         a.loss5[3] = carve;
         a.loss5[4] = -10.0f * log10f(fine);
+    }
+    if (last) {      // (uniform over the workgroup) the workspace is left zeroed, every byte of it: the partials too
+        __syncthreads();
+        for (int i = tid; i < 3 * DL_BLOCKS; i += DL_THREADS) a.partial[i] = 0.0;
     }
 }
 

@@ -45,4 +45,11 @@ static inline int check_net(const plnerf_step_net* n) {
     return PLNERF_OK;
 }
 
+// feature_linear.weight / .bias (params[18], [19]) are copied as float4 by plnerf_mlp_pack_weights, which refuses them
+// unless they are 16-byte aligned: the one-call entries look BEFORE their first launch (a refused call enqueues nothing),
+// as the last of their argument checks, so that every other refusal keeps the code it had
+static inline int check_params_aligned(const float* const* params) {
+    return (plnerf::aligned16(params[18]) && plnerf::aligned16(params[19])) ? PLNERF_OK : PLNERF_EINVAL;
+}
+
 }  // namespace plnerf_step

@@ -104,6 +104,7 @@ int train_step(const plnerf_step_config* c, const plnerf_step_io* io, const plne
     if (workspace_bytes < p.bytes) return PLNERF_EINVAL;
     const int layout = plnerf_mlp_saved_layout(c->precision, 0, c->fwd_kernel);
     if (layout < 0) return layout;
+    if ((rc = check_params_aligned(io->coarse.params)) || (rc = check_params_aligned(io->fine.params))) return rc;
 
     hipStream_t st = (hipStream_t)stream;
     const int prec = c->precision, xyz = c->input_ch, dir = c->input_ch_views;
