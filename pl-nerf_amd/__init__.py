@@ -22,6 +22,8 @@ from .render import (batchify, batchify_rays, compute_weights, compute_weights_p
                      sample_pdf_reformulation)
 from .png import read_png, write_png
 from .view import ViewRenderer, render_path_frames
+from . import depthview   # plnerf_depth_render_view: the depth-supervised variant's frames, one library call each
+from .depthview import DepthViewRenderer, render_video_frames
 
 
 
@@ -40,5 +42,5 @@ __all__ = [
     "library_version", "depth", "FlatAdam", "TrainStep", "save_checkpoint", "checkpoint_path", "select_rays", "select_view_rays", "RayBank", "batch_schedule", "RayColumns", "DrawSource",
     "set_draw_source", "MeanTracker", "compute_rmse", "image_metrics", "metric_rows", "render_images_with_metrics",
     "sample_error_rows", "DepthViews", "DepthTrainStep", "ViewRenderer", "render_path_frames", "write_png", "read_png",
-    "write_images_with_metrics", "write_images_with_metrics_testdist",
+    "write_images_with_metrics", "write_images_with_metrics_testdist", "depthview", "DepthViewRenderer", "render_video_frames",
 ]

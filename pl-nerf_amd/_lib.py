@@ -305,7 +305,64 @@ def _merge(headers):
     return merged
 
 
-ALL_SIGNATURES = _merge(HEADERS)      # every entry point of the library
+ALL_SIGNATURES = _merge(HEADERS)      # every entry point of the registered ABI
+
+# ---- experimental headers (include/experimental/): entry points the library exports and lib() binds, OUTSIDE the registered
+# ABI above -- their signatures and structs may still change without a PLNERF_VERSION step.  Same row shape as HEADERS; the
+# header's own tests hold a row to the checks the registry gives the others.  Promoting a header moves its file up to
+# include/ and its row into HEADERS.
+
+# include/experimental/plnerf_hip_depthview.h: one call = one rendered view of the depth-supervised variant
+
+
+class DepthViewConfig(ctypes.Structure):
+    """plnerf_depth_view_config."""
+    _fields_ = [("max_rays", c_i), ("n_samples", c_i), ("n_importance", c_i), ("mode", c_i), ("color_mode", c_i),
+                ("lindisp", c_i), ("perturb", c_i), ("white_bkgd", c_i), ("raw_noise_std", c_fl), ("zero_tol", c_fl),
+                ("epsilon", c_fl), ("H", c_i), ("W", c_i), ("near", c_fl), ("far", c_fl), ("precision", c_i), ("fwd_kernel", c_i),
+                ("input_ch", c_i), ("input_ch_views", c_i), ("input_scale", c_fl), ("density_beta", c_fl),
+                ("seed", ctypes.c_uint64)]
+
+
+class DepthViewIo(ctypes.Structure):
+    """plnerf_depth_view_io."""
+    _fields_ = [("coarse", ViewNet), ("fine", ViewNet), ("t_vals", c_f), ("u_vals", c_f)] + \
+               [(name, c_f) for name in VIEW_PLANES] + \
+               [("pred_hyp", c_f), ("valid", c_f), ("error_row", c_f), ("rgb8", c_f), ("depth16", c_f), ("depth_mm16", c_f)]
+
+
+class DepthViewArgs(ctypes.Structure):
+    """plnerf_depth_view_args."""
+    _fields_ = [("c2w", ctypes.c_float * 12), ("fx", c_fl), ("fy", c_fl), ("cx", c_fl), ("cy", c_fl), ("step", ctypes.c_uint32),
+                ("pix0", c_i), ("n_pix", c_i), ("pack_weights", c_i), ("depth16_scale", c_fl), ("depth_mm_mult", c_fl)]
+
+
+DEPTHVIEW_STRUCTS = {"plnerf_depth_view_config": DepthViewConfig, "plnerf_depth_view_io": DepthViewIo,
+                     "plnerf_depth_view_args": DepthViewArgs}
+DEPTHVIEW_SIGNATURES = {
+    "plnerf_depth_view_rays": (c_i, [c_i, c_i] + [c_fl] * 4 + [ctypes.POINTER(ctypes.c_float), c_i, c_i, c_fl, c_fl] + [c_f] * 5 +
+                               [c_s]),
+    "plnerf_frame_export_u16": (c_i, [c_f, c_fl, c_f, c_i, c_s]),
+    "plnerf_depth_render_view_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DepthViewConfig)]),
+    "plnerf_depth_render_view": (c_i, [ctypes.POINTER(DepthViewConfig), ctypes.POINTER(DepthViewIo),
+                                       ctypes.POINTER(DepthViewArgs), c_f, ctypes.c_size_t, c_s]),
+}
+
+EXPERIMENTAL_HEADERS = (
+    ("experimental/plnerf_hip_depthview.h", DEPTHVIEW_SIGNATURES, DEPTHVIEW_STRUCTS),
+)
+EXPERIMENTAL_SIGNATURES = _merge(EXPERIMENTAL_HEADERS)
+
+
+def _disjoint(experimental, registered):
+    """An experimental entry that the registered ABI also declares would be bound twice, the later list winning."""
+    for name in experimental:
+        if name in registered:
+            raise ValueError(f"{name} is declared by an experimental header and by the registered ABI: one entry point, "
+                             "one header")
+
+
+_disjoint(EXPERIMENTAL_SIGNATURES, ALL_SIGNATURES)
 
 _lib = None
 
@@ -321,7 +378,7 @@ def lib():
                 "plnerf_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
-        for name, (res, args) in ALL_SIGNATURES.items():
+        for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -438,18 +438,53 @@ render_hyp = render
 
 def render_images_with_metrics(count, indices, images, depths, valid_depths, poses, H, W, intrinsics, lpips_alex, args,
                                render_kwargs_test, embedcam_fn=None, with_test_time_optimization=False, *,
-                               keep_images=True):
+                               keep_images=True, one_call=False):
     """run_nerf_sample_based_depth.py:424-510: evaluate.render_images_with_metrics on this variant's render, with the
     per-view intrinsics[i] = (fx, fy, cx, cy) and the sensor depths[i] [H,W,1] / valid_depths[i] [H,W] of every view.
     With args.input_ch_cam > 0 the camera code is embedcam_fn(i), or zeros when embedcam_fn is None (set in
     render_kwargs_test["embedded_cam"], as there).  with_test_time_optimization (the per-view optimisation of that code)
-    is not provided: it raises."""
+    is not provided: it raises.  one_call: frames come from a depthview.DepthViewRenderer (one library call per frame, blocks
+    of args.chunk) when it serves the configuration AND the kwargs ask for no draws (perturb 0, no density noise: the
+    test-time settings, at which its frames are render()'s bit for bit); any other configuration takes render() as before.
+    The poses and intrinsics are copied to the host once for all views (the call reads host floats), and the renderer's range
+    status words are read once, after the last view."""
     if with_test_time_optimization:
         raise NotImplementedError("with_test_time_optimization: the per-view camera-code optimisation is not provided")
     set_camera_code = _camera_code_setter(args, render_kwargs_test, embedcam_fn, RB.default_device())
-    return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
-                        render_kwargs_test, render, lambda img_idx: intrinsics[img_idx, :], True, set_camera_code,
-                        keep_images)
+    renderer = _view_renderer(render_kwargs_test, H, W, args) if one_call else None
+    if renderer is None:
+        return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
+                            render_kwargs_test, render, lambda img_idx: intrinsics[img_idx, :], True, set_camera_code,
+                            keep_images)
+    host_poses, host_intrinsics = _on_host(poses), _on_host(intrinsics)
+
+    def render_fn(H, W, intrinsic, chunk=None, c2w=None, **kwargs):
+        return renderer.render(c2w, intrinsic, check=False)
+    out = _score_views(count, indices, images, depths, valid_depths, host_poses, H, W, lpips_alex, args.chunk,
+                       render_kwargs_test, render_fn, lambda img_idx: host_intrinsics[img_idx, :], True, set_camera_code,
+                       keep_images)
+    renderer.check_range()      # (its own packed buffers carry the status words of its frames: sticky, read once)
+    return out
+
+
+def _on_host(x):
+    """A float32 host copy (one transfer for all views: DepthViewRenderer.enqueue reads host floats)."""
+    return torch.as_tensor(x).detach().to(device="cpu", dtype=torch.float32)
+
+
+def _view_renderer(render_kwargs_test, H, W, args):
+    """The DepthViewRenderer of an evaluation loop (blocks of args.chunk), or None when the loop stays with render(): a
+    configuration plnerf_depth_render_view does not serve (a camera code, say, with args.input_ch_cam > 0), or kwargs that
+    ask for draws (perturb > 0 or density noise) -- the renderer's are counter-based and keyed by its own (seed, step), not
+    what render() would draw, so only the draw-free test-time settings, where the two routes agree bit for bit, go there."""
+    from .depthview import DepthViewRenderer
+    kw = {k: v for k, v in render_kwargs_test.items() if k not in ("near", "far", "ndc")}
+    if kw.get("perturb", 0.) > 0. or kw.get("raw_noise_std", 0.) > 0.:
+        return None
+    if getattr(args, "input_ch_cam", 0) > 0 or not DepthViewRenderer.supported(kw):
+        return None
+    return DepthViewRenderer(kw, H, W, min(int(args.chunk), H * W), render_kwargs_test.get("near", 0.),
+                             render_kwargs_test.get("far", 1.))
 
 
 def _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev):
@@ -463,7 +498,7 @@ def _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev):
 
 
 def test_images_samples(count, indices, images, depths, valid_depths, poses, H, W, intrinsics, lpips_alex, args,
-                        render_kwargs_test, embedcam_fn=None, with_test_time_optimization=False):
+                        render_kwargs_test, embedcam_fn=None, with_test_time_optimization=False, *, one_call=False):
     """run_nerf_sample_based_depth.py:349-421 (`--task test_samples_error`): how close the importance samples land to
     the rendered surface.  For each of `count` views of `indices` (all of them in order for None, else
     np.random.choice(indices, count, replace=False)), rendered under no_grad with the per-view intrinsics[i] =
@@ -475,7 +510,13 @@ def test_images_samples(count, indices, images, depths, valid_depths, poses, H, 
     device by plnerf_sample_error as soon as they exist (added to the view's fp64 row) and dropped, so no [H,W,N]
     hypothesis plane is ever held.  The rows are read back once, after the last view; the means are fp64 (the
     reference's are fp32).  images, depths and lpips_alex are accepted and unused, as there; the reference's
-    metrics_depth_samples.txt is MeanTracker.print(f) on the caller's side.  with_test_time_optimization raises."""
+    metrics_depth_samples.txt is MeanTracker.print(f) on the caller's side.  with_test_time_optimization raises.
+
+    one_call: each view is ONE library call (depthview.DepthViewRenderer, blocks of args.chunk) that scores every block's
+    hypotheses while they are in its workspace -- the same blocks added in the same order, so the same rows -- and no
+    hypotheses reach Python.  Only where the call serves the configuration and the kwargs ask for no draws (perturb 0, no
+    density noise: the test-time settings); any other configuration takes the route above.  The poses and intrinsics are
+    copied to the host once for all views."""
     if with_test_time_optimization:
         raise NotImplementedError("with_test_time_optimization: the per-view camera-code optimisation is not provided")
     dev = RB.default_device()
@@ -483,9 +524,18 @@ def test_images_samples(count, indices, images, depths, valid_depths, poses, H, 
     set_camera_code = _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev)
     chunk, n_rays = args.chunk, H * W
     rows = torch.zeros(count, L.SAMPLEERR_ROW, dtype=torch.float64, device=dev)
-    workspace = torch.empty(L.sample_error_workspace_bytes(min(chunk, n_rays)), dtype=torch.uint8, device=dev)
+    renderer = _view_renderer(render_kwargs_test, H, W, args) if one_call else None
+    if renderer is None:
+        workspace = torch.empty(L.sample_error_workspace_bytes(min(chunk, n_rays)), dtype=torch.uint8, device=dev)
+    else:
+        host_poses, host_intrinsics = _on_host(poses), _on_host(intrinsics)
     with torch.no_grad():
         for n, img_idx in enumerate(img_i):
+            if renderer is not None:
+                renderer.error_row.zero_()
+                renderer.enqueue(host_poses[img_idx, :3, :4], host_intrinsics[img_idx, :], valid=valid_depths[img_idx])
+                rows[n].copy_(renderer.error_row)
+                continue
             set_camera_code(img_idx)
             intrinsic = intrinsics[img_idx, :]
             rays_o, rays_d = get_rays(H, W, intrinsic, poses[img_idx, :3, :4])
@@ -499,6 +549,8 @@ def test_images_samples(count, indices, images, depths, valid_depths, poses, H, 
                                   out=rows[n], workspace=workspace, accumulate=True)
                 del extras
     _check_range(render_kwargs_test)
+    if renderer is not None:
+        renderer.check_range()      # (its own packed buffers carry the status words of its frames)
 
     mean_depth_metrics = MeanTracker()
     for total, counted in rows.cpu().tolist():
