@@ -3,20 +3,22 @@
 // source and nothing saved for a backward -- the launches render() -> batchify_rays() -> render_rays() reach through Python,
 // ctypes and torch under torch.no_grad(), with the same arguments, in the same order, on the one stream -- so the two routes
 // agree bit for bit.  The maps are written straight into the caller's frame planes at the block's pixel offset; one
-// plnerf_frame_export over the call's pixels follows the last block.  No kernel of the path is duplicated here.
+// plnerf_frame_export over the call's pixels follows the last block.  The forward up to the fine network and the choice
+// between a caller's plane and the workspace are step_common.h's.  No kernel of the path is duplicated here.
 #include "step_common.h"
 #include "../../include/plnerf_hip_view.h"
 
 namespace {
 
-using namespace plnerf_step;      // ALIGN, NOISE_STREAM, scale2, Carver (shared with the one-call training steps)
+using namespace plnerf_step;
 
 // The workspace, carved for config.max_rays: one block's rays, samples and raw outputs, and a block of every plane the
 // caller may leave out.
 struct Plan {
-    float *rays_o, *rays_d, *viewdirs, *near, *far, *o_ndc, *d_ndc;
-    float *z_c, *pts_c, *raw_c, *noise_c, *z_f, *pts_f, *raw_f, *noise_f;
-    float *disp, *acc, *depth, *rgb0, *disp0, *acc0, *depth0, *z_std;
+    Rays rays;
+    float *o_ndc, *d_ndc;
+    Samples coarse, fine;
+    ViewMaps left_out;
     size_t bytes;
 };
 
@@ -25,45 +27,27 @@ Plan carve(const plnerf_step_config* c, void* workspace) {
     const bool noise = c->raw_noise_std > 0.0f;
     Carver w{(unsigned char*)workspace, 0};
     Plan p{};
-    p.rays_o = w.floats(3 * R); p.rays_d = w.floats(3 * R); p.viewdirs = w.floats(3 * R);
-    p.near = w.floats(R); p.far = w.floats(R);
+    p.rays = w.rays(R);
     p.o_ndc = w.floats(c->ndc ? 3 * R : 0); p.d_ndc = w.floats(c->ndc ? 3 * R : 0);
-    p.z_c = w.floats(R * S); p.pts_c = w.floats(3 * R * S); p.raw_c = w.floats(4 * R * S);
-    p.noise_c = w.floats(noise ? R * S : 0);
-    p.z_f = w.floats(R * F); p.pts_f = w.floats(3 * R * F); p.raw_f = w.floats(4 * R * F);
-    p.noise_f = w.floats(noise ? R * F : 0);
-    p.disp = w.floats(R); p.acc = w.floats(R); p.depth = w.floats(R);
-    p.rgb0 = w.floats(3 * R); p.disp0 = w.floats(R); p.acc0 = w.floats(R); p.depth0 = w.floats(R); p.z_std = w.floats(R);
+    p.coarse = w.samples(R, S, noise);
+    p.fine = w.samples(R, F, noise);
+    p.left_out = w.view_maps(R);
     p.bytes = w.off;
     return p;
 }
 
-// plnerf_train_step's checks of the fields this call reads (the ray source, the bank and Adam are not its business)
-int check_config(const plnerf_step_config* c) {
-    if (!c) return PLNERF_EINVAL;
-    if (c->mode != PLNERF_MODE_LINEAR && c->mode != PLNERF_MODE_CONSTANT) return PLNERF_EINVAL;
-    if (c->max_rays < 1 || c->n_samples < (c->mode == PLNERF_MODE_LINEAR ? 2 : 3) || c->n_importance < 1) return PLNERF_EINVAL;
-    if (c->color_mode != PLNERF_COLOR_MIDPOINT && c->color_mode != PLNERF_COLOR_LEFT) return PLNERF_EINVAL;
-    if (c->H < 1 || c->W < 1 || (c->ndc && !(c->ndc_focal != 0.0)) || !(c->fx != 0.0f) || !(c->fy != 0.0f)) return PLNERF_EINVAL;
-    if (c->fwd_kernel != PLNERF_FWD_KERNEL_AUTO && c->fwd_kernel != PLNERF_FWD_KERNEL_RR && c->fwd_kernel != PLNERF_FWD_KERNEL_PP)
-        return PLNERF_EINVAL;
-    if (!(c->raw_noise_std >= 0.0f)) return PLNERF_EINVAL;
-    // the in-kernel encoding's widths (plnerf_mlp_fwd without `embedded`)
-    if (c->input_ch < 3 || c->input_ch > 63 || (c->input_ch - 3) % 6 != 0 || c->input_ch_views < 3 || c->input_ch_views > 27 ||
-        (c->input_ch_views - 3) % 6 != 0)
-        return PLNERF_EINVAL;
-    if (plnerf_mlp_packed_bytes(c->precision) == 0) return PLNERF_ENOSYS;
-    if (c->n_samples > PLNERF_MAX_SAMPLES || c->n_samples + c->n_importance > 1024) return PLNERF_ERANGE;
-    // (row counts are ints throughout the ABI)
-    if ((uint64_t)c->max_rays * (uint64_t)(c->n_samples + c->n_importance) > (uint64_t)INT32_MAX / 4) return PLNERF_ERANGE;
-    if ((uint64_t)c->H * (uint64_t)c->W > (1ull << 30)) return PLNERF_ERANGE;
-    return PLNERF_OK;
+Pass pass_of(const plnerf_step_config* c, int R, int ray_id0, uint32_t step, const float* t_vals, const float* u_vals) {
+    return make_pass(*c, c->mode, c->farcolorfix, 1.0f, 0.0f, R, ray_id0, step, t_vals, u_vals);
 }
 
-int check_net(const plnerf_view_net* n) {
-    if (!n->packed) return PLNERF_EINVAL;
-    for (int i = 0; i < PLNERF_N_PARAM_TENSORS; ++i)
-        if (!n->params[i]) return PLNERF_EINVAL;
+// Behind the shared checks, those of the fields only this entry reads: the view's size and intrinsics, NDC (the ray source,
+// the bank and Adam are not its business)
+int check_config(const plnerf_step_config* c) {
+    if (!c) return PLNERF_EINVAL;
+    const int rc = check_pass(pass_of(c, c->max_rays, 0, 0, nullptr, nullptr), min_samples(c->mode), 1024, 0);
+    if (rc) return rc;
+    if (c->H < 1 || c->W < 1 || (c->ndc && !(c->ndc_focal != 0.0)) || !(c->fx != 0.0f) || !(c->fy != 0.0f)) return PLNERF_EINVAL;
+    if ((uint64_t)c->H * (uint64_t)c->W > (1ull << 30)) return PLNERF_ERANGE;
     return PLNERF_OK;
 }
 
@@ -86,82 +70,41 @@ extern "C" int plnerf_render_view(const plnerf_step_config* c, const plnerf_view
     if (!io->t_vals || !io->rgb || (!c->perturb && !io->u_vals) || (io->depth16 && !io->depth)) return PLNERF_EINVAL;
     const Plan p = carve(c, workspace);
     if (workspace_bytes < p.bytes) return PLNERF_EINVAL;
-    if ((rc = plnerf_step::check_params_aligned(io->coarse.params)) || (rc = plnerf_step::check_params_aligned(io->fine.params)))
-        return rc;
+    if ((rc = check_params_aligned(io->coarse.params)) || (rc = check_params_aligned(io->fine.params))) return rc;
 
-    hipStream_t st = (hipStream_t)stream;
-    const int S = c->n_samples, N = c->n_importance, F = S + N, mode = c->mode;
-    const int prec = c->precision, xyz = c->input_ch, dir = c->input_ch_views;
-    const bool noise = c->raw_noise_std > 0.0f;
-#define VIEW_OK(call) do { rc = (call); if (rc) return rc; } while (0)
-
+    const int F = c->n_samples + c->n_importance;
     if (a->pack_weights) {
-        VIEW_OK(plnerf_mlp_pack_weights(io->coarse.params, prec, xyz, dir, io->coarse.packed, stream));
-        VIEW_OK(plnerf_mlp_pack_weights(io->fine.params, prec, xyz, dir, io->fine.packed, stream));
+        STEP_OK(plnerf_mlp_pack_weights(io->coarse.params, c->precision, c->input_ch, c->input_ch_views, io->coarse.packed, stream));
+        STEP_OK(plnerf_mlp_pack_weights(io->fine.params, c->precision, c->input_ch, c->input_ch_views, io->fine.packed, stream));
     }
     const int end = a->pix0 + a->n_pix;
     for (int p0 = a->pix0; p0 < end; p0 += c->max_rays) {      // (a ray's global id is its pixel index)
         const int R = end - p0 < c->max_rays ? end - p0 : c->max_rays;
-        const size_t at = (size_t)p0;
-        // a plane the caller left out: this block's values go to the workspace
-        float* rgb = io->rgb + 3 * at;
-        float* disp = io->disp ? io->disp + at : p.disp;
-        float* acc = io->acc ? io->acc + at : p.acc;
-        float* depth = io->depth ? io->depth + at : p.depth;
-        float* rgb0 = io->rgb0 ? io->rgb0 + 3 * at : p.rgb0;
-        float* disp0 = io->disp0 ? io->disp0 + at : p.disp0;
-        float* acc0 = io->acc0 ? io->acc0 + at : p.acc0;
-        float* depth0 = io->depth0 ? io->depth0 + at : p.depth0;
-        float* z_std = io->z_std ? io->z_std + at : p.z_std;
+        const Pass ps = pass_of(c, R, p0, a->step, io->t_vals, io->u_vals);
+        const ViewMaps m = block_maps(io, (size_t)p0, p.left_out);
 
         // ---- this block's rays: origins, directions, unit view directions, near / far ----
-        VIEW_OK(plnerf_view_rays(c->H, c->W, c->fx, c->fy, c->cx, c->cy, a->c2w, p0, R, c->near, c->far, p.rays_o, p.rays_d,
-                                 p.viewdirs, p.near, p.far, stream));
-        const float *o = p.rays_o, *d = p.rays_d;
+        Rays r = p.rays;
+        STEP_OK(plnerf_view_rays(c->H, c->W, c->fx, c->fy, c->cx, c->cy, a->c2w, p0, R, c->near, c->far, r.o, r.d, r.viewdirs,
+                                 r.near, r.far, stream));
         if (c->ndc) {      // (the view directions stay those of the camera-space rays)
-            VIEW_OK(plnerf_ndc_rays(c->H, c->W, c->ndc_focal, 1.0, p.rays_o, p.rays_d, R, p.o_ndc, p.d_ndc, stream));
-            o = p.o_ndc; d = p.d_ndc;
+            STEP_OK(plnerf_ndc_rays(c->H, c->W, c->ndc_focal, 1.0, r.o, r.d, R, p.o_ndc, p.d_ndc, stream));
+            r.o = p.o_ndc; r.d = p.d_ndc;
         }
 
-        // ---- coarse pass ----
-        VIEW_OK(plnerf_coarse_samples(o, d, p.near, p.far, io->t_vals, nullptr, c->seed, a->step, p0, R, S, c->lindisp ? 1 : 0,
-                                      c->perturb ? 1 : 0, p.z_c, p.pts_c, stream));
-        VIEW_OK(plnerf_mlp_fwd(io->coarse.packed, prec, p.pts_c, p.viewdirs, nullptr, xyz, dir, R * S, S, 1.0f, 0.0f, p.raw_c,
-                               nullptr, c->fwd_kernel, stream));
-        if (noise) {
-            VIEW_OK(plnerf_normal(c->seed, NOISE_STREAM, a->step, p0, R, S, p.noise_c, stream));
-            if (c->raw_noise_std != 1.0f) VIEW_OK(scale2(p.noise_c, (size_t)R * S, nullptr, 0, c->raw_noise_std, st));
-        }
-        if (mode == PLNERF_MODE_LINEAR)
-            VIEW_OK(plnerf_coarse_epilogue(p.raw_c, p.z_c, p.near, p.far, o, d, noise ? p.noise_c : nullptr,
-                                           c->perturb ? nullptr : io->u_vals, 0, c->seed, a->step, p0, R, S, N, c->color_mode,
-                                           c->white_bkgd ? 1 : 0, c->farcolorfix ? 1 : 0, c->zero_tol, c->epsilon, rgb0, disp0,
-                                           acc0, depth0, nullptr, nullptr, nullptr, p.z_f, p.pts_f, z_std, stream));
-        else
-            VIEW_OK(plnerf_coarse_epilogue_const(p.raw_c, p.z_c, p.near, p.far, o, d, noise ? p.noise_c : nullptr,
-                                                 c->perturb ? nullptr : io->u_vals, 0, c->seed, a->step, p0, R, S, N,
-                                                 c->white_bkgd ? 1 : 0, rgb0, disp0, acc0, depth0, nullptr, p.z_f, p.pts_f,
-                                                 z_std, stream));
-
-        // ---- fine pass ----
-        VIEW_OK(plnerf_mlp_fwd(io->fine.packed, prec, p.pts_f, p.viewdirs, nullptr, xyz, dir, R * F, F, 1.0f, 0.0f, p.raw_f,
-                               nullptr, c->fwd_kernel, stream));
-        if (noise) {
-            VIEW_OK(plnerf_normal(c->seed, NOISE_STREAM + 1, a->step, p0, R, F, p.noise_f, stream));
-            if (c->raw_noise_std != 1.0f) VIEW_OK(scale2(p.noise_f, (size_t)R * F, nullptr, 0, c->raw_noise_std, st));
-        }
-        VIEW_OK(plnerf_quad_fwd(p.raw_f, p.z_f, p.near, p.far, d, noise ? p.noise_f : nullptr, R, F, mode, c->color_mode,
-                                c->white_bkgd ? 1 : 0, c->farcolorfix ? 1 : 0, rgb, disp, acc, depth, nullptr, nullptr, nullptr,
+        // ---- both passes up to the fine network's raw output, then the last stage ----
+        STEP_OK(forward(ps, r, io->coarse.packed, io->fine.packed, p.coarse, p.fine, m.coarse, stream));
+        STEP_OK(plnerf_quad_fwd(p.fine.raw, p.fine.z, r.near, r.far, r.d, p.fine.noise, R, F, ps.mode, ps.color_mode, ps.white_bkgd,
+                                ps.farcolorfix, m.fine.rgb, m.fine.disp, m.fine.acc, m.fine.depth, nullptr, nullptr, nullptr,
                                 stream));
     }
 
     // ---- the call's pixels as 8-bit colour and 16-bit depth ----
     if (io->rgb8 || io->depth16) {
         const size_t at = (size_t)a->pix0;
-        VIEW_OK(plnerf_frame_export(io->rgb8 ? io->rgb + 3 * at : nullptr, io->rgb8 ? io->rgb8 + 3 * at : nullptr,
+        STEP_OK(plnerf_frame_export(io->rgb8 ? io->rgb + 3 * at : nullptr, io->rgb8 ? io->rgb8 + 3 * at : nullptr,
                                     io->depth16 ? io->depth + at : nullptr, a->depth16_scale,
                                     io->depth16 ? io->depth16 + at : nullptr, a->n_pix, stream));
     }
-#undef VIEW_OK
     return PLNERF_OK;
 }

@@ -116,6 +116,8 @@ int main(int argc, char** argv) {
     if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ENOSYS || q(&bad) != 0 || lay(&bad, &v) != PLNERF_ENOSYS) return 15;
     bad = c; bad.n_samples = 600; bad.n_importance = 600;
     if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ERANGE) return 16;                /* compiled limits */
+    bad = c; bad.n_importance = 2147483647;
+    if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ERANGE || q(&bad) != 0) return 28; /* no signed overflow in S + N */
     a.ray_id0 = 480 * 640 - 1000;
     if (p(&c, &io, &a, ws, need, NULL) != PLNERF_ERANGE) return 17;                  /* ray_id0 + rays > H * W */
     a.ray_id0 = 0;

@@ -84,6 +84,8 @@ int main(int argc, char** argv) {
     if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ENOSYS) return 11;                /* unknown precision */
     bad = c; bad.n_samples = 600; bad.n_importance = 600;
     if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ERANGE) return 12;                /* S + N > 1024 */
+    bad = c; bad.n_importance = 2147483647;
+    if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ERANGE || q(&bad) != 0) return 22; /* no signed overflow in S + N */
     bad = c; bad.max_rays = 0;
     if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_EINVAL) return 13;
     if (p(&c, &io, &a, ws, need - 1, NULL) != PLNERF_EINVAL) return 14;              /* workspace too small */

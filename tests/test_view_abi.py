@@ -112,6 +112,8 @@ int main(int argc, char** argv) {
     if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ENOSYS || q(&bad) != 0) return 12; /* a precision that is not built */
     bad = c; bad.n_samples = 600; bad.n_importance = 600;
     if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ERANGE || q(&bad) != 0) return 13; /* S + N > 1024 */
+    bad = c; bad.n_importance = 2147483647;
+    if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ERANGE || q(&bad) != 0) return 70; /* no signed overflow in S + N */
     bad = c; bad.max_rays = 1 << 24;
     if (p(&bad, &io, &a, ws, need, NULL) != PLNERF_ERANGE || q(&bad) != 0) return 14; /* the row-count overflow */
     bad = c; bad.max_rays = 0;
