@@ -24,7 +24,8 @@ from .png import read_png, write_png
 from .view import ViewRenderer, render_path_frames
 from . import depthview   # plnerf_depth_render_view: the depth-supervised variant's frames, one library call each
 from .depthview import DepthViewRenderer, render_video_frames
-
+from . import camcode     # test-time optimisation of a held-out view's camera code (plnerf_camcode_sweep / _update)
+from .camcode import CameraCodeOptimizer, optimize_camera_embedding
 
 
 def library_path():
@@ -43,4 +44,5 @@ __all__ = [
     "set_draw_source", "MeanTracker", "compute_rmse", "image_metrics", "metric_rows", "render_images_with_metrics",
     "sample_error_rows", "DepthViews", "DepthTrainStep", "ViewRenderer", "render_path_frames", "write_png", "read_png",
     "write_images_with_metrics", "write_images_with_metrics_testdist", "depthview", "DepthViewRenderer", "render_video_frames",
+    "camcode", "CameraCodeOptimizer", "optimize_camera_embedding",
 ]

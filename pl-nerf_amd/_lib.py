@@ -364,6 +364,32 @@ def _disjoint(experimental, registered):
 
 _disjoint(EXPERIMENTAL_SIGNATURES, ALL_SIGNATURES)
 
+# ---- a third table, same row shape, for include/experimental/plnerf_hip_camcode.h: the test-time optimisation of a view's
+# camera code (plnerf_amd.camcode).  Experimental like the table above (no PLNERF_VERSION step) and kept apart from it: each
+# of the two existing tables is pinned row by row by its own tests, so a header that neither of them lists gets its own.
+CAMCODE_MAX_WIDTH, CAMCODE_MAX_CAM, CAMCODE_MAX_ROWS, CAMCODE_MAX_GROUPS = 128, 32, 1024, 2048      # PLNERF_CAMCODE_MAX_*
+
+
+class CamcodeState(ctypes.Structure):
+    """plnerf_camcode_state (device memory: filled on the host, uploaded once)."""
+    _fields_ = [("cam", c_fl * 32), ("exp_avg", c_fl * 32), ("exp_avg_sq", c_fl * 32), ("best_cam", c_fl * 32), ("lr", c_fl),
+                ("best", c_fl), ("max_psnr", c_fl), ("step", c_i), ("num_bad_epochs", c_i), ("best_iter", c_i)]
+
+
+CAMCODE_STRUCTS = {"plnerf_camcode_state": CamcodeState}
+CAMCODE_SIGNATURES = {
+    "plnerf_camcode_sweep_workspace_bytes": (ctypes.c_size_t, [c_i]),
+    "plnerf_camcode_sweep": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f, c_i] + [c_f] * 6 + [ctypes.c_size_t, c_f, c_f, c_s]),
+    # (the state lives in DEVICE memory: a device pointer like every other, not a ctypes pointer the host could follow)
+    "plnerf_camcode_update": (c_i, [c_f, c_i, c_f, c_f, c_i] + [c_fl] * 4 + [c_i, c_f, c_f, c_i, c_s]),
+}
+CAMCODE_HEADERS = (
+    ("experimental/plnerf_hip_camcode.h", CAMCODE_SIGNATURES, CAMCODE_STRUCTS),
+)
+CAMCODE_TABLE_SIGNATURES = _merge(CAMCODE_HEADERS)
+_disjoint(CAMCODE_TABLE_SIGNATURES, ALL_SIGNATURES)
+_disjoint(CAMCODE_TABLE_SIGNATURES, EXPERIMENTAL_SIGNATURES)
+
 _lib = None
 
 
@@ -378,7 +404,7 @@ def lib():
                 "plnerf_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
-        for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES}.items():
+        for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -442,15 +442,18 @@ def render_images_with_metrics(count, indices, images, depths, valid_depths, pos
     """run_nerf_sample_based_depth.py:424-510: evaluate.render_images_with_metrics on this variant's render, with the
     per-view intrinsics[i] = (fx, fy, cx, cy) and the sensor depths[i] [H,W,1] / valid_depths[i] [H,W] of every view.
     With args.input_ch_cam > 0 the camera code is embedcam_fn(i), or zeros when embedcam_fn is None (set in
-    render_kwargs_test["embedded_cam"], as there).  with_test_time_optimization (the per-view optimisation of that code)
-    is not provided: it raises.  one_call: frames come from a depthview.DepthViewRenderer (one library call per frame, blocks
-    of args.chunk) when it serves the configuration AND the kwargs ask for no draws (perturb 0, no density noise: the
-    test-time settings, at which its frames are render()'s bit for bit); any other configuration takes render() as before.
+    render_kwargs_test["embedded_cam"], as there).  with_test_time_optimization: with embedcam_fn None, the code of every view is
+    optimised first where the reference does (:458-463; camcode.optimize_camera_embedding, one CameraCodeOptimizer kept across
+    the views where the cached route serves the configuration); with args.input_ch_cam == 0 there is no code to optimise and
+    the flag raises (the reference ignores it there).
+    one_call: frames come from a depthview.DepthViewRenderer (one library call per frame, blocks of args.chunk) when it
+    serves the configuration AND the kwargs ask for no draws (perturb 0, no density noise: the test-time settings, at which
+    its frames are render()'s bit for bit); any other configuration takes render() as before.
     The poses and intrinsics are copied to the host once for all views (the call reads host floats), and the renderer's range
     status words are read once, after the last view."""
-    if with_test_time_optimization:
-        raise NotImplementedError("with_test_time_optimization: the per-view camera-code optimisation is not provided")
-    set_camera_code = _camera_code_setter(args, render_kwargs_test, embedcam_fn, RB.default_device())
+    optimise = _test_time_optimizer(with_test_time_optimization, args, render_kwargs_test, embedcam_fn, images, poses,
+                                    intrinsics, H, W)
+    set_camera_code = _camera_code_setter(args, render_kwargs_test, embedcam_fn, RB.default_device(), optimise)
     renderer = _view_renderer(render_kwargs_test, H, W, args) if one_call else None
     if renderer is None:
         return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
@@ -487,14 +490,38 @@ def _view_renderer(render_kwargs_test, H, W, args):
                              render_kwargs_test.get("far", 1.))
 
 
-def _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev):
+def _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev, optimise=None):
     """The evaluation loops' camera code of view img_idx (run_nerf_sample_based_depth.py:384-395, 458-469): with
-    args.input_ch_cam > 0, embedcam_fn(i), or zeros when embedcam_fn is None, set in render_kwargs_test["embedded_cam"]."""
+    args.input_ch_cam > 0, embedcam_fn(i), or zeros when embedcam_fn is None, set in render_kwargs_test["embedded_cam"];
+    optimise(img_idx) (_test_time_optimizer) then replaces the zeros by the view's optimised code."""
     def set_camera_code(img_idx):
         if getattr(args, "input_ch_cam", 0) > 0:
             render_kwargs_test["embedded_cam"] = (torch.zeros((args.input_ch_cam,), device=dev) if embedcam_fn is None
                                                   else embedcam_fn(torch.tensor(img_idx, device=dev)))
+            if optimise is not None and embedcam_fn is None:
+                optimise(img_idx)
     return set_camera_code
+
+
+def _test_time_optimizer(with_test_time_optimization, args, render_kwargs_test, embedcam_fn, images, poses, intrinsics, H, W):
+    """with_test_time_optimization of the two evaluation loops (:384-389, :458-463): None without the flag, else
+    optimise(img_idx), which leaves the view's optimised code in render_kwargs_test["embedded_cam"].  One
+    camcode.CameraCodeOptimizer serves all views where the cached route takes the configuration; elsewhere each view runs
+    the plain route.  (The reference also writes the code to test_latent_codes_<scene>/<i>.txt; that stays with the caller.)"""
+    if not with_test_time_optimization:
+        return None
+    if getattr(args, "input_ch_cam", 0) < 1:
+        raise NotImplementedError("with_test_time_optimization: args.input_ch_cam is 0, there is no code to optimise")
+    from . import camcode
+    fast = []
+
+    def optimise(img_idx):
+        if not fast:
+            ok = camcode.CameraCodeOptimizer.unsupported_reason(render_kwargs_test, args, H, W, 32 << 30) is None
+            fast.append(camcode.CameraCodeOptimizer(render_kwargs_test, H, W, args) if ok else None)
+        camcode.optimize_camera_embedding(images[img_idx], poses[img_idx, :3, :4], H, W, intrinsics[img_idx, :], args,
+                                          render_kwargs_test, optimizer=fast[0], route="auto" if fast[0] else "plain")
+    return optimise
 
 
 def test_images_samples(count, indices, images, depths, valid_depths, poses, H, W, intrinsics, lpips_alex, args,
@@ -510,18 +537,19 @@ def test_images_samples(count, indices, images, depths, valid_depths, poses, H, 
     device by plnerf_sample_error as soon as they exist (added to the view's fp64 row) and dropped, so no [H,W,N]
     hypothesis plane is ever held.  The rows are read back once, after the last view; the means are fp64 (the
     reference's are fp32).  images, depths and lpips_alex are accepted and unused, as there; the reference's
-    metrics_depth_samples.txt is MeanTracker.print(f) on the caller's side.  with_test_time_optimization raises.
+    metrics_depth_samples.txt is MeanTracker.print(f) on the caller's side.  with_test_time_optimization: as
+    render_images_with_metrics (`images` is read then: the optimisation's targets).
 
     one_call: each view is ONE library call (depthview.DepthViewRenderer, blocks of args.chunk) that scores every block's
     hypotheses while they are in its workspace -- the same blocks added in the same order, so the same rows -- and no
     hypotheses reach Python.  Only where the call serves the configuration and the kwargs ask for no draws (perturb 0, no
     density noise: the test-time settings); any other configuration takes the route above.  The poses and intrinsics are
     copied to the host once for all views."""
-    if with_test_time_optimization:
-        raise NotImplementedError("with_test_time_optimization: the per-view camera-code optimisation is not provided")
+    optimise = _test_time_optimizer(with_test_time_optimization, args, render_kwargs_test, embedcam_fn, images, poses,
+                                    intrinsics, H, W)
     dev = RB.default_device()
     count, img_i = _choose_views(count, indices)
-    set_camera_code = _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev)
+    set_camera_code = _camera_code_setter(args, render_kwargs_test, embedcam_fn, dev, optimise)
     chunk, n_rays = args.chunk, H * W
     rows = torch.zeros(count, L.SAMPLEERR_ROW, dtype=torch.float64, device=dev)
     renderer = _view_renderer(render_kwargs_test, H, W, args) if one_call else None
