@@ -2,8 +2,10 @@
 frame of the depth-supervised variant (depth.py), its `test_samples_error` row scored while the hypotheses are in the
 workspace, and frames that leave the device as 8-bit colour / 16-bit depth.
 
-`DepthViewRenderer` is view.ViewRenderer for that variant: it owns the frame planes, the workspace, both packed weight
-buffers, the two linspace tables and the three structs of the (experimental) ABI, filled once.  What a frame holds is what
+`DepthViewRenderer` is view.ViewRenderer for that variant, on the same base (onecall.Renderer owns the frame planes, the
+workspace, both packed weight buffers, the two linspace tables and the three structs of the (experimental) ABI, filled
+once); what is written here is this entry's own: the per-call intrinsic, the hypothesis plane, the sampling-error row and
+the millimetre plane.  What a frame holds is what
 depth.render() computes under functional.DrawSource(seed, 0, step) for the same pose and intrinsics GIVEN AS DEVICE TENSORS,
 bit for bit: depth.render() builds its rays with depth.get_rays where the pose lives, and the call's rays are the device's
 evaluation of those expressions.  Configurations outside the call (supported()) stay with depth.render().
@@ -11,41 +13,30 @@ evaluation of those expressions.  Configurations outside the call (supported()) 
 `render_video_frames` is the frame loop of render_video (run_nerf_sample_based_depth.py:277-295) on that route: '{idx}.png'
 of to8b(rgb) and of the depth in millimetres, without the colour-mapped plane and without the mp4.
 """
-import ctypes
 import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from . import functional as Fn
-from .nerf import NeRF
+from .onecall import Renderer, fill_depth, fill_sampling, refusal_head
 from .png import write_png
-from .view import _aligned
 
 
-class DepthViewRenderer:
+class DepthViewRenderer(Renderer):
     """Frames of H x W views through plnerf_depth_render_view.  render_kwargs: depth.create_nerf's dict (render_kwargs_test,
     say) without near / far; chunk: pixels per block (depth.render()'s chunk).  The pose and the intrinsic (fx, fy, cx, cy)
     handed to render() / enqueue() may live anywhere: 12 + 4 host floats are read from them."""
+    ENTRY, IO, ARGS, FALLBACK = "plnerf_depth_render_view", L.DepthViewIo, L.DepthViewArgs, "depth.render()"
 
     @staticmethod
     def unsupported_reason(render_kwargs):
         """Why plnerf_depth_render_view cannot serve this configuration (None: it can)."""
         from .depth import _host_box, _kernel_encoding
         kw = render_kwargs
-        c, f = kw.get("network_fn"), kw.get("network_fine")
-        if not (isinstance(c, NeRF) and isinstance(f, NeRF)) or c is f:
-            return "two networks (network_fn and network_fine) of the package's NeRF class are needed"
-        if int(kw.get("N_importance", 0)) < 1:
-            return "N_importance must be at least 1"
-        if not kw.get("use_viewdirs", False):
-            return "use_viewdirs must be set"
-        if kw.get("mode") not in ("linear", "constant") or kw.get("color_mode", "midpoint") not in ("midpoint", "left"):
-            return "mode must be linear or constant, color_mode midpoint or left"
-        S, N = int(kw["N_samples"]), int(kw["N_importance"])
-        if S < (3 if kw["mode"] == "constant" else 2) or S + N > L.DEPTH_STEP_MAX_SAMPLES:
-            return "the sample counts are outside the kernels' limits"
+        why = refusal_head(kw, L.DEPTH_STEP_MAX_SAMPLES)
+        if why is not None:
+            return why
         if kw.get("is_joint", False):
             return "is_joint stays with depth.render()"
         if kw.get("pytest", False) or kw.get("retraw", False) or kw.get("c2w_staticcam") is not None or kw.get("with_5_9", False):
@@ -62,6 +53,7 @@ class DepthViewRenderer:
         enc = _kernel_encoding(emb[0], emb[1], True)
         if enc is None or not _host_box(*box)[2]:
             return "the in-kernel encoding needs the package's encoders and an identity bounding box"
+        c, f = kw["network_fn"], kw["network_fine"]
         if c.precision != f.precision or c.density_beta != f.density_beta:
             return "both networks must run in one precision and with one density activation"
         for n in (c, f):
@@ -72,66 +64,21 @@ class DepthViewRenderer:
                 return "the networks must live on the GPU"
         return None
 
-    @staticmethod
-    def supported(render_kwargs):
-        return DepthViewRenderer.unsupported_reason(render_kwargs) is None
-
     def __init__(self, render_kwargs, H, W, chunk, near, far, seed=0):
         from .depth import _kernel_encoding
-        why = self.unsupported_reason(render_kwargs)
-        if why is not None:
-            raise ValueError(f"DepthViewRenderer: {why}; use depth.render()")
-        kw = render_kwargs
-        self.nets = (kw["network_fn"], kw["network_fine"])
-        coarse = self.nets[0]
-        dev = coarse.param_list()[0].device
-        self.device, self.H, self.W, self.far = dev, int(H), int(W), float(far)
-        self.precision = coarse.precision
-        cfg = self.config = L.DepthViewConfig()
-        cfg.max_rays, cfg.n_samples, cfg.n_importance = int(chunk), int(kw["N_samples"]), int(kw["N_importance"])
-        cfg.mode, cfg.color_mode = L.MODE[kw["mode"]], L.COLOR[kw.get("color_mode", "midpoint")]
-        cfg.lindisp, cfg.perturb = int(bool(kw.get("lindisp", False))), int(kw.get("perturb", 0.) > 0.)
-        cfg.white_bkgd = int(bool(kw.get("white_bkgd", False)))
-        cfg.raw_noise_std = float(kw.get("raw_noise_std", 0.))
-        cfg.zero_tol, cfg.epsilon = float(kw.get("zero_tol", 1e-4)), float(kw.get("epsilon", 1e-3))
+        kw = self._accepted(render_kwargs)
+        coarse = kw["network_fn"]
+        cfg = L.DepthViewConfig()
+        fill_sampling(cfg, kw, chunk, coarse, seed, mode=kw["mode"])
         cfg.H, cfg.W, cfg.near, cfg.far = int(H), int(W), float(near), float(far)
-        cfg.precision, cfg.fwd_kernel = L.PRECISION[coarse.precision], L.FWD_KERNEL
-        cfg.input_ch, cfg.input_ch_views = int(coarse.input_ch), int(coarse.hip_view_ch)
         emb = kw["network_query_fn"].embedders
-        cfg.input_scale, cfg.density_beta = float(_kernel_encoding(emb[0], emb[1], True)[2]), float(coarse.density_beta)
-        cfg.seed = int(seed)
-        nbytes = L.lib().plnerf_depth_render_view_workspace_bytes(ctypes.byref(cfg))
-        if nbytes == 0:
-            raise ValueError("DepthViewRenderer: plnerf_depth_render_view refuses this configuration; use depth.render()")
-        self.workspace, self.workspace_bytes = _aligned(nbytes, dev), nbytes
-        self.t_vals = Fn.cpu_linspace(cfg.n_samples, dev)
-        self.u_vals = Fn.cpu_linspace(cfg.n_importance, dev)
-        n = self.H * self.W
-        self.planes = {name: torch.empty((n, 3) if name in ("rgb", "rgb0") else (n,), device=dev) for name in L.VIEW_PLANES}
+        fill_depth(cfg, _kernel_encoding(emb[0], emb[1], True)[2], coarse)
+        self._build(kw, cfg, H, W, far)
         self._pred_hyp = None                                                 # [H W, N], allocated when first asked for
-        self.error_row = torch.zeros(L.SAMPLEERR_ROW, dtype=torch.float64, device=dev)
-        self.rgb8 = torch.empty(n, 3, device=dev, dtype=torch.uint8)
-        self.depth16 = torch.empty(n, device=dev, dtype=torch.int16)          # (uint16 bit patterns: depth / far)
-        self.depth_mm16 = torch.empty(n, device=dev, dtype=torch.int16)       # (uint16 bit patterns: millimetres)
-        # the renderer's own packed buffers (zeroed once: the kernels only ever OR into the status word)
-        packed_bytes = L.lib().plnerf_mlp_packed_bytes(cfg.precision)
-        self.packed = tuple(torch.zeros(packed_bytes // 4, device=dev, dtype=torch.float32) for _ in range(2))
-        self._status_off = L.lib().plnerf_mlp_status_offset(cfg.precision) // 4
-        io = self.io = L.DepthViewIo()
-        self._params = tuple([p.detach() for p in net.param_list()] for net in self.nets)
-        for io_net, params, packed in zip((io.coarse, io.fine), self._params, self.packed):
-            for k, p in enumerate(params):
-                io_net.params[k] = L.dptr(p, f"params[{k}]").value
-            io_net.packed = packed.data_ptr()
-        io.t_vals, io.u_vals = self.t_vals.data_ptr(), self.u_vals.data_ptr()
-        for name in L.VIEW_PLANES:
-            setattr(io, name, self.planes[name].data_ptr())
-        self.args = L.DepthViewArgs()
-        self.args.pack_weights = 1
-        self.args.depth16_scale = float(np.float32(1.0) / np.float32(far))
+        self.error_row = torch.zeros(L.SAMPLEERR_ROW, dtype=torch.float64, device=self.device)
+        self.depth_mm16 = torch.empty(self.H * self.W, device=self.device, dtype=torch.int16)      # (uint16 bit patterns: millimetres)
         self.args.depth_mm_mult = 1000.0
         self._valid = None
-        self._refs = (ctypes.byref(cfg), ctypes.byref(io), ctypes.byref(self.args), ctypes.c_void_p(self.workspace.data_ptr()))
 
     @property
     def pred_hyp(self):
@@ -139,31 +86,6 @@ class DepthViewRenderer:
         if self._pred_hyp is None:
             self._pred_hyp = torch.empty(self.H * self.W, self.config.n_importance, device=self.device)
         return self._pred_hyp
-
-    def current(self):
-        """Do the parameter addresses the structs hold still belong to the live networks (a .to() or a precision change
-        moves them)?"""
-        return all(net.precision == self.precision and
-                   all(p.data_ptr() == q.data_ptr() for p, q in zip(net.param_list(), params))
-                   for net, params in zip(self.nets, self._params))
-
-    def status_words(self):
-        """Both packed buffers' range status words, (coarse, fine), as 1-element int32 views."""
-        return tuple(p.view(torch.int32)[self._status_off:self._status_off + 1] for p in self.packed)
-
-    def check_range(self, bits=None):
-        """The evaluation loops' check for the guarded precisions: a clamped frame must not pass silently.  bits: the two
-        status words as host integers (a caller that copied them itself); None reads them from the device (synchronises)."""
-        if self.precision not in L.GUARDED_PRECISIONS:
-            return
-        if bits is None:
-            bits = [int(word.item()) for word in self.status_words()]
-        for b, word, which in zip(bits, self.status_words(), ("coarse", "fine")):
-            if b:
-                word.zero_()
-                raise FloatingPointError(
-                    f"plnerf_amd: the {which} network left the IEEE-half range while rendering (status {b}, precision="
-                    f"{self.precision!r}): the frame was clamped.  Use precision='bf16x3' or 'fp32' for this network.")
 
     def enqueue(self, c2w, intrinsic, step=0, export=False, pix0=0, n_pix=None, valid=None, want_hyp=False):
         """Enqueue pixels [pix0, pix0 + n_pix) of the view (c2w, intrinsic = (fx, fy, cx, cy)) on the current stream (the
@@ -173,16 +95,9 @@ class DepthViewRenderer:
         gets there.  The call reads 12 + 4 HOST floats: hand over host tensors (or lists) and nothing waits for the device; a
         pose or an intrinsic that lives on the device costs a blocking device-to-host copy each, per call -- a loop over many
         views copies them to the host once, before it starts (as depth.test_images_samples(one_call=True) does)."""
-        if not self.current():
-            raise RuntimeError("DepthViewRenderer: the networks' parameters moved; build a new DepthViewRenderer")
-        a = self.args
-        a.c2w[:] = [float(v) for v in torch.as_tensor(c2w, device="cpu")[:3, :4].reshape(-1)]
+        self._aim(c2w, step, export, pix0, n_pix)
+        a, io = self.args, self.io
         a.fx, a.fy, a.cx, a.cy = [float(v) for v in torch.as_tensor(intrinsic, device="cpu").reshape(-1)[:4]]
-        a.step, a.pix0 = int(step), int(pix0)
-        a.n_pix = self.H * self.W - int(pix0) if n_pix is None else int(n_pix)
-        io = self.io
-        io.rgb8 = self.rgb8.data_ptr() if export else None
-        io.depth16 = self.depth16.data_ptr() if export else None
         io.depth_mm16 = self.depth_mm16.data_ptr() if export else None
         io.pred_hyp = self.pred_hyp.data_ptr() if want_hyp else None
         if valid is not None:
@@ -193,9 +108,7 @@ class DepthViewRenderer:
         else:
             io.valid, io.error_row = None, None
         self._valid = valid      # (alive until the next call is enqueued behind this one)
-        cfg, io_ref, args, ws = self._refs
-        L.check(L.lib().plnerf_depth_render_view(cfg, io_ref, args, ws, self.workspace_bytes, L.stream()),
-                "plnerf_depth_render_view")
+        self._call()
 
     def render(self, c2w, intrinsic, step=0, export=False, valid=None, want_hyp=False, check=True):
         """[rgb_map, disp_map, acc_map, extras] of the full view, shaped like depth.render()'s result; every tensor is a
@@ -211,18 +124,15 @@ class DepthViewRenderer:
             self.enqueue(c2w, intrinsic, step, export, valid=valid, want_hyp=want_hyp)
             if check:
                 self.check_range()
-        H, W, p = self.H, self.W, self.planes
-        shaped = {k: (v.view(H, W, 3) if v.dim() == 2 else v.view(H, W)) for k, v in p.items()}
-        extras = {"rgb0": shaped["rgb0"], "disp0": shaped["disp0"], "acc0": shaped["acc0"], "depth0": shaped["depth0"],
-                  "depth_map": shaped["depth"], "z_std": shaped["z_std"]}
+        ret = self._result(export)
+        extras = ret[3]
         if want_hyp:
-            extras["pred_hyp"] = self.pred_hyp.view(H, W, -1)
+            extras["pred_hyp"] = self.pred_hyp.view(self.H, self.W, -1)
         if valid is not None:
             extras["sample_error_row"] = self.error_row
         if export:
-            extras["rgb8"], extras["depth16"] = self.rgb8.view(H, W, 3), self.depth16.view(H, W)
-            extras["depth_mm16"] = self.depth_mm16.view(H, W)
-        return [shaped["rgb"], shaped["disp"], shaped["acc"], extras]
+            extras["depth_mm16"] = self.depth_mm16.view(self.H, self.W)
+        return ret
 
 
 def render_video_frames(poses, H, W, intrinsics, rgb_dir, depth_dir, render_kwargs_test, chunk, seed=0):
@@ -246,30 +156,13 @@ def render_video_frames(poses, H, W, intrinsics, rgb_dir, depth_dir, render_kwar
     intr = intr.reshape(1, 4).expand(n, 4) if intr.numel() == 4 else intr.reshape(n, -1)
     # (host copies, made once: enqueue reads host floats and must not wait for the device between two frames)
     host_poses = [torch.as_tensor(c2w).detach().to(device="cpu", dtype=torch.float32)[:3, :4] for c2w in poses]
-    stage = [{"rgb8": torch.empty(H, W, 3, dtype=torch.uint8).pin_memory(),
-              "mm16": torch.empty(H, W, dtype=torch.int16).pin_memory(),
-              "status": torch.zeros(2, dtype=torch.int32).pin_memory(), "done": torch.cuda.Event()} for _ in range(2)]
-    # (the renderer has ONE set of planes: frame idx + 1 overwrites them in stream order, after frame idx's copies)
 
-    def finish(i):
-        s = stage[i % 2]
-        s["done"].synchronize()
-        renderer.check_range([int(b) for b in s["status"]])
+    def finish(i, s):
         write_png(os.path.join(rgb_dir, frame_name(i)), s["rgb8"].numpy())
         write_png(os.path.join(depth_dir, frame_name(i)), s["mm16"].numpy().view(np.uint16))
 
-    with torch.no_grad():
-        for i, c2w in enumerate(host_poses):
-            renderer.enqueue(c2w, intr[i], step=i, export=True)
-            s = stage[i % 2]
-            s["rgb8"].copy_(renderer.rgb8.view(H, W, 3), non_blocking=True)
-            s["mm16"].copy_(renderer.depth_mm16.view(H, W), non_blocking=True)
-            for k, word in enumerate(renderer.status_words()):
-                s["status"][k:k + 1].copy_(word, non_blocking=True)
-            s["done"].record()
-            if i > 0:
-                finish(i - 1)
-        finish(n - 1)
+    renderer.staged_frames(n, lambda i: renderer.enqueue(host_poses[i], intr[i], step=i, export=True),
+                           [("rgb8", renderer.rgb8.view(H, W, 3)), ("mm16", renderer.depth_mm16.view(H, W))], finish)
     return n
 
 

@@ -8,6 +8,11 @@ output pointer.  Device memory that can move under a plan (a network's packed bu
 optim.FlatAdam's flat buffers, the moments after a `load_state_dict`) is looked at before every step with a handful of
 pointer compares, the way FlatAdam.step confirms its own layout: `current()` says whether the plan still describes the
 live objects, and train.TrainStep builds a new one when it does not.  A plan never steps memory it has not just seen.
+
+`DepthStepPlan` is the same for plnerf_depth_train_step (include/plnerf_hip_depthstep.h).  What the two plans share is
+written once: the config fields in onecall's fillers (which the frame renderers use too, and from whose tuples the plan
+keys are built), and in `_Plan` below the workspace that serves both modes' entries, the gradient block, the two _NetSlots
+and the tail of a step; `_flat_adam_over` is the test both supported() start from.
 """
 import ctypes
 
@@ -15,16 +20,15 @@ import torch
 
 from . import _lib as L
 from . import functional as Fn
+from .onecall import aligned_workspace, fill_adam, fill_depth, fill_pinhole, fill_sampling, pinhole, sampling, tables
 from .optim import FlatAdam
 
 
 def plan_key(kw, kind, max_rays, H, W, K, near, far, bank, seed):
-    """Everything a plan's config is built from: a step whose key differs gets a plan of its own."""
-    return (kind, int(max_rays), int(H), int(W), float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]), float(near),
-            float(far), id(bank) if bank is not None else None, int(seed), int(kw["N_samples"]), int(kw["N_importance"]),
-            kw["color_mode"], bool(kw.get("lindisp", False)), kw.get("perturb", 0.) > 0., bool(kw.get("white_bkgd", False)),
-            bool(kw.get("farcolorfix", False)), float(kw.get("raw_noise_std", 0.)), float(kw.get("zero_tol", 1e-4)),
-            float(kw.get("epsilon", 1e-3)), bool(kw.get("ndc", True)), L.FWD_KERNEL)
+    """Everything a plan's config is built from: a step whose key differs gets a plan of its own.  The sampling and camera
+    fields are the tuples the config is filled from."""
+    return (kind, int(max_rays), id(bank) if bank is not None else None, int(seed), sampling(kw),
+            pinhole(kw.get("ndc", True), K, H, W, near, far), L.FWD_KERNEL)
 
 
 class _NetSlot:
@@ -111,85 +115,91 @@ class _NetSlot:
                 p.grad = g
 
 
-class StepPlan:
+def _flat_adam_over(opt, params, nets):
+    """Is `opt` a FlatAdam with one flat group over exactly `params`, plain Adam (no decay, amsgrad or maximize), guarded
+    by nothing but device words and the step's own networks?  What a _NetSlot takes for granted."""
+    if not (isinstance(opt, FlatAdam) and len(opt.param_groups) == 1 and len(opt._flat) == 1 and opt._flat[0] is not None):
+        return False
+    group = opt.param_groups[0]
+    ps = group['params']
+    if len(ps) != len(params) or any(a is not b for a, b in zip(ps, params)):
+        return False
+    if group.get('weight_decay', 0) or group.get('amsgrad') or group.get('maximize'):
+        return False
+    return all(isinstance(g, torch.Tensor) or any(g is n for n in nets) for g in opt.guards)
+
+
+class _Plan:
+    """What both plans are made of behind their filled config."""
+    ENTRY = ENTRY_CONST = None      # the entry point and its piecewise-constant sibling: same structs, same workspace
+
+    def _build(self, cfg, io, args, nets, opts, firsts, launches):
+        """opts[k], firsts[k]: network k's optimizer and the index of its first parameter in that optimizer's flat group;
+        launches: _NetSlot's."""
+        dev = self.device = nets[0].param_list()[0].device
+        self.config, self.io, self.args = cfg, io, args
+        # ONE workspace for both entries (they carve it alike): a constant_init warm-up switches entries between steps on
+        # the same memory and the same gradient buffers.  A query answers 0 for the mode its entry does not serve, and for a
+        # shape its kernels refuse (N_samples = 2).
+        by_mode = {}
+        for mode, entry in (("linear", self.ENTRY), ("constant", self.ENTRY_CONST)):
+            if hasattr(cfg, "mode"):
+                cfg.mode = L.MODE[mode]
+            by_mode[mode] = getattr(L.lib(), entry + "_workspace_bytes")(ctypes.byref(cfg))
+        self.modes = tuple(m for m, n in by_mode.items() if n)
+        nbytes = self.workspace_bytes = max(by_mode.values())
+        if nbytes == 0:
+            raise ValueError(f"{self.ENTRY} and {self.ENTRY_CONST} refuse this configuration")
+        # zeroed once: the loss kernel's partial sums (every step leaves them zeroed)
+        self.workspace = aligned_workspace(nbytes, dev, zero=True)
+        self.t_vals, self.u_vals = tables(cfg, io, dev)
+        # both networks' gradients back to back in one allocation, a GRAD_TAIL behind each (functional._mlp_backward_launch's
+        # layout, which FlatAdam.step walks as one run per network); the backward writes every gradient entry and [0] of the
+        # tail, the rest of the tail is never read
+        n24 = L.N_PARAM_TENSORS
+        sizes = [sum(o._flat[0]['sizes'][first:first + n24]) + Fn.GRAD_TAIL for o, first in zip(opts, firsts)]
+        self.grad_block = torch.zeros(sum(sizes), device=dev, dtype=torch.float32)
+        self.slots = (_NetSlot(nets[0], opts[0], self.grad_block[:sizes[0]], io.coarse, nets, firsts[0], launches),
+                      _NetSlot(nets[1], opts[1], self.grad_block[sizes[0]:], io.fine, nets, firsts[1], launches))
+        self._refs = (ctypes.byref(cfg), ctypes.byref(io), ctypes.byref(args), ctypes.c_void_p(self.workspace.data_ptr()))
+
+    def _step(self, mode):
+        """Enqueue the step the structs describe through `mode`'s entry; leave on the host what FlatAdam.step would."""
+        entry = self.ENTRY_CONST if mode == "constant" else self.ENTRY
+        cfg, io, args, ws = self._refs
+        L.check(getattr(L.lib(), entry)(cfg, io, args, ws, self.workspace_bytes, L.stream()), entry)
+        self.slots[0].advance()
+        self.slots[1].advance()
+
+
+class StepPlan(_Plan):
     """kind "view": rays of one view per step (TrainStep.step_view); "bank": of `bank`, a train.RayBank (step_batch).
     nets = (coarse, fine), opts = (coarse optimizer, fine optimizer): native networks of one 16-bit precision, each
     stepped by a FlatAdam with one flat group over exactly its 24 parameters (supported() says whether they are)."""
+    ENTRY, ENTRY_CONST = "plnerf_train_step", "plnerf_train_step_const"
 
     @staticmethod
     def supported(nets, opts):
-        for net, opt in zip(nets, opts):
-            if not (isinstance(opt, FlatAdam) and len(opt.param_groups) == 1 and len(opt._flat) == 1 and opt._flat[0] is not None):
-                return False
-            group = opt.param_groups[0]
-            ps, plist = group['params'], net.param_list()
-            if len(ps) != len(plist) or any(a is not b for a, b in zip(ps, plist)):
-                return False
-            if group.get('weight_decay', 0) or group.get('amsgrad') or group.get('maximize'):
-                return False
-            if any(not (isinstance(g, torch.Tensor) or any(g is n for n in nets)) for g in opt.guards):
-                return False
-        return opts[0].param_groups[0]['betas'] == opts[1].param_groups[0]['betas'] and \
+        return all(_flat_adam_over(opt, net.param_list(), nets) for net, opt in zip(nets, opts)) and \
+            opts[0].param_groups[0]['betas'] == opts[1].param_groups[0]['betas'] and \
             opts[0].param_groups[0]['eps'] == opts[1].param_groups[0]['eps']
 
     def __init__(self, kw, nets, opts, kind, max_rays, H, W, K, near, far, seed, bank=None):
-        coarse, fine = nets
-        dev = coarse.param_list()[0].device
-        self.device = dev
         self.kind = kind
         self.bank = bank
-        cfg = self.config = L.StepConfig()
-        cfg.max_rays, cfg.n_samples, cfg.n_importance = int(max_rays), int(kw["N_samples"]), int(kw["N_importance"])
-        cfg.mode, cfg.color_mode = L.MODE["linear"], L.COLOR[kw["color_mode"]]
-        cfg.lindisp, cfg.perturb = int(bool(kw.get("lindisp", False))), int(kw.get("perturb", 0.) > 0.)
-        cfg.white_bkgd, cfg.farcolorfix = int(bool(kw.get("white_bkgd", False))), int(bool(kw.get("farcolorfix", False)))
-        cfg.raw_noise_std = float(kw.get("raw_noise_std", 0.))
-        cfg.zero_tol, cfg.epsilon = float(kw.get("zero_tol", 1e-4)), float(kw.get("epsilon", 1e-3))
-        cfg.ndc, cfg.ndc_focal = int(bool(kw.get("ndc", True))), float(K[0][0])
-        cfg.H, cfg.W = int(H), int(W)
-        cfg.fx, cfg.fy, cfg.cx, cfg.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
-        cfg.near, cfg.far = float(near), float(far)
-        cfg.precision, cfg.fwd_kernel = L.PRECISION[coarse.precision], L.FWD_KERNEL
-        cfg.input_ch, cfg.input_ch_views = int(coarse.input_ch), int(coarse.hip_view_ch)
+        cfg = L.StepConfig()
+        fill_sampling(cfg, kw, max_rays, nets[0], seed)      # (mode: _build's queries and every run() write it)
+        fill_pinhole(cfg, kw.get("ndc", True), K, H, W, near, far)
+        fill_adam(cfg, opts[0].param_groups[0])
         cfg.ray_source = L.STEP_RAYS_BANK if kind == "bank" else L.STEP_RAYS_VIEW
         cfg.n_views = len(bank.i_train) if bank is not None else 0
-        group = opts[0].param_groups[0]
-        cfg.beta1, cfg.beta2, cfg.adam_eps = float(group['betas'][0]), float(group['betas'][1]), float(group['eps'])
-        cfg.seed = int(seed)
         cfg.bank_seed = int(bank.seed) if bank is not None else 0
-        # ONE workspace for both entries (plnerf_train_step and its constant-mode sibling plnerf_train_step_const carve it
-        # alike): a constant_init warm-up switches entries between steps on the same memory and the same gradient buffers.
-        # A query answers 0 for the mode its entry does not serve, and for a shape its kernels refuse (N_samples = 2).
-        by_mode = {}
-        for mode, query in (("linear", L.lib().plnerf_train_step_workspace_bytes),
-                            ("constant", L.lib().plnerf_train_step_const_workspace_bytes)):
-            cfg.mode = L.MODE[mode]
-            by_mode[mode] = query(ctypes.byref(cfg))
-        self.modes = tuple(m for m, n in by_mode.items() if n)
-        nbytes = max(by_mode.values())
-        if nbytes == 0:
-            raise ValueError("plnerf_train_step and plnerf_train_step_const refuse this configuration")
-        # zeroed once: the loss kernel's partial sums (every step leaves them zeroed)
-        raw = torch.zeros((nbytes + L.STEP_WORKSPACE_ALIGN) // 4 + 1, device=dev, dtype=torch.float32)
-        pad = (-raw.data_ptr()) % L.STEP_WORKSPACE_ALIGN
-        self.workspace = raw[pad // 4:]
-        self.workspace_bytes = nbytes
-        self.t_vals = Fn.cpu_linspace(cfg.n_samples, dev)
-        self.u_vals = Fn.cpu_linspace(cfg.n_importance, dev)
-        # both networks' gradients back to back in one allocation, a GRAD_TAIL behind each (functional._mlp_backward_launch's
-        # layout); the backward writes every gradient entry and [0] of the tail, the rest of the tail is never read
-        sizes = [sum(o._flat[0]['sizes']) + Fn.GRAD_TAIL for o in opts]
-        self.grad_block = torch.zeros(sum(sizes), device=dev, dtype=torch.float32)
-        io = self.io = L.StepIo()
-        self.slots = (_NetSlot(coarse, opts[0], self.grad_block[:sizes[0]], io.coarse, nets),
-                      _NetSlot(fine, opts[1], self.grad_block[sizes[0]:], io.fine, nets))
-        io.t_vals, io.u_vals = self.t_vals.data_ptr(), self.u_vals.data_ptr()
+        io, args = L.StepIo(), L.StepArgs()
+        self._build(cfg, io, args, nets, opts, (0, 0), 1)
         if bank is not None:
             io.views, io.poses, io.images = bank.views.data_ptr(), bank.poses.data_ptr(), bank.images.data_ptr()
             self.bank_ptrs = (io.views, io.poses, io.images)
-        self.args = L.StepArgs()
-        self.args.loss_scale = 1.0
-        self._refs = (ctypes.byref(cfg), ctypes.byref(io), ctypes.byref(self.args), ctypes.c_void_p(self.workspace.data_ptr()))
+        args.loss_scale = 1.0
 
     def current(self):
         """Does every address the structs hold still belong to the live objects?"""
@@ -222,113 +232,60 @@ class StepPlan:
         a.loss_scale = loss_scale
         loss4 = torch.empty(4, device=self.device)
         self.io.loss4 = loss4.data_ptr()
-        cfg, io, args, ws = self._refs
         self.config.mode = L.MODE[mode]
-        if mode == "constant":
-            L.check(L.lib().plnerf_train_step_const(cfg, io, args, ws, self.workspace_bytes, L.stream()),
-                    "plnerf_train_step_const")
-        else:
-            L.check(L.lib().plnerf_train_step(cfg, io, args, ws, self.workspace_bytes, L.stream()), "plnerf_train_step")
-        self.slots[0].advance()
-        self.slots[1].advance()
+        self._step(mode)
         return loss4
 
 
 def depth_plan_key(args, kw, max_rays, views, seed):
-    """Everything a DepthStepPlan's config is built from (the DepthViews by identity; current() watches their tensors)."""
+    """Everything a DepthStepPlan's config is built from (the DepthViews by identity; current() watches their tensors); the
+    sampling fields are the tuple the config is filled from."""
     g = lambda name, default: getattr(args, name, default)
-    return (int(max_rays), id(views), int(seed), int(kw["N_samples"]), int(kw["N_importance"]), kw["color_mode"],
-            bool(kw.get("lindisp", False)), kw.get("perturb", 0.) > 0., bool(kw.get("white_bkgd", False)),
-            float(kw.get("raw_noise_std", 0.)), float(kw.get("zero_tol", 1e-4)), float(kw.get("epsilon", 1e-3)),
-            bool(g("is_joint", False)), float(g("space_carving_weight", 0.)), float(g("space_carving_threshold", 0.0)),
-            L.FWD_KERNEL)
+    return (int(max_rays), id(views), int(seed), sampling(kw), bool(g("is_joint", False)),
+            float(g("space_carving_weight", 0.)), float(g("space_carving_threshold", 0.0)), L.FWD_KERNEL)
 
 
-class DepthStepPlan:
+class DepthStepPlan(_Plan):
     """The host side of plnerf_depth_train_step (include/plnerf_hip_depthstep.h), StepPlan's sibling for the depth loop:
     nets = (coarse, fine) stepped by ONE FlatAdam `opt` whose one flat group holds exactly their 48 parameters, coarse
     first (depth.create_nerf); `views` a depth.DepthViews; scale, shift: DEPTH_SCALES / DEPTH_SHIFTS [V, 1]; ss_grad,
     ss_m, ss_v [2, V]: their dense gradient and Adam moments.  The workspace is zeroed once (the loss kernel's partials);
     a step's rendered outputs are views of it (outputs()), valid until this plan's next step."""
+    ENTRY, ENTRY_CONST = "plnerf_depth_train_step", "plnerf_depth_train_step_const"
     CLIP_VALUE = 0.1      # clip_grad_value_ of run_nerf_sample_based_depth.py:1156
 
     @staticmethod
     def supported(nets, opt):
-        if not (isinstance(opt, FlatAdam) and len(opt.param_groups) == 1 and len(opt._flat) == 1 and opt._flat[0] is not None):
-            return False
-        group = opt.param_groups[0]
-        ps, plist = group['params'], list(nets[0].param_list()) + list(nets[1].param_list())
-        if len(ps) != len(plist) or any(a is not b for a, b in zip(ps, plist)):
-            return False
-        if group.get('weight_decay', 0) or group.get('amsgrad') or group.get('maximize'):
-            return False
-        return all(isinstance(g, torch.Tensor) or any(g is n for n in nets) for g in opt.guards)
+        return _flat_adam_over(opt, list(nets[0].param_list()) + list(nets[1].param_list()), nets)
 
     def __init__(self, args, kw, nets, opt, views, max_rays, seed, input_scale, scale, shift, ss_grad, ss_m, ss_v,
                  ss_betas=(0.9, 0.999), ss_eps=1e-8):
-        coarse, fine = nets
-        dev = coarse.param_list()[0].device
         g = lambda name, default: getattr(args, name, default)
-        self.device, self.views = dev, views
-        cfg = self.config = L.DepthStepConfig()
-        cfg.max_rays, cfg.n_samples, cfg.n_importance = int(max_rays), int(kw["N_samples"]), int(kw["N_importance"])
-        cfg.color_mode = L.COLOR[kw["color_mode"]]
-        cfg.lindisp, cfg.perturb = int(bool(kw.get("lindisp", False))), int(kw.get("perturb", 0.) > 0.)
-        cfg.white_bkgd = int(bool(kw.get("white_bkgd", False)))
-        cfg.raw_noise_std = float(kw.get("raw_noise_std", 0.))
-        cfg.zero_tol, cfg.epsilon = float(kw.get("zero_tol", 1e-4)), float(kw.get("epsilon", 1e-3))
+        self.views = views
+        cfg = L.DepthStepConfig()
+        fill_sampling(cfg, kw, max_rays, nets[0], seed)
+        fill_depth(cfg, input_scale, nets[0])
+        fill_adam(cfg, opt.param_groups[0])
         cfg.n_views, cfg.H, cfg.W, cfg.n_hyp = views.n_views, views.H, views.W, views.n_hyp
         cfg.pose_rows = int(views.poses.shape[1])
         cfg.near, cfg.far = float(views.near), float(views.far)
-        cfg.precision, cfg.fwd_kernel = L.PRECISION[coarse.precision], L.FWD_KERNEL
-        cfg.input_ch, cfg.input_ch_views = int(coarse.input_ch), int(coarse.hip_view_ch)
-        cfg.input_scale, cfg.density_beta = float(input_scale), float(coarse.density_beta)
         cfg.is_joint = int(bool(g("is_joint", False)))
         cfg.space_carving_weight = float(g("space_carving_weight", 0.))
         cfg.space_carving_threshold = float(g("space_carving_threshold", 0.0))
         cfg.clip_value = self.CLIP_VALUE
-        group = opt.param_groups[0]
-        cfg.beta1, cfg.beta2, cfg.adam_eps = float(group['betas'][0]), float(group['betas'][1]), float(group['eps'])
         cfg.ss_beta1, cfg.ss_beta2, cfg.ss_adam_eps = float(ss_betas[0]), float(ss_betas[1]), float(ss_eps)
-        cfg.seed = int(seed)
-        # one workspace for both entries (plnerf_depth_train_step_const carves it as the linear entry does, so the layout
-        # below serves either); a query answers 0 for a shape its kernels refuse
-        by_mode = {"linear": L.lib().plnerf_depth_train_step_workspace_bytes(ctypes.byref(cfg)),
-                 "constant": L.lib().plnerf_depth_train_step_const_workspace_bytes(ctypes.byref(cfg))}
-        self.modes = tuple(m for m, n in by_mode.items() if n)
-        nbytes = max(by_mode.values())
-        if nbytes == 0:
-            raise ValueError("plnerf_depth_train_step and plnerf_depth_train_step_const refuse this configuration")
-        raw = torch.zeros((nbytes + L.STEP_WORKSPACE_ALIGN) // 4 + 1, device=dev, dtype=torch.float32)
-        pad = (-raw.data_ptr()) % L.STEP_WORKSPACE_ALIGN
-        self.workspace = raw[pad // 4:]
-        self.workspace_bytes = nbytes
+        io = L.DepthStepIo()
+        # the flat group's two halves, which FlatAdam.step walks as two runs (one plnerf_adam_step launch each)
+        self._build(cfg, io, L.DepthStepArgs(), nets, (opt, opt), (0, L.N_PARAM_TENSORS), 2)
+        # (both entries carve the workspace alike, so one layout serves either)
+        entry = self.ENTRY if "linear" in self.modes else self.ENTRY_CONST
         self.layout = L.DepthStepViews()
-        if by_mode["linear"]:
-            L.check(L.lib().plnerf_depth_train_step_layout(ctypes.byref(cfg), ctypes.byref(self.layout)),
-                    "plnerf_depth_train_step_layout")
-        else:
-            L.check(L.lib().plnerf_depth_train_step_const_layout(ctypes.byref(cfg), ctypes.byref(self.layout)),
-                    "plnerf_depth_train_step_const_layout")
-        self.t_vals = Fn.cpu_linspace(cfg.n_samples, dev)
-        self.u_vals = Fn.cpu_linspace(cfg.n_importance, dev)
-        # both networks' gradients back to back in one allocation, a GRAD_TAIL behind each: functional._mlp_backward_launch's
-        # layout, which FlatAdam.step walks as two runs (one plnerf_adam_step launch each)
-        fl = opt._flat[0]
-        n24 = L.N_PARAM_TENSORS
-        sizes = [sum(fl['sizes'][:n24]) + Fn.GRAD_TAIL, sum(fl['sizes'][n24:]) + Fn.GRAD_TAIL]
-        self.grad_block = torch.zeros(sum(sizes), device=dev, dtype=torch.float32)
-        io = self.io = L.DepthStepIo()
-        self.slots = (_NetSlot(coarse, opt, self.grad_block[:sizes[0]], io.coarse, nets, first=0, launches=2),
-                      _NetSlot(fine, opt, self.grad_block[sizes[0]:], io.fine, nets, first=n24, launches=2))
-        io.t_vals, io.u_vals = self.t_vals.data_ptr(), self.u_vals.data_ptr()
+        L.check(getattr(L.lib(), entry + "_layout")(ctypes.byref(cfg), ctypes.byref(self.layout)), entry + "_layout")
         self.tensors = (views.images, views.hypotheses, views.valid, views.poses, views.intrinsics, scale, shift, ss_grad,
                         ss_m, ss_v)
         self.ptrs = self._tensor_ptrs()
         (io.images, io.hyp, io.valid, io.poses, io.intrinsics, io.scale, io.shift, io.ss_grad, io.ss_exp_avg,
          io.ss_exp_avg_sq) = self.ptrs
-        self.args = L.DepthStepArgs()
-        self._refs = (ctypes.byref(cfg), ctypes.byref(io), ctypes.byref(self.args), ctypes.c_void_p(self.workspace.data_ptr()))
 
     def _tensor_ptrs(self):
         v = self.views
@@ -355,15 +312,7 @@ class DepthStepPlan:
         a.carve, a.ss_step, a.ss_lr, a.ss_adam_step = int(carve), int(ss_step), ss_lr, ss_adam_step
         loss5 = torch.empty(5, device=self.device)
         self.io.loss5 = loss5.data_ptr()
-        cfg, io, args, ws = self._refs
-        if mode == "constant":
-            L.check(L.lib().plnerf_depth_train_step_const(cfg, io, args, ws, self.workspace_bytes, L.stream()),
-                    "plnerf_depth_train_step_const")
-        else:
-            L.check(L.lib().plnerf_depth_train_step(cfg, io, args, ws, self.workspace_bytes, L.stream()),
-                    "plnerf_depth_train_step")
-        self.slots[0].advance()
-        self.slots[1].advance()
+        self._step(mode)
         return loss5
 
     def view_of(self, name, shape, dtype=torch.float32):

@@ -303,6 +303,29 @@ def test_unsupported_configurations_raise(P):
             P.DepthViewRenderer(bad, H, W, 50, NEAR, FAR)
 
 
+def test_moved_parameters_are_refused_on_the_host(P):
+    """A renderer holds the parameters' addresses: when one has moved, enqueue() raises before anything is enqueued, and a
+    new renderer on the same networks renders the same frame."""
+    kw = _kwargs("f16x3", N_samples=8, N_importance=8)
+    vr = _renderer(P, kw, 16, 9, Hv=4, Wv=6)
+    first = {k: v.clone() for k, v in _frame(vr, 4)[0].items()}
+    p = kw["network_fine"].param_list()[3]
+    old = p.data
+    try:
+        p.data = p.data.clone()
+        assert not vr.current()
+        with pytest.raises(RuntimeError, match="DepthViewRenderer: the networks' parameters moved"):
+            vr.enqueue(_pose(), _intrinsic(), step=4)
+        fresh = _renderer(P, kw, 16, 9, Hv=4, Wv=6)
+        assert fresh.current()
+        again = _frame(fresh, 4)[0]
+        for name in PLANES + ("pred_hyp",):
+            assert same_bits(again[name], first[name]), name      # (torch.equal, but for a disparity that is NaN in both)
+    finally:
+        p.data = old      # (the networks are shared with the other tests)
+    assert vr.current()
+
+
 # ----------------------------------------------------------------------------- independence of the chunking
 def _snapshot(vr):
     planes = {k: v.clone() for k, v in vr.planes.items()}

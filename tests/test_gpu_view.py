@@ -275,6 +275,30 @@ def test_unsupported_configurations_raise(P):
             P.ViewRenderer(bad, H_VIEW, W_VIEW, K_VIEW, 50, 2.0, 6.0)
 
 
+def test_moved_parameters_are_refused_on_the_host(P):
+    """A renderer holds the parameters' addresses: when one has moved, enqueue() raises before anything is enqueued, and a
+    new renderer on the same networks renders the same frame."""
+    kw = _kwargs("f16x3", N_samples=8, N_importance=8, **CASES["linear_left_u_vals"][0])
+    c2w = _pose()
+    vr = _renderer(P, kw, 4, 6, K_VIEW, 16, 2.0, 6.0, 9)
+    first = {k: v.clone() for k, v in _frame(vr, c2w, 4)[0].items()}
+    p = kw["network_fine"].param_list()[3]
+    old = p.data
+    try:
+        p.data = p.data.clone()
+        assert not vr.current()
+        with pytest.raises(RuntimeError, match="ViewRenderer: the networks' parameters moved"):
+            vr.enqueue(c2w, step=4)
+        fresh = _renderer(P, kw, 4, 6, K_VIEW, 16, 2.0, 6.0, 9)
+        assert fresh.current()
+        again = _frame(fresh, c2w, 4)[0]
+        for name in PLANES:
+            assert same_bits(again[name], first[name]), name      # (torch.equal, but for a disparity that is NaN in both)
+    finally:
+        p.data = old      # (the networks are shared with the other tests)
+    assert vr.current()
+
+
 # ----------------------------------------------------------------------------- independence of the chunking
 def _snapshot(vr):
     return {k: v.clone() for k, v in vr.planes.items()}, vr.rgb8.clone(), vr.depth16.clone()
