@@ -8,10 +8,12 @@
 //
 // One wavefront owns one ray.  weights, tau, T and the cdf never leave the CU: they are LDS rows of the wave (the
 // separate launches write them to HBM for the next launch to read back).  HBM sees raw, z and u in, the coarse maps,
-// z_fine, pts and z_std out: algorithmic bytes per ray 20 S + 4 N (+44) in, 16 (S + N) + 32 out.  Every device
-// function is the one the separate kernels use (ray_dev.h), so the results are bit-identical to
-// plnerf_quad_fwd -> plnerf_sample_pl -> plnerf_merge_sort -> plnerf_ray_points
-// (tests/test_gpu_parity.py::test_fused_coarse_epilogue_equals_separate_launches).
+// z_fine, pts and z_std out: algorithmic bytes per ray 20 S + 4 N (+44) in, 16 (S + N) + 32 out.  The scan, the
+// element rule and map write, the cdfs, each draw's inversion, the general sort arm and the positions are the bodies
+// the separate kernels run (ray_fwd_dev.h, over ray_dev.h's leaves), so the results are bit-identical to
+// plnerf_quad_fwd -> plnerf_sample_pl -> plnerf_merge_sort -> plnerf_ray_points by construction
+// (guarded by tests/test_gpu_step.py::test_fused_coarse_epilogue_equals_separate_launches).  This kernel's own: the
+// LDS layout, z_std, and the rank merge of two ascending runs, which no separate launch has.
 //
 // Piecewise-constant mode (MODE = PLNERF_MODE_CONSTANT: the vanilla-NeRF baseline, `constant_init`, the depth script's
 // constant configuration) is the same kernel with compute_weights (run_plnerf.py:504-513) as the quadrature and sample_pdf
@@ -20,14 +22,14 @@
 // (tests/test_gpu_const_epilogue.py); entry points in include/plnerf_hip_constepi.h.
 #include "common.h"
 #include "philox.h"
-#include "ray_dev.h"
+#include "ray_fwd_dev.h"
 #include "../../include/plnerf_hip_constepi.h"
 
 using namespace plnerf;
 
 namespace {
 
-constexpr int WAVES = 4;
+constexpr int WAVES = RAY_WAVES;
 
 struct EpiArgs {
     RayIn in;
@@ -39,13 +41,7 @@ struct EpiArgs {
     int color_mode, white_bkgd, farcolorfix;
     float zero_tol, eps;
     int lds_stride;
-    float* rgb_map;
-    float* disp_map;
-    float* acc_map;
-    float* depth_map;
-    float* weights;          // optional [R, S+1] (constant mode: [R, S])
-    float* tau;              // optional [R, S+2]
-    float* T;                // optional [R, S+2]
+    QuadOut out;             // the coarse maps; optional weights [R, S+1] (constant mode: [R, S]), tau, T [R, S+2]
     float* z_fine;           // [R, S+N]
     float* pts;              // [R, S+N, 3]
     float* z_std;            // [R]
@@ -67,12 +63,11 @@ template <int KPL, bool HYP, int KS = KPL, int MODE = PLNERF_MODE_LINEAR>
 __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
     constexpr bool LINEAR = MODE == PLNERF_MODE_LINEAR;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
-    const int S = a.S, K = S + 2, n = LINEAR ? S + 1 : S, N = a.N, NF = S + N;
-    float* zk = smem + (size_t)wave * a.lds_stride;   // K knots [near, z, far]
+    const RayWave rw(a.R);
+    const int lane = rw.lane, ray = rw.ray;
+    const bool live = rw.live;
+    const int S = a.S, K = S + 2, N = a.N, NF = S + N;
+    float* zk = smem + (size_t)rw.wave * a.lds_stride;   // K knots [near, z, far]
     float* tau = zk + K;                               // K
     float* col = tau + K;                              // 3 S
     float* Tr = col + 3 * S;                           // K  (constant mode: the sampler's S - 2 weights)
@@ -82,78 +77,26 @@ __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
     load_ray(a.in, ray, lane, zk, tau, col, dnorm);
     __syncthreads();
 
-    // ---- quadrature (quad_fwd_kernel's loop) with the cdf's running sum riding along ----
-    double carry = 1.0, ccarry = 0.0;
-    double sr = 0, sg = 0, sb = 0, sd = 0, sa = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool valid = i < n;
-        float seg = 0.f, e = 1.f, f = 1.f;
-        if (valid) interval<MODE>(i, S, zk, tau, dnorm, seg, e, f);
-        const double incl = wave_incl_prod((double)f);
-        double excl = __shfl_up(incl, 1);
-        if (lane == 0) excl = 1.0;
-        const float Ti = (float)(carry * excl);
-        const float Tn = (float)(carry * incl);
-        carry = carry * __shfl(incl, 63);
+    // ---- quadrature (quad_scan, as quad_fwd_kernel runs it) with the linear cdf's running sum riding along ----
+    QuadSums sums;
+    [[maybe_unused]] double ccarry = 0.0;
+    quad_scan<MODE>(S, zk, tau, dnorm, lane, [&](const int i, const bool valid, const float e, float, const float Ti, const float Tn) {
         float w = 0.0f;
         if (valid) {
-            w = (1.0f - e) * Ti;
-            sr += (double)(w * elem_colour<MODE>(i, 0, S, col, a.color_mode, a.farcolorfix));
-            sg += (double)(w * elem_colour<MODE>(i, 1, S, col, a.color_mode, a.farcolorfix));
-            sb += (double)(w * elem_colour<MODE>(i, 2, S, col, a.color_mode, a.farcolorfix));
-            sd += (double)(w * elem_depth<MODE>(i, zk));
-            sa += (double)w;
+            w = quad_element<MODE>(sums, a.out, ray, live, i, e, Ti, Tn, S, zk, col, a.color_mode, a.farcolorfix);
             if constexpr (LINEAR) Tr[i + 1] = Tn;
             else if (i >= 1 && i < S - 1) Tr[i - 1] = w + 1e-5f;      // sample_pdf's weights[..., 1:-1] + 1e-5
-            if (live) {
-                if (a.weights) a.weights[(size_t)ray * n + i] = w;
-                if (LINEAR && a.T) a.T[(size_t)ray * K + i + 1] = Tn;
-            }
         }
-        if constexpr (LINEAR) {
-            // cdf = [0, cumsum(weights)] (fp64 running sum, each entry rounded to fp32), as sample_pl_kernel builds it
-            const double cincl = wave_incl_sum((double)w);
-            if (valid) cdf[i + 1] = (float)(ccarry + cincl);
-            ccarry = ccarry + __shfl(cincl, 63);
-        }
-    }
-    if (LINEAR && live) {
-        if (a.T && lane == 0) a.T[(size_t)ray * K] = 1.0f;
-        if (a.tau)
-            for (int s = lane; s < K; s += 64) a.tau[(size_t)ray * K + s] = tau[s];
-    }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sd = wave_sum(sd); sa = wave_sum(sa);
-    if (live && lane == 0) {
-        const float acc = (float)sa, depth = (float)sd;
-        float r = (float)sr, g = (float)sg, b = (float)sb;
-        if (a.white_bkgd) {
-            const float bg = 1.0f - acc;
-            r += bg; g += bg; b += bg;
-        }
-        a.rgb_map[3 * ray + 0] = r;
-        a.rgb_map[3 * ray + 1] = g;
-        a.rgb_map[3 * ray + 2] = b;
-        a.depth_map[ray] = depth;
-        a.acc_map[ray] = acc;
-        a.disp_map[ray] = 1.0f / tmax(1e-10f, depth / acc);
-    }
+        if constexpr (LINEAR) cdf_scan_step(i, valid, w, ccarry, cdf);      // (cdf_linear_rows' step: w is in a register here)
+    });
+    quad_write_maps<MODE>(sums, a.out, ray, live, lane, S, tau, a.white_bkgd);
     __syncthreads();
     const int B = S - 1;          // (constant mode) bins z_mid = cdf entries
     if constexpr (LINEAR) {
-        if (lane == 0) { Tr[0] = 1.0f; cdf[0] = 0.0f; cdf[K - 1] = 1.0f; }
+        if (lane == 0) Tr[0] = 1.0f;
+        cdf_linear_ends(cdf, K, lane);
     } else {
-        // cdf = [0, cumsum(pdf)], pdf = w' / sum(w') (sample_const_kernel's: torch.sum's order, IEEE division, fp64 running
-        // sum rounded per entry; the last entry is what the sum gives, not forced to 1)
-        const float total = torch_row_sum(Tr, B - 1, lane);
-        for (int base = 0; base < B - 1; base += 64) {
-            const int j = base + lane;
-            const float pdf = (j < B - 1) ? Tr[j] / total : 0.0f;
-            const double cincl = wave_incl_sum((double)pdf);
-            if (j < B - 1) cdf[j + 1] = (float)(ccarry + cincl);
-            ccarry = ccarry + __shfl(cincl, 63);
-        }
-        if (lane == 0) cdf[0] = 0.0f;
+        cdf_const_rows(Tr, B - 1, lane, cdf);
         if constexpr (HYP) {
             if (live && a.bins_out)
                 for (int j = lane; j < B; j += 64) a.bins_out[(size_t)ray * B + j] = 0.5f * (zk[j + 2] + zk[j + 1]);
@@ -161,38 +104,20 @@ __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
     }
     __syncthreads();
 
-    // ---- importance samples (sample_pl_kernel's / sample_const_kernel's loop), clamped to [near, far] ----
+    // ---- importance samples (invert_pl / invert_const, as sample_pl_kernel / sample_const_kernel run them), clamped to
+    // [near, far]; unlike the separate samplers a dead wave draws too: barriers follow ----
     const float lo = zk[0], hi = zk[K - 1];
-    [[maybe_unused]] const float zt = a.zero_tol, eps = a.eps;
     double ssum = 0.0;
     for (int k = lane; k < N; k += 64) {
         const float u = a.u ? a.u[(size_t)ray * a.u_row_stride + k] : rng_uniform(a.rng, a.rng.ray_id0 + ray, k);
         int ind;
         float out;
         if constexpr (LINEAR) {
-            ind = upper_bound(cdf, K, u);
-            const int below = ind - 1 > 0 ? ind - 1 : 0;
-            const int above = ind < K - 1 ? ind : K - 1;
-            const float s0 = zk[below], s1 = zk[above];
-            const float T0 = Tr[below];
-            const float tau0 = tau[below], tau1 = tau[above];
-            const int di = below < S ? below : S;
-            const float d = tau[di + 1] - tau[di];
-            out = (d < zt && d > -zt) ? s0 : -1.0f;
-            const bool rising = d >= zt;
-            if (rising || d <= -zt) out = invert_segment(s0, s1, T0, tau0, tau1, u, eps, rising);      // (one evaluation, operands selected per lane)
-            if (out != out) out = s0;
+            [[maybe_unused]] float T0, tau0, s0;
+            out = invert_pl(cdf, zk, tau, Tr, S, u, a.zero_tol, a.eps, ind, T0, tau0, s0);
         } else {
-            ind = upper_bound(cdf, B, u);
-            const int below = ind - 1 > 0 ? ind - 1 : 0;
-            const int above = ind < B - 1 ? ind : B - 1;
-            const float c0 = cdf[below], c1 = cdf[above];
-            float denom = c1 - c0;
-            if (denom < 1e-5f) denom = 1.0f;
-            const float t = (u - c0) / denom;
-            // z_mid = .5 * (z[1:] + z[:-1]) of the two bins
-            const float b0 = 0.5f * (zk[below + 2] + zk[below + 1]), b1 = 0.5f * (zk[above + 2] + zk[above + 1]);
-            out = b0 + t * (b1 - b0);
+            // z_mid = .5 * (z[1:] + z[:-1])
+            out = invert_const(cdf, B, u, [&](const int j) { return 0.5f * (zk[j + 2] + zk[j + 1]); }, ind);
         }
         if constexpr (HYP) {
             if (live) {
@@ -258,16 +183,8 @@ __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
             const int p = 64 * r + lane;
             rank_z[r] = p < S ? p + count_lt(skey, N, zkey[p]) : -1;
         }
-    } else {
-#pragma unroll
-        for (int r = 0; r < KPL; ++r) {
-            const int p = 64 * r + lane;
-            uint32_t key = 0xFFFFFFFFu;
-            if (p < S) key = sort_key(zk[p + 1]);
-            else if (p < NF) key = sort_key(smp[p - S]);
-            x[r] = key;
-        }
-        bitonic_sort_regs<KPL>(x, lane);
+    } else {      // merge_sort_kernel's network (the samples are clamped already)
+        sort_row_regs<KPL>(x, NF, lane, [&](const int p) { return p < S ? zk[p + 1] : smp[p - S]; });
     }
     float* zs = col;                  // NF <= 3 S + K + K + N floats from col on (col, Tr, cdf, smp are contiguous)
     // ONE barrier for both arms (`merge` is decided per wave = per ray: a barrier inside each arm was reached at different
@@ -282,38 +199,14 @@ __global__ __launch_bounds__(256) void coarse_epilogue_kernel(const EpiArgs a) {
         for (int r = 0; r < KS; ++r)
             if (64 * r + lane < N) zs[rank_s[r]] = sort_unkey(xs[r]);
     } else {
-#pragma unroll
-        for (int r = 0; r < KPL; ++r) {
-            const int p = 64 * r + lane;
-            if (p < NF) zs[p] = sort_unkey(x[r]);
-        }
+        store_row_regs<KPL>(x, NF, lane, [&](const int p, const float v) { zs[p] = v; });
     }
     __syncthreads();
     if (live)
         for (int p = lane; p < NF; p += 64) a.z_fine[(size_t)ray * NF + p] = zs[p];
     if (!live) return;
     // ---- positions of the merged samples ----
-    const float o[3] = {a.rays_o[3 * (size_t)ray], a.rays_o[3 * (size_t)ray + 1], a.rays_o[3 * (size_t)ray + 2]};
-    const float dd[3] = {a.in.rays_d[3 * (size_t)ray], a.in.rays_d[3 * (size_t)ray + 1], a.in.rays_d[3 * (size_t)ray + 2]};
-    float* prow = a.pts + (size_t)ray * 3 * NF;
-    if ((3 * NF) % 4 == 0 && ((uintptr_t)a.pts & 15) == 0) {
-        for (int q = lane; q < 3 * NF / 4; q += 64) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int e = 4 * q + k, si = e / 3, c = e - 3 * si;
-                const float oc = c == 0 ? o[0] : (c == 1 ? o[1] : o[2]);
-                const float dc = c == 0 ? dd[0] : (c == 1 ? dd[1] : dd[2]);
-                v[k] = oc + dc * zs[si];
-            }
-            reinterpret_cast<float4*>(prow)[q] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    } else {
-        for (int e = lane; e < 3 * NF; e += 64) {
-            const int si = e / 3, c = e - 3 * si;
-            prow[e] = (c == 0 ? o[0] : (c == 1 ? o[1] : o[2])) + (c == 0 ? dd[0] : (c == 1 ? dd[1] : dd[2])) * zs[si];
-        }
-    }
+    ray_positions(a.rays_o, a.in.rays_d, ray, zs, NF, a.pts + (size_t)ray * 3 * NF, lane);
 }
 
 template <int KPL, bool HYP = false, int KS = KPL, int MODE = PLNERF_MODE_LINEAR>
@@ -368,8 +261,8 @@ extern "C" int plnerf_coarse_epilogue(const float* raw, const float* z, const fl
     a.rng = RngArgs{(uint32_t)seed, (uint32_t)(seed >> 32), 1u, step, ray_id0, u ? 0 : 1};
     a.R = R; a.S = S; a.N = N; a.color_mode = color_mode; a.white_bkgd = white_bkgd; a.farcolorfix = farcolorfix;
     a.zero_tol = zero_tol; a.eps = epsilon;
-    a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
-    a.weights = weights; a.tau = tau; a.T = T; a.z_fine = z_fine; a.pts = pts; a.z_std = z_std;
+    a.out = QuadOut{rgb_map, disp_map, acc_map, depth_map, weights, tau, T};
+    a.z_fine = z_fine; a.pts = pts; a.z_std = z_std;
     a.lds_stride = lds_row(S, N);
     const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
     if (lds > 160 * 1024) return PLNERF_ERANGE;
@@ -400,8 +293,8 @@ extern "C" int plnerf_fine_epilogue(const float* raw, const float* z, const floa
     a.rng = RngArgs{(uint32_t)seed, (uint32_t)(seed >> 32), 4u, step, ray_id0, u ? 0 : 1};
     a.R = R; a.S = S; a.N = N; a.color_mode = color_mode; a.white_bkgd = white_bkgd; a.farcolorfix = farcolorfix;
     a.zero_tol = zero_tol; a.eps = epsilon;
-    a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
-    a.weights = weights; a.tau = tau; a.T = T; a.z_std = z_std;
+    a.out = QuadOut{rgb_map, disp_map, acc_map, depth_map, weights, tau, T};
+    a.z_std = z_std;
     a.samples = samples; a.inds = inds; a.u_out = u_out;
     a.lds_stride = lds_row(S, N);
     const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
@@ -430,8 +323,8 @@ extern "C" int plnerf_coarse_epilogue_const(const float* raw, const float* z, co
     a.rays_o = rays_o; a.u = u; a.u_row_stride = u_row_stride;
     a.rng = RngArgs{(uint32_t)seed, (uint32_t)(seed >> 32), 1u, step, ray_id0, u ? 0 : 1};
     a.R = R; a.S = S; a.N = N; a.white_bkgd = white_bkgd;
-    a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
-    a.weights = weights; a.z_fine = z_fine; a.pts = pts; a.z_std = z_std;
+    a.out = QuadOut{rgb_map, disp_map, acc_map, depth_map, weights, nullptr, nullptr};
+    a.z_fine = z_fine; a.pts = pts; a.z_std = z_std;
     a.lds_stride = lds_row(S, N);
     const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
     if (lds > 160 * 1024) return PLNERF_ERANGE;
@@ -457,8 +350,8 @@ extern "C" int plnerf_fine_epilogue_const(const float* raw, const float* z, cons
     a.u = u; a.u_row_stride = u_row_stride;
     a.rng = RngArgs{(uint32_t)seed, (uint32_t)(seed >> 32), 4u, step, ray_id0, u ? 0 : 1};      // (stream 4: as plnerf_fine_epilogue)
     a.R = R; a.S = S; a.N = N; a.white_bkgd = white_bkgd;
-    a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
-    a.weights = weights; a.z_std = z_std;
+    a.out = QuadOut{rgb_map, disp_map, acc_map, depth_map, weights, nullptr, nullptr};
+    a.z_std = z_std;
     a.samples = samples; a.inds = inds; a.u_out = u_out; a.bins_out = bins_out;
     a.lds_stride = lds_row(S, N);
     const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);

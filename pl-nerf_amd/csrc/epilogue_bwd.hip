@@ -30,12 +30,9 @@ struct FineConstBwdArgs {
 __global__ __launch_bounds__(256) void fine_epilogue_const_bwd_kernel(const FineConstBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ unsigned wave_max_bits[RAY_WAVES];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * RAY_WAVES + wave;
-    const bool live = ray < a.q.R;
-    if (!live) ray = a.q.R - 1;
-    const int S = a.q.S, n = S - 2;
-    float* gin = smem + (size_t)wave * a.q.lds_stride;
+    const RayWave rw(a.q.R);
+    const int lane = rw.lane, ray = rw.ray, S = a.q.S, n = S - 2;
+    float* gin = smem + (size_t)rw.wave * a.q.lds_stride;
     float* row = gin + a.gin_floats;
     float total, dot;
     sample_const_bwd_rows(a.s, ray, lane, row, total, dot);
@@ -43,7 +40,7 @@ __global__ __launch_bounds__(256) void fine_epilogue_const_bwd_kernel(const Fine
     for (int i = lane; i < n; i += 64) gin[i + 1] = (row[i] - dot) / total;
     if (lane == 0) { gin[0] = 0.0f; gin[S - 1] = 0.0f; }
     __syncthreads();      // the sampler's rows are read: the quadrature's may overwrite them
-    quad_bwd_rows<PLNERF_MODE_CONSTANT>(a.q, ray, live, wave, lane, row, wave_max_bits, gin);
+    quad_bwd_rows<PLNERF_MODE_CONSTANT>(a.q, ray, rw.live, rw.wave, lane, row, wave_max_bits, gin);
 }
 
 }  // namespace

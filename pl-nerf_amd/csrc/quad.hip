@@ -18,65 +18,22 @@ constexpr int WAVES = RAY_WAVES;  // rays per 256-thread workgroup
 template <int MODE>
 __global__ __launch_bounds__(256) void quad_fwd_kernel(QuadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
-    const int S = a.S;
-    float* zk = smem + wave * a.lds_stride;
+    const RayWave rw(a.R);
+    const int lane = rw.lane, ray = rw.ray, S = a.S;
+    const bool live = rw.live;
+    float* zk = smem + rw.wave * a.lds_stride;
     float* tau = zk + (S + 2);
     float* col = tau + (S + 2);
     float dnorm;
     load_ray(RayIn{a.raw, a.z, a.near, a.far, a.rays_d, a.noise, a.S}, ray, lane, zk, tau, col, dnorm);
     __syncthreads();
 
-    const int n = (MODE == PLNERF_MODE_LINEAR) ? S + 1 : S;
-    double carry = 1.0;
-    double sr = 0, sg = 0, sb = 0, sd = 0, sa = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool valid = i < n;
-        float seg = 0.f, e = 1.f, f = 1.f;
-        if (valid) interval<MODE>(i, S, zk, tau, dnorm, seg, e, f);
-        const double incl = wave_incl_prod((double)f);
-        double excl = __shfl_up(incl, 1);
-        if (lane == 0) excl = 1.0;
-        const float Ti = (float)(carry * excl);
-        const float Tn = (float)(carry * incl);
-        carry = carry * __shfl(incl, 63);
-        if (valid) {
-            const float w = (1.0f - e) * Ti;
-            sr += (double)(w * elem_colour<MODE>(i, 0, S, col, a.color_mode, a.farcolorfix));
-            sg += (double)(w * elem_colour<MODE>(i, 1, S, col, a.color_mode, a.farcolorfix));
-            sb += (double)(w * elem_colour<MODE>(i, 2, S, col, a.color_mode, a.farcolorfix));
-            sd += (double)(w * elem_depth<MODE>(i, zk));
-            sa += (double)w;
-            if (live) {
-                if (a.weights) a.weights[(size_t)ray * n + i] = w;
-                if (MODE == PLNERF_MODE_LINEAR && a.T) a.T[(size_t)ray * (S + 2) + i + 1] = Tn;
-            }
-        }
-    }
-    if (MODE == PLNERF_MODE_LINEAR && live) {
-        if (a.T && lane == 0) a.T[(size_t)ray * (S + 2)] = 1.0f;
-        if (a.tau)
-            for (int s = lane; s < S + 2; s += 64) a.tau[(size_t)ray * (S + 2) + s] = tau[s];
-    }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sd = wave_sum(sd); sa = wave_sum(sa);
-    if (live && lane == 0) {
-        const float acc = (float)sa, depth = (float)sd;
-        float r = (float)sr, g = (float)sg, b = (float)sb;
-        if (a.white_bkgd) {
-            const float bg = 1.0f - acc;
-            r += bg; g += bg; b += bg;
-        }
-        a.rgb_map[3 * ray + 0] = r;
-        a.rgb_map[3 * ray + 1] = g;
-        a.rgb_map[3 * ray + 2] = b;
-        a.depth_map[ray] = depth;
-        a.acc_map[ray] = acc;
-        a.disp_map[ray] = 1.0f / tmax(1e-10f, depth / acc);
-    }
+    // the scan, its element rule and the map write: ray_fwd_dev.h
+    QuadSums sums;
+    quad_scan<MODE>(S, zk, tau, dnorm, lane, [&](const int i, const bool valid, const float e, float, const float Ti, const float Tn) {
+        if (valid) quad_element<MODE>(sums, a.out, ray, live, i, e, Ti, Tn, S, zk, col, a.color_mode, a.farcolorfix);
+    });
+    quad_write_maps<MODE>(sums, a.out, ray, live, lane, S, tau, a.white_bkgd);
 }
 
 // Backward: quad_bwd_rows (ray_bwd_dev.h).
@@ -84,11 +41,8 @@ template <int MODE>
 __global__ __launch_bounds__(256) void quad_bwd_kernel(QuadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ unsigned wave_max_bits[WAVES];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
-    quad_bwd_rows<MODE>(a, ray, live, wave, lane, smem + wave * a.lds_stride, wave_max_bits, nullptr);
+    const RayWave rw(a.R);
+    quad_bwd_rows<MODE>(a, rw.ray, rw.live, rw.wave, rw.lane, smem + rw.wave * a.lds_stride, wave_max_bits, nullptr);
 }
 
 int check_common(const float* raw, const float* z, const float* near, const float* far,
@@ -116,8 +70,7 @@ extern "C" int plnerf_quad_fwd(const float* raw, const float* z, const float* ne
     QuadArgs a{};
     a.raw = raw; a.z = z; a.near = near; a.far = far; a.rays_d = rays_d; a.noise = noise;
     a.R = R; a.S = S; a.color_mode = color_mode; a.white_bkgd = white_bkgd; a.farcolorfix = farcolorfix;
-    a.rgb_map = rgb_map; a.disp_map = disp_map; a.acc_map = acc_map; a.depth_map = depth_map;
-    a.weights = weights; a.tau = tau; a.T = T;
+    a.out = QuadOut{rgb_map, disp_map, acc_map, depth_map, weights, tau, T};
     a.lds_stride = ((5 * S + 4) + 3) & ~3;
     const size_t lds = (size_t)WAVES * a.lds_stride * sizeof(float);
     dim3 grid((R + WAVES - 1) / WAVES), block(WAVES * 64);

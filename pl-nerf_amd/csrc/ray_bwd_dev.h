@@ -4,11 +4,9 @@
 // Everything that includes this is built with -ffp-contract=off.
 #pragma once
 #include "common.h"
-#include "ray_dev.h"
+#include "ray_fwd_dev.h"
 
 namespace plnerf {
-
-constexpr int RAY_WAVES = 4;      // rays (= wavefronts) per 256-thread workgroup of every per-ray kernel
 
 struct QuadArgs {
     const float* raw;
@@ -20,14 +18,7 @@ struct QuadArgs {
     int R, S;
     int color_mode, white_bkgd, farcolorfix;
     int lds_stride;  // floats per wave
-    // forward outputs
-    float* rgb_map;
-    float* disp_map;
-    float* acc_map;
-    float* depth_map;
-    float* weights;
-    float* tau;
-    float* T;
+    QuadOut out;     // forward outputs
     // backward inputs / output
     const float* g_rgb;
     const float* g_depth;
@@ -91,17 +82,7 @@ __device__ __forceinline__ void quad_bwd_rows(const QuadArgs& a, const int ray, 
     __syncthreads();
 
     // pass 1: forward scan, stash per-element terms
-    double carry = 1.0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool valid = i < n;
-        float seg = 0.f, e = 1.f, f = 1.f;
-        if (valid) interval<MODE>(i, S, zk, tau, dnorm, seg, e, f);
-        const double incl = wave_incl_prod((double)f);
-        double excl = __shfl_up(incl, 1);
-        if (lane == 0) excl = 1.0;
-        const float Ti = (float)(carry * excl);
-        carry = carry * __shfl(incl, 63);
+    quad_scan<MODE>(S, zk, tau, dnorm, lane, [&](const int i, const bool valid, const float e, const float f, const float Ti, float) {
         if (valid) {
             float G = gr * elem_colour<MODE>(i, 0, S, col, a.color_mode, a.farcolorfix) +
                       gg * elem_colour<MODE>(i, 1, S, col, a.color_mode, a.farcolorfix) +
@@ -113,7 +94,7 @@ __device__ __forceinline__ void quad_bwd_rows(const QuadArgs& a, const int ray, 
             wv[i] = (1.0f - e) * Ti;
             qv[i] = Ti;   // G_i and seg_i are recomputed in pass 2 (cheaper than two more LDS rows)
         }
-    }
+    });
     if (lane == 0) {
         fv[n] = 1.0f;
         av[n] = (MODE == PLNERF_MODE_LINEAR && a.g_T) ? a.g_T[(size_t)ray * (S + 2) + n] : 0.0f;

@@ -1,6 +1,6 @@
 // Device functions shared by the per-ray kernels (quad.hip, sampler.hip, epilogue.hip): one definition of the
-// quadrature's element rules, the cdf inversion and the register sort, so that the fused coarse epilogue computes
-// bit for bit what the separate launches compute.  Everything that includes this is built with -ffp-contract=off.
+// quadrature's element rules, the cdf inversion and the register sort -- the leaves; the loops around them are
+// ray_fwd_dev.h's and ray_bwd_dev.h's.  Everything that includes this is built with -ffp-contract=off.
 #pragma once
 #include "common.h"
 

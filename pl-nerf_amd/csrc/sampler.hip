@@ -35,42 +35,21 @@ struct SampleConstArgs {
 
 __global__ __launch_bounds__(256) void sample_const_kernel(SampleConstArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
-    const int B = a.B, n = a.B - 1;
-    float* cdf = smem + wave * a.lds_stride;   // B entries
+    const RayWave rw(a.R);
+    const int lane = rw.lane, ray = rw.ray, B = a.B, n = a.B - 1;
+    float* cdf = smem + rw.wave * a.lds_stride;   // B entries
     float* bins = cdf + B;                      // B entries
     float* wv = bins + B;                       // n entries (weights + 1e-5)
     for (int j = lane; j < B; j += 64) bins[j] = a.bins[(size_t)ray * B + j];
     for (int j = lane; j < n; j += 64) wv[j] = a.weights[(size_t)ray * n + j] + 1e-5f;
     __syncthreads();
-    const float total = torch_row_sum(wv, n, lane);
-    // cdf = [0, cumsum(pdf)]: fp64 running sum, each entry rounded to fp32
-    double carry = 0.0;
-    for (int base = 0; base < n; base += 64) {
-        const int j = base + lane;
-        const float pdf = (j < n) ? wv[j] / total : 0.0f;
-        const double incl = wave_incl_sum((double)pdf);
-        if (j < n) cdf[j + 1] = (float)(carry + incl);
-        carry = carry + __shfl(incl, 63);
-    }
-    if (lane == 0) cdf[0] = 0.0f;
+    cdf_const_rows(wv, n, lane, cdf);
     __syncthreads();
-    if (!live) return;
+    if (!rw.live) return;
     const float* urow = a.u + (size_t)ray * a.u_row_stride;
     for (int k = lane; k < a.N; k += 64) {
-        const float u = urow[k];
-        const int ind = upper_bound(cdf, B, u);
-        const int below = ind - 1 > 0 ? ind - 1 : 0;
-        const int above = ind < B - 1 ? ind : B - 1;
-        const float c0 = cdf[below], c1 = cdf[above];
-        float denom = c1 - c0;
-        if (denom < 1e-5f) denom = 1.0f;
-        const float t = (u - c0) / denom;
-        const float b0 = bins[below], b1 = bins[above];
-        a.samples[(size_t)ray * a.N + k] = b0 + t * (b1 - b0);
+        int ind;
+        a.samples[(size_t)ray * a.N + k] = invert_const(cdf, B, urow[k], [&](const int j) { return bins[j]; }, ind);
         if (a.inds) a.inds[(size_t)ray * a.N + k] = (int64_t)ind;
     }
 }
@@ -86,15 +65,12 @@ struct SampleConstBwdArgs {
 // Backward of sample_const_kernel with respect to `weights`: sample_const_bwd_rows (ray_bwd_dev.h).
 __global__ __launch_bounds__(256) void sample_const_bwd_kernel(SampleConstBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
-    const int n = a.in.B - 1;
-    float* cdf = smem + wave * a.lds_stride;
+    const RayWave rw(a.R);
+    const int lane = rw.lane, ray = rw.ray, n = a.in.B - 1;
+    float* cdf = smem + rw.wave * a.lds_stride;
     float total, dot;
     sample_const_bwd_rows(a.in, ray, lane, cdf, total, dot);
-    if (!live) return;
+    if (!rw.live) return;
     for (int i = lane; i < n; i += 64) a.g_weights[(size_t)ray * n + i] = (cdf[i] - dot) / total;
 }
 
@@ -119,12 +95,10 @@ struct SamplePlArgs {
 
 __global__ __launch_bounds__(256) void sample_pl_kernel(SamplePlArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
+    const RayWave rw(a.R);
+    const int lane = rw.lane, ray = rw.ray;
     const int S = a.S, K = a.S + 2;            // K knots / cdf entries
-    float* cdf = smem + wave * a.lds_stride;
+    float* cdf = smem + rw.wave * a.lds_stride;
     float* knots = cdf + K;
     float* tau = knots + K;
     float* Tr = tau + K;
@@ -137,36 +111,17 @@ __global__ __launch_bounds__(256) void sample_pl_kernel(SamplePlArgs a) {
         else kn = a.z[(size_t)ray * S + j - 1];
         knots[j] = kn;
     }
-    // cdf = [0, cumsum(weights)] (fp64 running sum), last entry forced to 1
-    double carry = 0.0;
-    const int n = S + 1;
-    for (int base = 0; base < n; base += 64) {
-        const int j = base + lane;
-        const float w = (j < n) ? a.weights[(size_t)ray * n + j] : 0.0f;
-        const double incl = wave_incl_sum((double)w);
-        if (j < n) cdf[j + 1] = (float)(carry + incl);
-        carry = carry + __shfl(incl, 63);
-    }
+    // cdf = [0, cumsum(weights)], the weights read from HBM inside the scan
+    cdf_linear_rows(S + 1, lane, cdf, [&](const int j) { return a.weights[(size_t)ray * (S + 1) + j]; });
     __syncthreads();
-    if (lane == 0) { cdf[0] = 0.0f; cdf[K - 1] = 1.0f; }
+    cdf_linear_ends(cdf, K, lane);
     __syncthreads();
-    if (!live) return;
+    if (!rw.live) return;
     const float* urow = a.u + (size_t)ray * a.u_row_stride;
-    const float zt = a.zero_tol, eps = a.eps;
     for (int k = lane; k < a.N; k += 64) {
-        const float u = urow[k];
-        const int ind = upper_bound(cdf, K, u);
-        const int below = ind - 1 > 0 ? ind - 1 : 0;
-        const int above = ind < K - 1 ? ind : K - 1;
-        const float s0 = knots[below], s1 = knots[above];
-        const float T0 = Tr[below];
-        const float tau0 = tau[below], tau1 = tau[above];
-        const int di = below < S ? below : S;               // H4: reference reads out of bounds at u == 1
-        const float d = tau[di + 1] - tau[di];
-        float out = (d < zt && d > -zt) ? s0 : -1.0f;
-        const bool rising = d >= zt;
-        if (rising || d <= -zt) out = invert_segment(s0, s1, T0, tau0, tau1, u, eps, rising);      // (one evaluation, operands selected per lane)
-        if (out != out) out = s0;
+        int ind;
+        float T0, tau0, s0;
+        const float out = invert_pl(cdf, knots, tau, Tr, S, urow[k], a.zero_tol, a.eps, ind, T0, tau0, s0);
         const size_t o = (size_t)ray * a.N + k;
         a.samples[o] = out;
         if (a.T_below) a.T_below[o] = T0;
@@ -293,12 +248,10 @@ __device__ __forceinline__ void invert_segment_knot_grad(float s0, float s1, flo
 
 __global__ __launch_bounds__(256) void sample_pl_bwd_kernel(SamplePlBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
+    const RayWave rw(a.R);
+    const int lane = rw.lane, ray = rw.ray;
     const int S = a.S, K = a.S + 2, N = a.N;
-    float* knots = smem + wave * a.lds_stride;
+    float* knots = smem + rw.wave * a.lds_stride;
     float* tau = knots + K;
     float* Tr = tau + K;
     float* gT0 = Tr + K;          // per sample: gradient landing on T[below]
@@ -346,7 +299,7 @@ __global__ __launch_bounds__(256) void sample_pl_bwd_kernel(SamplePlBwdArgs a) {
         lo[k] = below; hi[k] = above;
     }
     __syncthreads();
-    if (!live) return;
+    if (!rw.live) return;
     // per-knot sums in sample order (deterministic); all reads are LDS broadcasts
     for (int j = lane; j < K; j += 64) {
         float st = 0.0f, sT = 0.0f;
@@ -386,28 +339,16 @@ struct MergeArgs {
 // among equals does not show.
 template <int KPL>
 __global__ __launch_bounds__(256) void merge_sort_kernel(MergeArgs a) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
+    const RayWave rw(a.R);
+    const int lane = rw.lane, ray = rw.ray;
     const int S = a.S, N = a.N, n = S + N;
     const float lo = a.near[ray], hi = a.far[ray];
     uint32_t x[KPL];
-#pragma unroll
-    for (int r = 0; r < KPL; ++r) {
-        const int p = 64 * r + lane;
-        uint32_t k = 0xFFFFFFFFu;
-        if (p < S) k = sort_key(a.z[(size_t)ray * S + p]);
-        else if (p < n) k = sort_key(tmin(tmax(a.z_new[(size_t)ray * N + (p - S)], lo), hi));
-        x[r] = k;
-    }
-    bitonic_sort_regs<KPL>(x, lane);
-    if (!live) return;
-#pragma unroll
-    for (int r = 0; r < KPL; ++r) {
-        const int p = 64 * r + lane;
-        if (p < n) a.out[(size_t)ray * n + p] = sort_unkey(x[r]);
-    }
+    sort_row_regs<KPL>(x, n, lane, [&](const int p) {
+        return p < S ? a.z[(size_t)ray * S + p] : tmin(tmax(a.z_new[(size_t)ray * N + (p - S)], lo), hi);
+    });
+    if (!rw.live) return;
+    store_row_regs<KPL>(x, n, lane, [&](const int p, const float v) { a.out[(size_t)ray * n + p] = v; });
 }
 
 inline int set_lds(const void* fn, size_t lds) {
@@ -542,12 +483,6 @@ extern "C" int plnerf_merge_sort(const float* z, const float* z_new, const float
 // ------------------------------------------------------------------------------------
 namespace {
 
-__device__ __forceinline__ float coarse_depth(const float nr, const float fr, const float t, const int lindisp) {
-    const float omt = 1.0f - t;
-    if (!lindisp) return nr * omt + fr * t;                 // near * (1 - t) + far * t
-    return 1.0f / (1.0f / nr * omt + 1.0f / fr * t);        // 1 / (1/near * (1 - t) + 1/far * t)
-}
-
 __global__ __launch_bounds__(256) void stratified_z_kernel(const float* __restrict__ near, const float* __restrict__ far,
                                                            const float* __restrict__ t_vals,
                                                            const float* __restrict__ t_rand, const int R, const int S,
@@ -557,13 +492,7 @@ __global__ __launch_bounds__(256) void stratified_z_kernel(const float* __restri
     const int r = (int)(idx / S), s = (int)(idx - (size_t)r * S);
     const float nr = near[r], fr = far[r];
     const float z = coarse_depth(nr, fr, t_vals[s], lindisp);
-    if (!t_rand) { z_out[idx] = z; return; }
-    // mids = .5 * (z[1:] + z[:-1]); upper = [mids, z[-1]]; lower = [z[0], mids]; z = lower + (upper - lower) * t_rand
-    const float zl = s > 0 ? coarse_depth(nr, fr, t_vals[s - 1], lindisp) : z;
-    const float zu = s + 1 < S ? coarse_depth(nr, fr, t_vals[s + 1], lindisp) : z;
-    const float lower = s > 0 ? 0.5f * (z + zl) : z;
-    const float upper = s + 1 < S ? 0.5f * (zu + z) : z;
-    z_out[idx] = lower + (upper - lower) * t_rand[idx];
+    z_out[idx] = t_rand ? stratified_depth(nr, fr, t_vals, s, S, lindisp, t_rand[idx]) : z;
 }
 
 __global__ __launch_bounds__(256) void ray_points_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
@@ -586,18 +515,9 @@ __global__ __launch_bounds__(256) void ray_points4_kernel(const float* __restric
     if (i4 >= (size_t)R * per_ray) return;
     const int r = (int)(i4 / per_ray);
     const int e0 = (int)(i4 - (size_t)r * per_ray) * 4;                     // first element within the ray's S x 3 block
-    const float o[3] = {rays_o[3 * (size_t)r], rays_o[3 * (size_t)r + 1], rays_o[3 * (size_t)r + 2]};
-    const float d[3] = {rays_d[3 * (size_t)r], rays_d[3 * (size_t)r + 1], rays_d[3 * (size_t)r + 2]};
-    const float* zr = z + (size_t)r * S;
-    float v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int e = e0 + k, sidx = e / 3, c = e - 3 * sidx;
-        const float oc = c == 0 ? o[0] : (c == 1 ? o[1] : o[2]);
-        const float dc = c == 0 ? d[0] : (c == 1 ? d[1] : d[2]);
-        v[k] = oc + dc * zr[sidx];
-    }
-    pts[i4] = make_float4(v[0], v[1], v[2], v[3]);
+    const float3 o = make_float3(rays_o[3 * (size_t)r], rays_o[3 * (size_t)r + 1], rays_o[3 * (size_t)r + 2]);
+    const float3 d = make_float3(rays_d[3 * (size_t)r], rays_d[3 * (size_t)r + 1], rays_d[3 * (size_t)r + 2]);
+    pts[i4] = ray_positions4(o, d, z + (size_t)r * S, e0);
 }
 
 }  // namespace

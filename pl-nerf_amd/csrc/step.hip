@@ -26,13 +26,14 @@
 #include "common.h"
 #include "philox.h"
 #include "pixel_select.h"
+#include "ray_fwd_dev.h"
 #include "../../include/plnerf_hip_batching.h"
 
 using namespace plnerf;
 
 namespace {
 
-constexpr int WAVES = 4;
+constexpr int WAVES = RAY_WAVES;
 
 __global__ __launch_bounds__(256) void uniform_kernel(const RngArgs g, const int R, const int n, float* __restrict__ out) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // one Philox block = 4 columns
@@ -197,13 +198,7 @@ __global__ __launch_bounds__(256) void ndc_rays_kernel(const NdcArgs a) {
     a.d_out[3 * (size_t)i + 2] = a.minus_two_near / pz;
 }
 
-// ---- coarse depths + positions, one wavefront per ray ----
-__device__ __forceinline__ float coarse_depth(const float nr, const float fr, const float t, const int lindisp) {
-    const float omt = 1.0f - t;
-    if (!lindisp) return nr * omt + fr * t;                 // near * (1 - t) + far * t
-    return 1.0f / (1.0f / nr * omt + 1.0f / fr * t);        // 1 / (1/near * (1 - t) + 1/far * t)
-}
-
+// ---- coarse depths + positions, one wavefront per ray: plnerf_stratified_z's and plnerf_ray_points' bodies (ray_fwd_dev.h) ----
 struct CoarseArgs {
     const float* rays_o;
     const float* rays_d;
@@ -219,50 +214,21 @@ struct CoarseArgs {
 
 __global__ __launch_bounds__(256) void coarse_samples_kernel(const CoarseArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ray = blockIdx.x * WAVES + wave;
-    const bool live = ray < a.R;
-    if (!live) ray = a.R - 1;
-    const int S = a.S;
-    float* zs = smem + (size_t)wave * ((S + 3) & ~3);
+    const RayWave rw(a.R);
+    const int lane = rw.lane, ray = rw.ray, S = a.S;
+    float* zs = smem + (size_t)rw.wave * ((S + 3) & ~3);
     const float nr = a.near[ray], fr = a.far[ray];
     for (int s = lane; s < S; s += 64) {
         float z = coarse_depth(nr, fr, a.t_vals[s], a.lindisp);
-        if (a.perturb) {
-            // mids = .5 (z[1:] + z[:-1]); upper = [mids, z[-1]]; lower = [z[0], mids]; z = lower + (upper - lower) t_rand
-            const float zl = s > 0 ? coarse_depth(nr, fr, a.t_vals[s - 1], a.lindisp) : z;
-            const float zu = s + 1 < S ? coarse_depth(nr, fr, a.t_vals[s + 1], a.lindisp) : z;
-            const float lower = s > 0 ? 0.5f * (z + zl) : z;
-            const float upper = s + 1 < S ? 0.5f * (zu + z) : z;
-            const float t = a.t_rand ? a.t_rand[(size_t)ray * S + s] : rng_uniform(a.rng, a.rng.ray_id0 + ray, s);
-            z = lower + (upper - lower) * t;
-        }
+        if (a.perturb)
+            z = stratified_depth(nr, fr, a.t_vals, s, S, a.lindisp,
+                                 a.t_rand ? a.t_rand[(size_t)ray * S + s] : rng_uniform(a.rng, a.rng.ray_id0 + ray, s));
         zs[s] = z;
-        if (live) a.z_vals[(size_t)ray * S + s] = z;
+        if (rw.live) a.z_vals[(size_t)ray * S + s] = z;
     }
     __syncthreads();
-    if (!live) return;
-    const float o[3] = {a.rays_o[3 * (size_t)ray], a.rays_o[3 * (size_t)ray + 1], a.rays_o[3 * (size_t)ray + 2]};
-    const float d[3] = {a.rays_d[3 * (size_t)ray], a.rays_d[3 * (size_t)ray + 1], a.rays_d[3 * (size_t)ray + 2]};
-    float* prow = a.pts + (size_t)ray * 3 * S;
-    if ((3 * S) % 4 == 0 && ((uintptr_t)a.pts & 15) == 0) {
-        for (int q = lane; q < 3 * S / 4; q += 64) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int e = 4 * q + k, si = e / 3, c = e - 3 * si;
-                const float oc = c == 0 ? o[0] : (c == 1 ? o[1] : o[2]);
-                const float dc = c == 0 ? d[0] : (c == 1 ? d[1] : d[2]);
-                v[k] = oc + dc * zs[si];
-            }
-            reinterpret_cast<float4*>(prow)[q] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    } else {
-        for (int e = lane; e < 3 * S; e += 64) {
-            const int si = e / 3, c = e - 3 * si;
-            prow[e] = (c == 0 ? o[0] : (c == 1 ? o[1] : o[2])) + (c == 0 ? d[0] : (c == 1 ? d[1] : d[2])) * zs[si];
-        }
-    }
+    if (!rw.live) return;
+    ray_positions(a.rays_o, a.rays_d, ray, zs, S, a.pts + (size_t)ray * 3 * S, lane);
 }
 
 // ---- loss = mean((rgb - t)^2) + mean((rgb0 - t)^2), and d loss / d rgb, d loss / d rgb0 (for an upstream gradient of

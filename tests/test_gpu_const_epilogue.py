@@ -94,7 +94,7 @@ def _assert_coarse_equal(Fn, c, N, white, what):
 # n = S - 2 is the length of the row torch.sum adds up: 1, 2, the 4..7 special case, 7, the first 8-lane vector; then the
 # workloads' sizes and the edges of the sort network's tiers (S + N <= 64 / 128 / 256 / 512 / 1024 with the N sub-tiers)
 SHAPES = [(3, 1), (4, 5), (6, 7), (9, 64), (10, 65), (37, 23), (64, 128), (128, 64), (66, 190), (130, 127), (300, 200),
-          (512, 512)]
+          (512, 512), (63, 1), (65, 65)]      # (the last two: the scan's and the cdf's 64-lane chunk edges)
 
 
 @pytest.mark.parametrize("S,N", SHAPES)

@@ -89,7 +89,7 @@ def quad_case(R, S, seed):
 
 
 @pytest.mark.parametrize("mode,cmode", [("linear", "midpoint"), ("linear", "left"), ("constant", "midpoint")])
-@pytest.mark.parametrize("S", [64, 192, 37])
+@pytest.mark.parametrize("S", [64, 192, 37, 65])      # (65: one element past the scan's 64-lane chunk in both modes)
 def test_quad_fwd_bwd_vs_oracle(P, mode, cmode, S):
     from plnerf_amd.functional import QuadratureFn
     R = 67

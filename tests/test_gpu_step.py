@@ -78,7 +78,9 @@ def test_philox_known_answers_and_device_draws(P):
 
 # ----------------------------------------------------------------------------- fused coarse epilogue
 @pytest.mark.parametrize("S,N,color,white", [(64, 128, "midpoint", True), (128, 64, "midpoint", False),
-                                             (37, 23, "left", True), (300, 200, "midpoint", True), (2, 1, "midpoint", False)])
+                                             (37, 23, "left", True), (300, 200, "midpoint", True), (2, 1, "midpoint", False),
+                                             # the scan's chunk edge: n = S + 1 = 64, S = 65, and 64 / 65 draws
+                                             (63, 1, "midpoint", True), (65, 64, "left", False), (129, 65, "midpoint", True)])
 def test_fused_coarse_epilogue_equals_separate_launches(P, S, N, color, white):
     """plnerf_coarse_epilogue == plnerf_quad_fwd -> plnerf_sample_pl -> clamp -> plnerf_merge_sort ->
     plnerf_ray_points, bit for bit (same device functions, same LDS values), forward and backward; z_std against
