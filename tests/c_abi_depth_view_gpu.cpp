@@ -1,8 +1,9 @@
 // A torch-free rendering host of the experimental C ABI (include/experimental/plnerf_hip_depthview.h): what a C, cgo or
 // ctypes caller writes to evaluate a trained model of the depth-supervised variant with libplnerf_hip.so -- device memory
-// from the HIP runtime, then nothing but plnerf_depth_render_view, once per frame.  Test infrastructure
-// (tests/test_gpu_depth_view.py builds it with g++, writes its input tables and compares its hashes with DepthViewRenderer on
-// the same inputs); not part of the product.
+// from the HIP runtime, then nothing but plnerf_depth_render_view, once per frame (tests/c_abi_host.h holds the error macros,
+// the tensor table and the network builder that the hosts share).  Test infrastructure (tests/test_gpu_depth_view.py builds
+// it with g++, writes its input tables and compares its hashes with DepthViewRenderer on the same inputs); not part of the
+// product.
 //
 //   c_abi_depth_view_gpu <precision> <fwd_kernel> <inputs.bin>
 //
@@ -13,62 +14,21 @@
 // valid + error_row and the three exports.
 // stdout: "<plane> <FNV-1a 64 of its bytes, hex>" for rgb, disp, acc, depth, rgb0, disp0, acc0, depth0, z_std, pred_hyp, rgb8,
 // depth16, depth_mm16, error_row.
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "experimental/plnerf_hip_depthview.h"
+#include "c_abi_host.h"      // HIP_OK / PL_OK, the network builder and FNV-1a
 
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 10; } } while (0)
-#define PL_OK(x) do { int rc_ = (x); if (rc_ != PLNERF_OK) { std::fprintf(stderr, "%s: %s\n", #x, plnerf_error_string(rc_)); return 11; } } while (0)
+using namespace c_abi_host;
 
 namespace {
-constexpr int W = 256, XYZ = 57, DIR = 3, IMG_H = 9, IMG_W = 13, NS = 6, NI = 5, N_PIX = IMG_H * IMG_W, BLOCK = 32;
-
-std::vector<size_t> param_sizes() {      // state_dict order: weight [out, in], bias [out]
-    std::vector<size_t> t;
-    for (int i = 0; i < 8; ++i) {
-        const int fan_in = i == 0 ? XYZ : (i == 5 ? W + XYZ : W);
-        t.push_back((size_t)W * fan_in);
-        t.push_back((size_t)W);
-    }
-    t.push_back((size_t)(W / 2) * (W + DIR)); t.push_back((size_t)(W / 2));      // views_linears.0
-    t.push_back((size_t)W * W); t.push_back((size_t)W);                          // feature_linear
-    t.push_back((size_t)W); t.push_back(1);                                      // alpha_linear
-    t.push_back((size_t)3 * (W / 2)); t.push_back(3);                            // rgb_linear
-    return t;
-}
+constexpr int XYZ = 57, DIR = 3, IMG_H = 9, IMG_W = 13, NS = 6, NI = 5, N_PIX = IMG_H * IMG_W, BLOCK = 32;
 
 // one network: its parameters from the file in one device buffer, and its packed buffer with the status word zeroed
-int make_net(std::FILE* f, int prec, plnerf_view_net* net) {
-    const std::vector<size_t> sizes = param_sizes();
-    size_t n = 0;
-    for (size_t s : sizes) n += s;
-    std::vector<float> h(n);
-    if (std::fread(h.data(), 4, n, f) != n) { std::fprintf(stderr, "inputs.bin is too short for a network\n"); return 4; }
-    float* flat;
-    HIP_OK(hipMalloc((void**)&flat, n * 4));
-    HIP_OK(hipMemcpy(flat, h.data(), n * 4, hipMemcpyHostToDevice));
-    const size_t packed_bytes = plnerf_mlp_packed_bytes(prec);
-    if (packed_bytes == 0) { std::fprintf(stderr, "precision mode %d is not built\n", prec); return 7; }
-    void* packed;
-    HIP_OK(hipMalloc(&packed, packed_bytes));
-    HIP_OK(hipMemset(packed, 0, packed_bytes));
-    size_t off = 0;
-    for (int k = 0; k < PLNERF_N_PARAM_TENSORS; ++k) { net->params[k] = flat + off; off += sizes[k]; }
-    net->packed = packed;
-    return 0;
-}
-
-unsigned long long fnv1a(const void* data, size_t n) {
-    const unsigned char* p = (const unsigned char*)data;
-    unsigned long long h = 0xcbf29ce484222325ull;
-    for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
-    return h;
+int read_net(std::FILE* f, int prec, plnerf_view_net* net) {
+    std::vector<float> h(param_count(XYZ, DIR));
+    if (std::fread(h.data(), 4, h.size(), f) != h.size()) { std::fprintf(stderr, "inputs.bin is too short for a network\n"); return 4; }
+    return make_net(h, XYZ, DIR, prec, net);
 }
 
 struct Plane { const char* name; size_t bytes; void* dev; };
@@ -93,9 +53,8 @@ int main(int argc, char** argv) {
 
     plnerf_depth_view_io io;
     std::memset(&io, 0, sizeof io);
-    int rc = make_net(f, prec, &io.coarse);
-    if (rc) return rc;
-    rc = make_net(f, prec, &io.fine);
+    int rc = read_net(f, prec, &io.coarse);
+    if (!rc) rc = read_net(f, prec, &io.fine);
     if (rc) return rc;
     std::vector<float> tables((size_t)NS + NI);
     std::vector<uint8_t> valid(N_PIX);
@@ -104,17 +63,13 @@ int main(int argc, char** argv) {
         return 4;
     }
     std::fclose(f);
-    float* d_tables;
-    uint8_t* d_valid;
-    double* d_row;
-    HIP_OK(hipMalloc((void**)&d_tables, tables.size() * 4));
-    HIP_OK(hipMemcpy(d_tables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMalloc((void**)&d_valid, valid.size()));
-    HIP_OK(hipMemcpy(d_valid, valid.data(), valid.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMalloc((void**)&d_row, 2 * sizeof(double)));
-    HIP_OK(hipMemset(d_row, 0, 2 * sizeof(double)));      // the caller zeroes the row before a frame's first call
+    const float* d_tables = upload(tables);
+    io.valid = upload(valid);
+    if (!d_tables || !io.valid) return 10;
+    double* d_row;      // the caller zeroes the row before a frame's first call
+    if (zeroed(&d_row, 2 * sizeof(double))) return 10;
     io.t_vals = d_tables; io.u_vals = d_tables + NS;
-    io.valid = d_valid; io.error_row = d_row;
+    io.error_row = d_row;
 
     Plane planes[] = {
         {"rgb", (size_t)N_PIX * 12, nullptr}, {"disp", (size_t)N_PIX * 4, nullptr}, {"acc", (size_t)N_PIX * 4, nullptr},
@@ -151,7 +106,7 @@ int main(int argc, char** argv) {
     const plnerf_view_net* nets[2] = {&io.coarse, &io.fine};
     for (int j = 0; j < 2; ++j) {
         uint32_t status;
-        HIP_OK(hipMemcpy(&status, (const unsigned char*)nets[j]->packed + plnerf_mlp_status_offset(prec), 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(&status, status_word(*nets[j], prec), 4, hipMemcpyDeviceToHost));
         if (status) { std::fprintf(stderr, "network %d left the half range (status %u)\n", j, status); return 14; }
     }
     for (int k = 0; k < N_PLANES; ++k) {

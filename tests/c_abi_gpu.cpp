@@ -1,7 +1,8 @@
 // A torch-free host of the C ABI (include/plnerf_hip.h): what a maintainer binding libplnerf_hip.so from C, cgo or ctypes
 // would write for one network evaluation and its backward -- device memory from the HIP runtime, every pointer a plain
 // device pointer, the stream NULL.  Test infrastructure (tests/test_gpu_parity.py::test_c_host_without_torch builds it with
-// g++, feeds it a file of inputs and compares the file of outputs with the oracle); not part of the product.
+// g++, feeds it a file of inputs and compares the file of outputs with the oracle); not part of the product.  The error macros,
+// the tensor table and the upload helper are tests/c_abi_host.h's, shared with the other hosts.
 //
 //   c_abi_gpu <precision> <R> <S> <in.bin> <out.bin>
 //
@@ -12,41 +13,15 @@
 //         near [R], far [R], rays_d [R,3], g_rgb [R,3], g_depth [R], g_acc [R]
 // out.bin (fp32): raw [R,S,4], rgb [R,3], disp [R], acc [R], depth [R], weights [R,S+1], g_raw [R,S,4], the 24 gradients,
 //         the first weight tensor after one Adam step
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-
-#include <cstdio>
 #include <cstdlib>
-#include <vector>
 
-#include "plnerf_hip.h"
+#include "c_abi_host.h"      // HIP_OK / PL_OK, param_tensors, upload
 
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 10; } } while (0)
-#define PL_OK(x) do { int rc_ = (x); if (rc_ != PLNERF_OK) { std::fprintf(stderr, "%s: %s\n", #x, plnerf_error_string(rc_)); return 11; } } while (0)
+using namespace c_abi_host;
 
 namespace {
-constexpr int W = 256, XYZ = 63, DIR = 27;
-
-std::vector<size_t> param_sizes() {      // state_dict order (run_nerf_helpers.py:87-101)
-    std::vector<size_t> n;
-    for (int i = 0; i < 8; ++i) {
-        const size_t fan_in = i == 0 ? XYZ : (i == 5 ? W + XYZ : W);
-        n.push_back(W * fan_in);
-        n.push_back(W);
-    }
-    n.push_back((size_t)(W / 2) * (W + DIR)); n.push_back(W / 2);      // views_linears.0
-    n.push_back((size_t)W * W); n.push_back(W);                        // feature_linear
-    n.push_back(W); n.push_back(1);                                    // alpha_linear
-    n.push_back(3 * (W / 2)); n.push_back(3);                          // rgb_linear
-    return n;
-}
-
-float* to_device(const std::vector<float>& h) {
-    float* d = nullptr;
-    if (hipMalloc((void**)&d, h.size() * sizeof(float) + 16) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return d;
-}
+constexpr int XYZ = 63, DIR = 27;
+constexpr size_t SPARE = 16;      // bytes of slack behind every input (kept: the kernels' tail reads have not been audited)
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -58,14 +33,15 @@ int main(int argc, char** argv) {
     std::FILE* in = std::fopen(argv[4], "rb");
     if (!in) return 4;
     auto read = [&](size_t n) { std::vector<float> v(n); if (std::fread(v.data(), 4, n, in) != n) v.clear(); return v; };
-    const std::vector<size_t> sizes = param_sizes();
+    std::vector<size_t> sizes;
+    for (const Tensor& t : param_tensors(XYZ, DIR)) sizes.push_back(t.n);
     const float* params[PLNERF_N_PARAM_TENSORS];
     float* params_dev[PLNERF_N_PARAM_TENSORS];
     float* grads[PLNERF_N_PARAM_TENSORS];
     for (int i = 0; i < PLNERF_N_PARAM_TENSORS; ++i) {
         const std::vector<float> h = read(sizes[i]);
         if (h.empty()) return 5;
-        params[i] = params_dev[i] = to_device(h);
+        params[i] = params_dev[i] = upload(h, SPARE);
         HIP_OK(hipMalloc((void**)&grads[i], sizes[i] * sizeof(float)));
         if (!params[i]) return 6;
     }
@@ -74,16 +50,15 @@ int main(int argc, char** argv) {
                              h_gacc = read(R);
     std::fclose(in);
     if (h_gacc.empty()) return 5;
-    float *pts = to_device(h_pts), *vd = to_device(h_vd), *z = to_device(h_z), *near = to_device(h_near), *far = to_device(h_far),
-          *rays_d = to_device(h_d), *g_rgb = to_device(h_grgb), *g_depth = to_device(h_gdep), *g_acc = to_device(h_gacc);
+    float *pts = upload(h_pts, SPARE), *vd = upload(h_vd, SPARE), *z = upload(h_z, SPARE), *near = upload(h_near, SPARE), *far = upload(h_far, SPARE),
+          *rays_d = upload(h_d, SPARE), *g_rgb = upload(h_grgb, SPARE), *g_depth = upload(h_gdep, SPARE), *g_acc = upload(h_gacc, SPARE);
     if (!pts || !vd || !z || !near || !far || !rays_d || !g_rgb || !g_depth || !g_acc) return 6;
 
     // weights into the kernels' fragment order; the status word behind them starts at zero (the library only ORs into it)
     const size_t packed_bytes = plnerf_mlp_packed_bytes(prec);
     if (packed_bytes == 0) { std::fprintf(stderr, "precision mode %d is not built\n", prec); return 7; }
     void* packed = nullptr;
-    HIP_OK(hipMalloc(&packed, packed_bytes));
-    HIP_OK(hipMemset(packed, 0, packed_bytes));
+    if (zeroed(&packed, packed_bytes)) return 10;
     PL_OK(plnerf_mlp_pack_weights(params, prec, XYZ, DIR, packed, nullptr));
 
     // forward with saved state
@@ -113,10 +88,7 @@ int main(int argc, char** argv) {
                          nullptr));
     // one Adam step on pts_linears.0.weight (step 1, lr 5e-4, no clipping, no guard words)
     float *m, *v;
-    HIP_OK(hipMalloc((void**)&m, sizes[0] * 4));
-    HIP_OK(hipMalloc((void**)&v, sizes[0] * 4));
-    HIP_OK(hipMemset(m, 0, sizes[0] * 4));
-    HIP_OK(hipMemset(v, 0, sizes[0] * 4));
+    if (zeroed(&m, sizes[0] * 4) || zeroed(&v, sizes[0] * 4)) return 10;
     PL_OK(plnerf_adam_step(params_dev[0], grads[0], m, v, (int64_t)sizes[0], 5e-4f, 0.9f, 0.999f, 1e-8f, 1, 1.0f, 0.0f, nullptr,
                            nullptr, nullptr, nullptr));
     HIP_OK(hipDeviceSynchronize());

@@ -1,6 +1,6 @@
 // A torch-free training host of the C ABI (include/plnerf_hip_step.h): what a C, cgo or ctypes caller writes to TRAIN with
-// libplnerf_hip.so -- device memory from the HIP runtime, weights from a fixed integer hash, then nothing but
-// plnerf_train_step, once per optimisation step.  Test infrastructure (tests/test_gpu_one_call.py builds it with g++ and
+// libplnerf_hip.so -- device memory from the HIP runtime, weights from a fixed integer hash (tests/c_abi_host.h, with the
+// error macros and what else the hosts share), then nothing but plnerf_train_step, once per optimisation step.  Test infrastructure (tests/test_gpu_one_call.py builds it with g++ and
 // compares its per-step losses with the Python one-call route started from the same weights); not part of the product.
 //
 //   c_abi_step_gpu <precision> <R> <N_samples> <N_importance> <steps> <fwd_kernel> [tables.bin]
@@ -11,94 +11,16 @@
 // caller comparing against the Python route supplies; without it the host computes start + i * step itself.
 // stdout: one line per step "step <k> loss <8 hex digits of the fp32 total> psnr <8 hex digits>", then
 // "params <sum of the coarse network's parameter bit patterns> <the fine network's>" (uint64, decimal).
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "plnerf_hip_step.h"
+#include "c_abi_host.h"      // HIP_OK / PL_OK and the scene's weights, tables and checksums
 
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 10; } } while (0)
-#define PL_OK(x) do { int rc_ = (x); if (rc_ != PLNERF_OK) { std::fprintf(stderr, "%s: %s\n", #x, plnerf_error_string(rc_)); return 11; } } while (0)
+using namespace c_abi_host;
 
 namespace {
-constexpr int W = 256, XYZ = 63, DIR = 27, IMG_H = 40, IMG_W = 48;
-
-// value i of sequence k, uniform in [0, 1): two rounds of the Numerical Recipes LCG over a counter (tests/test_gpu_one_call.py
-// restates it in numpy)
-inline float hashed(uint32_t k, uint32_t i) {
-    uint32_t x = i * 2654435761u + k * 0x9e3779b9u + 12345u;
-    x = x * 1664525u + 1013904223u;
-    x ^= x >> 15;
-    x = x * 1664525u + 1013904223u;
-    return (float)(x >> 8) * (1.0f / 16777216.0f);
-}
-
-struct Tensor { size_t n; int fan_in; };
-
-std::vector<Tensor> param_tensors() {      // state_dict order (run_nerf_helpers.py:87-101): weight [out, in], bias [out]
-    std::vector<Tensor> t;
-    for (int i = 0; i < 8; ++i) {
-        const int fan_in = i == 0 ? XYZ : (i == 5 ? W + XYZ : W);
-        t.push_back({(size_t)W * fan_in, fan_in});
-        t.push_back({(size_t)W, fan_in});
-    }
-    t.push_back({(size_t)(W / 2) * (W + DIR), W + DIR}); t.push_back({(size_t)(W / 2), W + DIR});      // views_linears.0
-    t.push_back({(size_t)W * W, W}); t.push_back({(size_t)W, W});                                      // feature_linear
-    t.push_back({(size_t)W, W}); t.push_back({1, W});                                                  // alpha_linear
-    t.push_back({(size_t)3 * (W / 2), W / 2}); t.push_back({3, W / 2});                                // rgb_linear
-    return t;
-}
-
-// one network: its flat parameter buffer filled from the hash (nn.Linear's uniform(-1 / sqrt(fan_in), 1 / sqrt(fan_in))), flat
-// gradient (+ 4 floats of tail) and moments, packed buffer with its status word zeroed
-int make_net(int which, int prec, plnerf_step_net* net, float** flat_out, size_t* n_out) {
-    const std::vector<Tensor> ts = param_tensors();
-    size_t n = 0;
-    for (const Tensor& t : ts) n += t.n;
-    std::vector<float> h(n);
-    size_t off = 0;
-    std::vector<size_t> offs;
-    for (size_t k = 0; k < ts.size(); ++k) {
-        const float bound = 1.0f / std::sqrt((float)ts[k].fan_in);
-        for (size_t i = 0; i < ts[k].n; ++i) h[off + i] = (2.0f * hashed((uint32_t)(100 * which + k), (uint32_t)i) - 1.0f) * bound;
-        offs.push_back(off);
-        off += ts[k].n;
-    }
-    float *flat, *grad, *m, *v;
-    HIP_OK(hipMalloc((void**)&flat, n * 4));
-    HIP_OK(hipMalloc((void**)&grad, (n + 4) * 4));
-    HIP_OK(hipMalloc((void**)&m, n * 4));
-    HIP_OK(hipMalloc((void**)&v, n * 4));
-    HIP_OK(hipMemcpy(flat, h.data(), n * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(grad, 0, (n + 4) * 4));
-    HIP_OK(hipMemset(m, 0, n * 4));
-    HIP_OK(hipMemset(v, 0, n * 4));
-    const size_t packed_bytes = plnerf_mlp_packed_bytes(prec);
-    if (packed_bytes == 0) { std::fprintf(stderr, "precision mode %d is not built\n", prec); return 7; }
-    void* packed;
-    HIP_OK(hipMalloc(&packed, packed_bytes));
-    HIP_OK(hipMemset(packed, 0, packed_bytes));
-    for (int k = 0; k < PLNERF_N_PARAM_TENSORS; ++k) net->params[k] = flat + offs[k];
-    net->param_flat = flat; net->grad_flat = grad; net->exp_avg = m; net->exp_avg_sq = v;
-    net->n_params = (int64_t)n;
-    net->packed = packed;
-    uint32_t* withheld;
-    HIP_OK(hipMalloc((void**)&withheld, 4));
-    HIP_OK(hipMemset(withheld, 0, 4));
-    net->withheld = withheld;
-    *flat_out = flat;
-    *n_out = n;
-    return 0;
-}
-
-const uint32_t* status_word(const plnerf_step_net& net, int prec) {
-    return (const uint32_t*)((const unsigned char*)net.packed + plnerf_mlp_status_offset(prec));
-}
+constexpr int XYZ = 63, DIR = 27, IMG_H = 40, IMG_W = 48;
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -122,44 +44,35 @@ int main(int argc, char** argv) {
 
     plnerf_step_io io;
     std::memset(&io, 0, sizeof io);
-    float *flat_c, *flat_f;
-    size_t n_c, n_f;
-    int rc = make_net(0, prec, &io.coarse, &flat_c, &n_c);
-    if (rc) return rc;
-    rc = make_net(1, prec, &io.fine, &flat_f, &n_f);
-    if (rc) return rc;
+    // each network: parameters from the hash in one flat buffer, packed buffer, flat gradient and moments, a counter of its own
+    plnerf_step_net* nets[2] = {&io.coarse, &io.fine};
+    for (int j = 0; j < 2; ++j) {
+        int rc = make_net(hashed_net_values(j, XYZ, DIR), XYZ, DIR, prec, nets[j]);
+        if (!rc) rc = add_training_state(nets[j], param_count(XYZ, DIR));
+        if (!rc) rc = zeroed(&nets[j]->withheld, 4);
+        if (rc) return rc;
+    }
     // the fine optimizer is guarded by both networks' words, the coarse one by its own (render.create_nerf)
     io.fine.skip_if_set = status_word(io.fine, prec); io.fine.skip_if_set2 = status_word(io.coarse, prec);
     io.coarse.skip_if_set = status_word(io.coarse, prec);
 
-    std::vector<float> tables((size_t)Ns + Ni);
-    if (argc == 8) {
-        std::FILE* f = std::fopen(argv[7], "rb");
-        if (!f || std::fread(tables.data(), 4, tables.size(), f) != tables.size()) return 4;
-        std::fclose(f);
-    } else {
-        for (int i = 0; i < Ns; ++i) tables[i] = (float)i * (1.0f / (float)(Ns - 1));
-        for (int i = 0; i < Ni; ++i) tables[Ns + i] = Ni > 1 ? (float)i * (1.0f / (float)(Ni - 1)) : 0.0f;
-    }
-    float* d_tables;
-    HIP_OK(hipMalloc((void**)&d_tables, tables.size() * 4));
-    HIP_OK(hipMemcpy(d_tables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice));
+    std::vector<float> tables;
+    if (!load_tables(argc == 8 ? argv[7] : nullptr, Ns, Ni, &tables)) return 4;
+    const float* d_tables = upload(tables);
+    if (!d_tables) return 10;
     io.t_vals = d_tables; io.u_vals = d_tables + Ns;
 
     std::vector<float> image((size_t)IMG_H * IMG_W * 3);
     for (size_t i = 0; i < image.size(); ++i) image[i] = hashed(999u, (uint32_t)i);
-    float* d_image;
-    HIP_OK(hipMalloc((void**)&d_image, image.size() * 4));
-    HIP_OK(hipMemcpy(d_image, image.data(), image.size() * 4, hipMemcpyHostToDevice));
+    const float* d_image = upload(image);
+    if (!d_image) return 10;
     float* d_loss;      // one loss4 per step, read back after the last one
-    HIP_OK(hipMalloc((void**)&d_loss, (size_t)steps * 4 * 4));
-    HIP_OK(hipMemset(d_loss, 0, (size_t)steps * 4 * 4));
+    if (zeroed(&d_loss, (size_t)steps * 4 * 4)) return 10;
 
     const size_t ws_bytes = plnerf_train_step_workspace_bytes(&cfg);
     if (ws_bytes == 0) { std::fprintf(stderr, "the configuration was refused\n"); return 8; }
-    void* ws;
-    HIP_OK(hipMalloc(&ws, ws_bytes));      // (hipMalloc's alignment is at least 256 bytes)
-    HIP_OK(hipMemset(ws, 0, ws_bytes));
+    void* ws;      // (hipMalloc's alignment is at least 256 bytes)
+    if (zeroed(&ws, ws_bytes)) return 10;
 
     plnerf_step_args a;
     std::memset(&a, 0, sizeof a);
@@ -178,24 +91,7 @@ int main(int argc, char** argv) {
     }
     HIP_OK(hipDeviceSynchronize());
 
-    std::vector<float> loss((size_t)steps * 4);
-    HIP_OK(hipMemcpy(loss.data(), d_loss, loss.size() * 4, hipMemcpyDeviceToHost));
-    for (int k = 0; k < steps; ++k) {
-        uint32_t bits[2];
-        std::memcpy(&bits[0], &loss[4 * k], 4);
-        std::memcpy(&bits[1], &loss[4 * k + 3], 4);
-        std::printf("step %d loss %08x psnr %08x\n", k, bits[0], bits[1]);
-    }
-    unsigned long long sums[2];
-    float* flats[2] = {flat_c, flat_f};
-    const size_t ns[2] = {n_c, n_f};
-    for (int j = 0; j < 2; ++j) {
-        std::vector<uint32_t> h(ns[j]);
-        HIP_OK(hipMemcpy(h.data(), flats[j], ns[j] * 4, hipMemcpyDeviceToHost));
-        sums[j] = 0;
-        for (uint32_t x : h) sums[j] += x;
-    }
-    std::printf("params %llu %llu\n", sums[0], sums[1]);
+    if (print_step_losses(d_loss, steps, 4, "psnr") || print_param_checksums(io.coarse, io.fine)) return 10;
     uint32_t withheld[2];
     HIP_OK(hipMemcpy(&withheld[0], io.coarse.withheld, 4, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(&withheld[1], io.fine.withheld, 4, hipMemcpyDeviceToHost));

@@ -1,6 +1,6 @@
 // A torch-free rendering host of the C ABI (include/plnerf_hip_view.h): what a C, cgo or ctypes caller writes to turn two
 // trained networks into a frame with libplnerf_hip.so -- device memory from the HIP runtime, weights from the fixed integer
-// hash of tests/c_abi_step_gpu.cpp, then nothing but plnerf_render_view, once per frame.  Test infrastructure
+// hash of tests/c_abi_host.h, then nothing but plnerf_render_view, once per frame.  Test infrastructure
 // (tests/test_gpu_view.py builds it with g++ and compares its hashes with ViewRenderer on the same weights and pose); not
 // part of the product.
 //
@@ -11,82 +11,16 @@
 // for byte in every plane and be finite (but for the disparity of a ray that met nothing).
 // tables.bin (optional, fp32): t_vals [64] then u_vals [128] -- torch.linspace(0, 1, n) to the bit.
 // stdout: "rgb8 <FNV-1a 64 of the 8-bit frame, hex>", "rgb <FNV-1a 64 of the fp32 colour plane>", "depth16 <...>".
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "plnerf_hip_view.h"
+#include "c_abi_host.h"      // HIP_OK / PL_OK and the scene's weights, tables and FNV-1a
 
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 10; } } while (0)
-#define PL_OK(x) do { int rc_ = (x); if (rc_ != PLNERF_OK) { std::fprintf(stderr, "%s: %s\n", #x, plnerf_error_string(rc_)); return 11; } } while (0)
+using namespace c_abi_host;
 
 namespace {
-constexpr int W = 256, XYZ = 63, DIR = 27, IMG_H = 16, IMG_W = 12, NS = 64, NI = 128, N_PIX = IMG_H * IMG_W;
-
-// value i of sequence k, uniform in [0, 1): tests/c_abi_step_gpu.cpp's hash (tests/test_gpu_one_call.py restates it in numpy)
-inline float hashed(uint32_t k, uint32_t i) {
-    uint32_t x = i * 2654435761u + k * 0x9e3779b9u + 12345u;
-    x = x * 1664525u + 1013904223u;
-    x ^= x >> 15;
-    x = x * 1664525u + 1013904223u;
-    return (float)(x >> 8) * (1.0f / 16777216.0f);
-}
-
-struct Tensor { size_t n; int fan_in; };
-
-std::vector<Tensor> param_tensors() {      // state_dict order (run_nerf_helpers.py:87-101): weight [out, in], bias [out]
-    std::vector<Tensor> t;
-    for (int i = 0; i < 8; ++i) {
-        const int fan_in = i == 0 ? XYZ : (i == 5 ? W + XYZ : W);
-        t.push_back({(size_t)W * fan_in, fan_in});
-        t.push_back({(size_t)W, fan_in});
-    }
-    t.push_back({(size_t)(W / 2) * (W + DIR), W + DIR}); t.push_back({(size_t)(W / 2), W + DIR});      // views_linears.0
-    t.push_back({(size_t)W * W, W}); t.push_back({(size_t)W, W});                                      // feature_linear
-    t.push_back({(size_t)W, W}); t.push_back({1, W});                                                  // alpha_linear
-    t.push_back({(size_t)3 * (W / 2), W / 2}); t.push_back({3, W / 2});                                // rgb_linear
-    return t;
-}
-
-// one network: its parameters from the hash (nn.Linear's uniform(-1 / sqrt(fan_in), 1 / sqrt(fan_in))) in one device buffer,
-// and its packed buffer with the status word zeroed
-int make_net(int which, int prec, plnerf_view_net* net) {
-    const std::vector<Tensor> ts = param_tensors();
-    size_t n = 0;
-    for (const Tensor& t : ts) n += t.n;
-    std::vector<float> h(n);
-    std::vector<size_t> offs;
-    size_t off = 0;
-    for (size_t k = 0; k < ts.size(); ++k) {
-        const float bound = 1.0f / std::sqrt((float)ts[k].fan_in);
-        for (size_t i = 0; i < ts[k].n; ++i) h[off + i] = (2.0f * hashed((uint32_t)(100 * which + k), (uint32_t)i) - 1.0f) * bound;
-        offs.push_back(off);
-        off += ts[k].n;
-    }
-    float* flat;
-    HIP_OK(hipMalloc((void**)&flat, n * 4));
-    HIP_OK(hipMemcpy(flat, h.data(), n * 4, hipMemcpyHostToDevice));
-    const size_t packed_bytes = plnerf_mlp_packed_bytes(prec);
-    if (packed_bytes == 0) { std::fprintf(stderr, "precision mode %d is not built\n", prec); return 7; }
-    void* packed;
-    HIP_OK(hipMalloc(&packed, packed_bytes));
-    HIP_OK(hipMemset(packed, 0, packed_bytes));
-    for (int k = 0; k < PLNERF_N_PARAM_TENSORS; ++k) net->params[k] = flat + offs[k];
-    net->packed = packed;
-    return 0;
-}
-
-unsigned long long fnv1a(const void* data, size_t n) {
-    const unsigned char* p = (const unsigned char*)data;
-    unsigned long long h = 0xcbf29ce484222325ull;
-    for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
-    return h;
-}
+constexpr int XYZ = 63, DIR = 27, IMG_H = 16, IMG_W = 12, NS = 64, NI = 128, N_PIX = IMG_H * IMG_W;
 
 // every plane of a frame, back to back on the host: rgb, disp, acc, depth, rgb0, disp0, acc0, depth0, z_std (fp32), rgb8, depth16
 constexpr size_t F32_FLOATS = (size_t)N_PIX * (3 + 1 + 1 + 1 + 3 + 1 + 1 + 1 + 1);
@@ -110,23 +44,15 @@ int main(int argc, char** argv) {
 
     plnerf_view_io io;
     std::memset(&io, 0, sizeof io);
-    int rc = make_net(0, prec, &io.coarse);
-    if (rc) return rc;
-    rc = make_net(1, prec, &io.fine);
+    // each network: parameters from the hash in one flat buffer, and its packed buffer
+    int rc = make_net(hashed_net_values(0, XYZ, DIR), XYZ, DIR, prec, &io.coarse);
+    if (!rc) rc = make_net(hashed_net_values(1, XYZ, DIR), XYZ, DIR, prec, &io.fine);
     if (rc) return rc;
 
-    std::vector<float> tables((size_t)NS + NI);
-    if (argc == 4) {
-        std::FILE* f = std::fopen(argv[3], "rb");
-        if (!f || std::fread(tables.data(), 4, tables.size(), f) != tables.size()) return 4;
-        std::fclose(f);
-    } else {
-        for (int i = 0; i < NS; ++i) tables[i] = (float)i * (1.0f / (float)(NS - 1));
-        for (int i = 0; i < NI; ++i) tables[NS + i] = (float)i * (1.0f / (float)(NI - 1));
-    }
-    float* d_tables;
-    HIP_OK(hipMalloc((void**)&d_tables, tables.size() * 4));
-    HIP_OK(hipMemcpy(d_tables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice));
+    std::vector<float> tables;
+    if (!load_tables(argc == 4 ? argv[3] : nullptr, NS, NI, &tables)) return 4;
+    const float* d_tables = upload(tables);
+    if (!d_tables) return 10;
     io.t_vals = d_tables; io.u_vals = d_tables + NS;
 
     // the frame: every plane in one allocation (each offset a multiple of 4 bytes)
@@ -181,7 +107,7 @@ int main(int argc, char** argv) {
     const plnerf_view_net* nets[2] = {&io.coarse, &io.fine};
     for (int j = 0; j < 2; ++j) {
         uint32_t status;
-        HIP_OK(hipMemcpy(&status, (const unsigned char*)nets[j]->packed + plnerf_mlp_status_offset(prec), 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(&status, status_word(*nets[j], prec), 4, hipMemcpyDeviceToHost));
         if (status) { std::fprintf(stderr, "network %d left the half range (status %u)\n", j, status); return 14; }
     }
     const unsigned char* bytes = frames[0].data();

@@ -9,18 +9,18 @@ The bound is exact, not measured: both routes launch the same kernels with the s
 (tests/test_gpu_one_call.py's argument), and the one kernel that is new, plnerf_fine_epilogue_const_bwd, equals the launches
 it replaces bit for bit (tests/test_gpu_const_bwd.py)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import c_hosts
 from oracle import plnerf_oracle as orc
 from test_gpu_batching import _scene
 from test_gpu_parity import g
 from test_gpu_step import _nets
-from test_gpu_one_call import _Counting, _assert_same_losses, _assert_same_state, _hashed, _settings
+from test_gpu_one_call import _Counting, _assert_same_losses, _assert_same_state, _settings
 from test_gpu_depth_one_call import DEV, V, _args as _depth_args, _assert_same_step, _views
 from test_gpu_depth_one_call import _assert_same_state as _assert_same_depth_state
 
@@ -321,36 +321,20 @@ def test_c_host_runs_the_warm_up_without_python(P, tmp_path):
     plnerf_train_step_const steps and then 2 plnerf_train_step steps on one workspace of max(const, linear) bytes; TrainStep with
     constant_init = 3 on the Python route, from the same hashed weights, image and pose, ends on the same parameters."""
     from plnerf_amd import _lib as L_
-    from plnerf_amd import functional as Fn
-    exe = str(tmp_path / "c_abi_const_step_gpu")
-    libdir = os.path.join(ROOT, "pl-nerf_amd")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                            os.path.join(ROOT, "tests", "c_abi_const_step_gpu.cpp"), "-o", exe, "-L", libdir, "-lplnerf_hip",
-                            "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"],
-                           capture_output=True, text=True, timeout=300)
-    assert build.returncode == 0, build.stderr[-2000:]
+    exe = c_hosts.build("c_abi_const_step_gpu", tmp_path)
     R, Ns, Ni, IMG_H, IMG_W, precision = 64, 16, 24, 40, 48, "f16x3"
-    tables = torch.cat([Fn.cpu_linspace(Ns, "cpu"), Fn.cpu_linspace(Ni, "cpu")])
-    (tmp_path / "tables.bin").write_bytes(tables.numpy().tobytes())
     out_path = tmp_path / "params.bin"
-    run = subprocess.run(["timeout", "-k", "10", "120", exe, str(L_.PRECISION[precision]), str(R), str(Ns), str(Ni), "2", "2",
-                          str(L_.FWD_KERNEL), str(tmp_path / "tables.bin"), str(out_path)], capture_output=True, text=True,
-                         timeout=300)
+    run = c_hosts.run(exe, L_.PRECISION[precision], R, Ns, Ni, 2, 2, L_.FWD_KERNEL,
+                      c_hosts.write_tables(tmp_path / "tables.bin", Ns, Ni), out_path)
     assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-2000:])
-    assert sum(1 for l in run.stdout.split("\n") if l.startswith("step ")) == 4
+    assert len(c_hosts.parse_steps(run.stdout)) == 4
     host = torch.from_numpy(np.fromfile(str(out_path), dtype=np.float32))
 
     args, kw, opt, opt_c = _nets(P, precision, N_samples=Ns, N_importance=Ni, constant_init=3)
     shapes = orc.param_shapes()
     for which, net in enumerate((kw["network_fn"], kw["network_fine"])):
-        sd = {}
-        for k, (name, shape) in enumerate(shapes):
-            fan_in = shape[1] if len(shape) == 2 else dict(shapes)[name.replace("bias", "weight")][1]
-            bound = np.float32(1.0) / np.sqrt(np.float32(fan_in))
-            vals = (np.float32(2.0) * _hashed(100 * which + k, int(np.prod(shape))) - np.float32(1.0)) * bound
-            sd[name] = torch.from_numpy(vals.astype(np.float32)).reshape(*shape)
-        net.load_state_dict(sd)
-    image = g(torch.from_numpy(_hashed(999, IMG_H * IMG_W * 3)).reshape(IMG_H, IMG_W, 3))
+        net.load_state_dict(c_hosts.hashed_state_dict(which, shapes))
+    image = g(torch.from_numpy(c_hosts.hashed(999, IMG_H * IMG_W * 3)).reshape(IMG_H, IMG_W, 3))
     K = [[60.0, 0, 0.5 * IMG_W], [0, 60.0, 0.5 * IMG_H], [0, 0, 1]]
     c2w = torch.tensor([[1.0, 0, 0, 0], [0, 1.0, 0, 0], [0, 0, 1.0, 4.0]])
     ts = P.TrainStep(args, kw, opt, opt_c, start=0, distributed=False, seed=11, range_check_every=0)

@@ -12,13 +12,13 @@ tests/test_gpu_parity.py::test_fused_adam_matches_torch holds for plnerf_adam_st
 expressions, torch's own kernel fusing some of them differently."""
 import ctypes
 import os
-import subprocess
 from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
+import c_hosts
 from oracle import plnerf_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -400,54 +400,27 @@ def test_checkpoint_after_one_call_steps_resumes_on_either_route(P, tmp_path):
 
 
 # ------------------------------------------------------------------------------ 9. the torch-free host
-def _hashed(k, n):
-    """tests/c_abi_depth_step_gpu.cpp's hashed(k, i) for i in [0, n)."""
-    i = np.arange(n, dtype=np.uint32)
-    with np.errstate(over="ignore"):
-        x = i * np.uint32(2654435761) + np.uint32((k * 0x9e3779b9) & 0xffffffff) + np.uint32(12345)
-        x = x * np.uint32(1664525) + np.uint32(1013904223)
-        x ^= x >> np.uint32(15)
-        x = x * np.uint32(1664525) + np.uint32(1013904223)
-    return (x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-
-
 @pytest.mark.parametrize("precision,n_hyp", [("f16x3", 3)])
 def test_c_host_trains_without_python(P, precision, n_hyp, tmp_path):
     """tests/c_abi_depth_step_gpu.cpp -- the HIP runtime and include/plnerf_hip_depthstep.h, nothing else -- runs 3 steps
     through plnerf_depth_train_step; step_view(one_call=True) from the same hashed weights, views and hypotheses meets the
     same losses, parameters, scales and shifts, bit for bit."""
     from plnerf_amd import _lib as L_
-    from plnerf_amd import functional as Fn
-    exe = str(tmp_path / "c_abi_depth_step_gpu")
-    libdir = os.path.join(ROOT, "pl-nerf_amd")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                            os.path.join(ROOT, "tests", "c_abi_depth_step_gpu.cpp"), "-o", exe, "-L", libdir, "-lplnerf_hip",
-                            "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"],
-                           capture_output=True, text=True, timeout=300)
-    assert build.returncode == 0, build.stderr[-2000:]
+    exe = c_hosts.build("c_abi_depth_step_gpu", tmp_path)
     R, Ns, Ni, steps = 256, 64, 32, 3
-    tables = torch.cat([Fn.cpu_linspace(Ns, "cpu"), Fn.cpu_linspace(Ni, "cpu")])
-    (tmp_path / "tables.bin").write_bytes(tables.numpy().tobytes())
-    run = subprocess.run([exe, str(L_.PRECISION[precision]), str(R), str(Ns), str(Ni), str(steps), str(L_.FWD_KERNEL), str(n_hyp),
-                          str(tmp_path / "tables.bin")], capture_output=True, text=True, timeout=300)
+    run = c_hosts.run(exe, L_.PRECISION[precision], R, Ns, Ni, steps, L_.FWD_KERNEL, n_hyp,
+                      c_hosts.write_tables(tmp_path / "tables.bin", Ns, Ni))
     assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-2000:])
-    lines = run.stdout.split("\n")
-    host_losses = [(int(l.split()[3], 16), int(l.split()[5], 16)) for l in lines if l.startswith("step ")]
-    host_sums = [int(x) for x in next(l for l in lines if l.startswith("params ")).split()[1:]]
-    host_ss = [int(x) for x in next(l for l in lines if l.startswith("ss ")).split()[1:]]
+    host_losses = c_hosts.parse_steps(run.stdout)
+    host_sums, host_ss = c_hosts.parse_sums(run.stdout, "params"), c_hosts.parse_sums(run.stdout, "ss")
     assert len(host_losses) == steps
 
     one = _step(P, True, seed=11, load=False, precision=precision, N_samples=Ns, N_importance=Ni, **SS)
     for which, net in enumerate(one.nets):
-        sd, shapes = {}, {name: tuple(t.shape) for name, t in net.state_dict().items()}
+        shapes = [(name, tuple(t.shape)) for name, t in net.state_dict().items()]
         assert len(shapes) == 24
-        for k, (name, shape) in enumerate(shapes.items()):
-            fan_in = shape[1] if len(shape) == 2 else shapes[name.replace("bias", "weight")][1]
-            bound = np.float32(1.0) / np.sqrt(np.float32(fan_in))
-            vals = (np.float32(2.0) * _hashed(100 * which + k, int(np.prod(shape))) - np.float32(1.0)) * bound
-            sd[name] = torch.from_numpy(vals.astype(np.float32)).reshape(*shape)
-        net.load_state_dict(sd)
-    px = V * H * W
+        net.load_state_dict(c_hosts.hashed_state_dict(which, shapes))
+    px, _hashed = V * H * W, c_hosts.hashed
     images = torch.from_numpy(_hashed(999, px * 3)).reshape(V, H, W, 3)
     hyp = torch.from_numpy(np.float32(2.0) + np.float32(4.0) * _hashed(998, px * n_hyp)).reshape(V, n_hyp, H, W)
     valid = torch.from_numpy(_hashed(997, px) > np.float32(0.3)).reshape(V, H, W)
@@ -459,9 +432,8 @@ def test_c_host_trains_without_python(P, precision, n_hyp, tmp_path):
     views = P.DepthViews(images.to(DEV), poses.to(DEV), intr.to(DEV), hyp.to(DEV), valid.to(DEV), 2.0, 6.0)
     ours = [one.step_view(views, k % V, R) for k in range(steps)]
     assert one.one_call_steps == steps and one._ss_steps == steps
-    bits = lambda t: int(t.detach().cpu().view(torch.int32).item()) & 0xffffffff
+    bits, checksum = c_hosts.bits, c_hosts.checksum
     for k, (step, (h_loss, h_carve)) in enumerate(zip(ours, host_losses)):
         assert torch.isfinite(step[0]) and (bits(step[0]), bits(step[2])) == (h_loss, h_carve), (k, float(step[0]), hex(h_loss))
-    checksum = lambda t: int(t.detach().reshape(-1).cpu().view(torch.int32).numpy().view(np.uint32).astype(np.uint64).sum())
     assert [checksum(torch.cat([p.detach().reshape(-1) for p in net.parameters()])) for net in one.nets] == host_sums
     assert [checksum(one.depth_scales), checksum(one.depth_shifts)] == host_ss

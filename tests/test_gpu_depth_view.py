@@ -18,13 +18,13 @@ import ctypes
 import functools
 import math
 import os
-import subprocess
 from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
+import c_hosts
 import containment as C
 import depthview_cases as cases
 import sampleerr_fp64 as ref64
@@ -581,26 +581,13 @@ def test_guard_bands(build):
 
 
 # ----------------------------------------------------------------------------- a host without Python
-def _fnv1a(data):
-    h = 0xcbf29ce484222325
-    for b in data:
-        h = ((h ^ b) * 0x100000001b3) & 0xffffffffffffffff
-    return h
-
-
 @pytest.mark.parametrize("precision", ["f16x3"])
 def test_c_host_renders_without_python(P, precision, tmp_path):
     """tests/c_abi_depth_view_gpu.cpp -- the HIP runtime and the experimental header, nothing else -- renders the 9 x 13 view
     in blocks of 32 from the tables written here; DepthViewRenderer on the same inputs produces the same bytes."""
     from plnerf_amd import _lib as L_
     from plnerf_amd import functional as Fn
-    exe = str(tmp_path / "c_abi_depth_view_gpu")
-    libdir = os.path.join(ROOT, "pl-nerf_amd")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                            os.path.join(ROOT, "tests", "c_abi_depth_view_gpu.cpp"), "-o", exe, "-L", libdir, "-lplnerf_hip",
-                            "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"],
-                           capture_output=True, text=True, timeout=300)
-    assert build.returncode == 0, build.stderr[-2000:]
+    exe = c_hosts.build("c_abi_depth_view_gpu", tmp_path)
     kw = _kwargs(precision, **CASES["white_bkgd"])
     valid = _masks()["random"]
     blobs = []
@@ -611,10 +598,9 @@ def test_c_host_renders_without_python(P, precision, tmp_path):
     blobs += [Fn.cpu_linspace(NS, "cpu").numpy().tobytes(), Fn.cpu_linspace(NI, "cpu").numpy().tobytes(),
               valid.to(torch.uint8).numpy().tobytes()]
     (tmp_path / "inputs.bin").write_bytes(b"".join(blobs))
-    run = subprocess.run(["timeout", "-k", "10", "120", exe, str(L_.PRECISION[precision]), str(L_.FWD_KERNEL),
-                          str(tmp_path / "inputs.bin")], capture_output=True, text=True)
+    run = c_hosts.run(exe, L_.PRECISION[precision], L_.FWD_KERNEL, tmp_path / "inputs.bin")
     assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-2000:])      # (no retry)
-    host = {line.split()[0]: int(line.split()[1], 16) for line in run.stdout.split("\n") if line.strip()}
+    host = c_hosts.parse_planes(run.stdout)
 
     c2w = torch.tensor([[0.8, -0.6, 0.0, 0.1], [0.6, 0.8, 0.0, -0.2], [0.0, 0.0, 1.0, 4.0]])
     vr = _renderer(P, kw, 32, seed=11)
@@ -624,4 +610,4 @@ def test_c_host_renders_without_python(P, precision, tmp_path):
     mine.update(pred_hyp=vr.pred_hyp, rgb8=vr.rgb8, depth16=vr.depth16, depth_mm16=vr.depth_mm16, error_row=vr.error_row)
     assert set(host) == set(mine)
     for name, t in mine.items():
-        assert _fnv1a(t.cpu().numpy().tobytes()) == host[name], name
+        assert c_hosts.fnv1a(t.cpu().numpy().tobytes()) == host[name], name

@@ -9,12 +9,11 @@ The bound is exact, not measured: both routes launch the same kernels with the s
 test_training_step_is_bitwise_reproducible and test_weight_gradients_do_not_depend_on_what_the_workspace_held establish
 that those kernels are deterministic and indifferent to what their workspace held."""
 import os
-import subprocess
 
-import numpy as np
 import pytest
 import torch
 
+import c_hosts
 from oracle import plnerf_oracle as orc
 from test_gpu_batching import _scene
 from test_gpu_parity import g
@@ -347,60 +346,31 @@ def test_plan_follows_buffers_that_move(P):
     assert one.one_call_steps == 3
 
 
-def _hashed(k, n):
-    """tests/c_abi_step_gpu.cpp's hashed(k, i) for i in [0, n)."""
-    i = np.arange(n, dtype=np.uint32)
-    with np.errstate(over="ignore"):
-        x = i * np.uint32(2654435761) + np.uint32((k * 0x9e3779b9) & 0xffffffff) + np.uint32(12345)
-        x = x * np.uint32(1664525) + np.uint32(1013904223)
-        x ^= x >> np.uint32(15)
-        x = x * np.uint32(1664525) + np.uint32(1013904223)
-    return (x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-
-
 @pytest.mark.parametrize("precision", ["f16x3"])
 def test_c_host_trains_without_python(P, precision, tmp_path):
     """tests/c_abi_step_gpu.cpp -- the HIP runtime and include/plnerf_hip_step.h, nothing else -- runs 5 steps through
     plnerf_train_step; the Python one-call route from the same hashed weights, image and pose meets the same losses and
     parameters, bit for bit (the same entry on the same inputs)."""
     from plnerf_amd import _lib as L_
-    from plnerf_amd import functional as Fn
-    exe = str(tmp_path / "c_abi_step_gpu")
-    libdir = os.path.join(ROOT, "pl-nerf_amd")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                            os.path.join(ROOT, "tests", "c_abi_step_gpu.cpp"), "-o", exe, "-L", libdir, "-lplnerf_hip",
-                            "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"],
-                           capture_output=True, text=True, timeout=300)
-    assert build.returncode == 0, build.stderr[-2000:]
+    exe = c_hosts.build("c_abi_step_gpu", tmp_path)
     R, Ns, Ni, IMG_H, IMG_W = 256, 64, 128, 40, 48
-    tables = torch.cat([Fn.cpu_linspace(Ns, "cpu"), Fn.cpu_linspace(Ni, "cpu")])
-    (tmp_path / "tables.bin").write_bytes(tables.numpy().tobytes())
-    run = subprocess.run([exe, str(L_.PRECISION[precision]), str(R), str(Ns), str(Ni), str(STEPS), str(L_.FWD_KERNEL),
-                          str(tmp_path / "tables.bin")], capture_output=True, text=True, timeout=300)
+    run = c_hosts.run(exe, L_.PRECISION[precision], R, Ns, Ni, STEPS, L_.FWD_KERNEL,
+                      c_hosts.write_tables(tmp_path / "tables.bin", Ns, Ni))
     assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-2000:])
-    lines = run.stdout.split("\n")
-    host_losses = [(int(l.split()[3], 16), int(l.split()[5], 16)) for l in lines if l.startswith("step ")]
-    host_sums = [int(x) for x in next(l for l in lines if l.startswith("params ")).split()[1:]]
+    host_losses, host_sums = c_hosts.parse_steps(run.stdout), c_hosts.parse_sums(run.stdout, "params")
     assert len(host_losses) == STEPS
 
     args, kw, opt, opt_c = _nets(P, precision, N_samples=Ns, N_importance=Ni)
     for which, net in enumerate((kw["network_fn"], kw["network_fine"])):
-        sd = {}
-        for k, (name, shape) in enumerate(orc.param_shapes()):
-            fan_in = shape[1] if len(shape) == 2 else dict(orc.param_shapes())[name.replace("bias", "weight")][1]
-            bound = np.float32(1.0) / np.sqrt(np.float32(fan_in))
-            vals = (np.float32(2.0) * _hashed(100 * which + k, int(np.prod(shape))) - np.float32(1.0)) * bound
-            sd[name] = torch.from_numpy(vals.astype(np.float32)).reshape(*shape)
-        net.load_state_dict(sd)
-    image = g(torch.from_numpy(_hashed(999, IMG_H * IMG_W * 3)).reshape(IMG_H, IMG_W, 3))
+        net.load_state_dict(c_hosts.hashed_state_dict(which, orc.param_shapes()))
+    image = g(torch.from_numpy(c_hosts.hashed(999, IMG_H * IMG_W * 3)).reshape(IMG_H, IMG_W, 3))
     K = [[60.0, 0, 0.5 * IMG_W], [0, 60.0, 0.5 * IMG_H], [0, 0, 1]]
     c2w = torch.tensor([[1.0, 0, 0, 0], [0, 1.0, 0, 0], [0, 0, 1.0, 4.0]])
     ts = P.TrainStep(args, kw, opt, opt_c, start=0, distributed=False, seed=11, one_call=True, range_check_every=0)
     ours = [ts.step_view(IMG_H, IMG_W, K, c2w, image, near=2.0, far=6.0, n_rand=R) for _ in range(STEPS)]
     assert ts.one_call_steps == STEPS
-    bits = lambda t: int(t.detach().cpu().view(torch.int32).item()) & 0xffffffff
+    bits = c_hosts.bits
     for k, ((loss, psnr), (h_loss, h_psnr)) in enumerate(zip(ours, host_losses)):
         assert torch.isfinite(loss) and (bits(loss), bits(psnr)) == (h_loss, h_psnr), (k, float(loss), hex(h_loss))
-    sums = [int(torch.cat([p.detach().reshape(-1) for p in net.parameters()]).cpu().view(torch.int32).numpy().view(np.uint32)
-                .astype(np.uint64).sum()) for net in ts.nets]
+    sums = [c_hosts.checksum(torch.cat([p.detach().reshape(-1) for p in net.parameters()])) for net in ts.nets]
     assert sums == host_sums

@@ -449,15 +449,8 @@ def test_c_host_without_torch(P, precision, tmp_path):
     piecewise-linear quadrature, both backwards and one Adam step on device memory it allocated itself; its outputs are
     compared with the oracle (forward 1e-5; gradients at the bounds of test_mlp_fwd_bwd_vs_oracle / test_mlp_bf16_modes) and
     with the Python mirror's on the same inputs (the same kernels: bit for bit)."""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "c_abi_gpu")
-    libdir = os.path.join(root, "pl-nerf_amd")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"), "-I", "/opt/rocm/include",
-                            os.path.join(root, "tests", "c_abi_gpu.cpp"), "-o", exe, "-L", libdir, "-lplnerf_hip",
-                            "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
+    import c_hosts
+    exe = c_hosts.build("c_abi_gpu", tmp_path)
     R, S = 37, 50                                  # (1850 rows: ragged against every tile size)
     gen = torch.Generator().manual_seed(4242)
     pts = (torch.rand(R, S, 3, generator=gen) * 2 - 1) * 2.5
@@ -473,8 +466,7 @@ def test_c_host_without_torch(P, precision, tmp_path):
             f.write(t.contiguous().float().numpy().tobytes())
     prec = {"fp32": 0, "f16x3": 3}[precision]      # PLNERF_PREC_*
     from plnerf_amd import _lib as L_
-    run = subprocess.run([exe, str(prec), str(R), str(S), str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), str(L_.FWD_KERNEL)],
-                         capture_output=True, text=True, timeout=300)
+    run = c_hosts.run(exe, prec, R, S, tmp_path / "in.bin", tmp_path / "out.bin", L_.FWD_KERNEL)
     assert run.returncode == 0, (run.returncode, run.stderr[-2000:])
     out = np.fromfile(tmp_path / "out.bin", dtype=np.float32)
     pos = [0]

@@ -9,14 +9,13 @@ through the call; render_path_frames' files; and tests/c_abi_view_gpu.cpp, which
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import c_hosts
 from oracle import plnerf_oracle as orc
-from test_gpu_one_call import _hashed
 from test_gpu_parity import dev, g
 from test_gpu_step import _nets
 
@@ -392,46 +391,23 @@ def test_render_path_frames_writes_the_frames(P, tmp_path):
 
 
 # ----------------------------------------------------------------------------- a host without Python
-def _fnv1a(data):
-    h = 0xcbf29ce484222325
-    for b in data:
-        h = ((h ^ b) * 0x100000001b3) & 0xffffffffffffffff
-    return h
-
-
 @pytest.mark.parametrize("precision", ["f16x3"])
 def test_c_host_renders_without_python(P, precision, tmp_path):
     """tests/c_abi_view_gpu.cpp -- the HIP runtime and include/plnerf_hip_view.h, nothing else -- renders a 16 x 12 view in
     blocks of 64 and of 192 pixels and checks them byte-identical and finite itself; ViewRenderer on the same hashed
     weights and pose produces the same bytes (the same entry on the same inputs)."""
     from plnerf_amd import _lib as L_
-    from plnerf_amd import functional as Fn
     from plnerf_amd.view import depth16_numpy
-    exe = str(tmp_path / "c_abi_view_gpu")
-    libdir = os.path.join(ROOT, "pl-nerf_amd")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                            os.path.join(ROOT, "tests", "c_abi_view_gpu.cpp"), "-o", exe, "-L", libdir, "-lplnerf_hip",
-                            "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"],
-                           capture_output=True, text=True, timeout=300)
-    assert build.returncode == 0, build.stderr[-2000:]
+    exe = c_hosts.build("c_abi_view_gpu", tmp_path)
     Ns, Ni, IMG_H, IMG_W = 64, 128, 16, 12
-    tables = torch.cat([Fn.cpu_linspace(Ns, "cpu"), Fn.cpu_linspace(Ni, "cpu")])
-    (tmp_path / "tables.bin").write_bytes(tables.numpy().tobytes())
-    run = subprocess.run([exe, str(L_.PRECISION[precision]), str(L_.FWD_KERNEL), str(tmp_path / "tables.bin")],
-                         capture_output=True, text=True, timeout=300)
+    run = c_hosts.run(exe, L_.PRECISION[precision], L_.FWD_KERNEL, c_hosts.write_tables(tmp_path / "tables.bin", Ns, Ni))
     assert run.returncode == 0, (run.returncode, run.stdout[-2000:], run.stderr[-2000:])
-    host = {line.split()[0]: int(line.split()[1], 16) for line in run.stdout.split("\n") if line.strip()}
+    host, _fnv1a = c_hosts.parse_planes(run.stdout), c_hosts.fnv1a
     assert set(host) == {"rgb8", "rgb", "depth16"}
 
     _, kw, _, _ = _nets(P, precision, N_samples=Ns, N_importance=Ni)
     for which, net in enumerate((kw["network_fn"], kw["network_fine"])):
-        sd = {}
-        for k, (name, shape) in enumerate(orc.param_shapes()):
-            fan_in = shape[1] if len(shape) == 2 else dict(orc.param_shapes())[name.replace("bias", "weight")][1]
-            bound = np.float32(1.0) / np.sqrt(np.float32(fan_in))
-            vals = (np.float32(2.0) * _hashed(100 * which + k, int(np.prod(shape))) - np.float32(1.0)) * bound
-            sd[name] = torch.from_numpy(vals.astype(np.float32)).reshape(*shape)
-        net.load_state_dict(sd)
+        net.load_state_dict(c_hosts.hashed_state_dict(which, orc.param_shapes()))
     kw = dict(kw, mode="linear", color_mode="midpoint", perturb=1.0, white_bkgd=True, raw_noise_std=0.0)
     kw.pop("ndc", None)
     K = [[20.0, 0, 0.5 * IMG_W], [0, 21.0, 0.5 * IMG_H], [0, 0, 1]]
