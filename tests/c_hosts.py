@@ -42,6 +42,14 @@ def hashed(k, n):
     return (x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
 
 
+def step_scene(img_h, img_w):
+    """The one view tests/c_abi_step_gpu.cpp and tests/c_abi_const_step_gpu.cpp train on, on the host: (K, c2w [3, 4], the
+    image [img_h, img_w, 3] of hashed(999, .))."""
+    K = [[60.0, 0, 0.5 * img_w], [0, 60.0, 0.5 * img_h], [0, 0, 1]]
+    c2w = torch.tensor([[1.0, 0, 0, 0], [0, 1.0, 0, 0], [0, 0, 1.0, 4.0]])
+    return K, c2w, torch.from_numpy(hashed(999, img_h * img_w * 3)).reshape(img_h, img_w, 3)
+
+
 def hashed_state_dict(which, shapes):
     """tests/c_abi_host.h's hashed_net_values(which, ...) as a state_dict; `shapes` is the ordered (name, shape) list."""
     by_name, sd = dict(shapes), {}

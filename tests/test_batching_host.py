@@ -1,21 +1,15 @@
 """Host-side logic of the use_batching ray source (no GPU): the epoch schedule of RayBank against the reference's
 i_batch loop (run_plnerf.py:1238-1249), and dp.shard_batch's balanced split of a global batch of any size."""
-import os
-import sys
-
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import abi_support as abi
 
 
 @pytest.fixture(scope="module")
-def P():
-    import __graft_entry__ as ge
-    if not os.path.exists(os.path.join(ROOT, "pl-nerf_amd", "libplnerf_hip.so")):
-        ge.build()
+def built():
+    """The package, with the library built first if it is absent (no GPU needed)."""
+    abi.built_lib()
     import plnerf_amd
     return plnerf_amd
 
@@ -36,16 +30,16 @@ def _reference_walk(M, N_rand, epochs):
 
 @pytest.mark.parametrize("M,B", [(612, 50), (612, 51), (612, 612), (612, 700), (100, 1), (7, 3), (1024, 256),
                                  (3 * 12 * 17, 4096), (513, 128), (578, 192)])
-def test_schedule_is_the_reference_i_batch_loop(P, M, B):
+def test_schedule_is_the_reference_i_batch_loop(built, M, B):
     images = torch.zeros(1, 1, M, 3)
     poses = torch.eye(4)[None]
-    bank = P.RayBank(images, poses, [[1.0, 0, 0], [0, 1.0, 0], [0, 0, 1]], [0], 0.0, 1.0, device="cpu")
+    bank = built.RayBank(images, poses, [[1.0, 0, 0], [0, 1.0, 0], [0, 0, 1]], [0], 0.0, 1.0, device="cpu")
     assert bank.M == M
     walk = list(_reference_walk(M, B, 3))
     assert walk[-1][0] == 2 and sum(n for _, _, n in walk) == 3 * M
     for g, want in enumerate(walk):
         assert bank.schedule(g, B) == want, (g, bank.schedule(g, B), want)
-        assert P.batch_schedule(g, M, B) == want
+        assert built.batch_schedule(g, M, B) == want
     # stateless: any step on its own, far past the start (a resumed run), is the walk's
     S = -(-M // B)
     for g in (10 * S, 10 * S + S - 1, 123457):
@@ -53,28 +47,28 @@ def test_schedule_is_the_reference_i_batch_loop(P, M, B):
         assert e == g // S and p0 == (g % S) * B and n == min(B, M - p0) and 0 < n <= B
 
 
-def test_bank_from_training_views(P):
+def test_bank_from_training_views(built):
     images = torch.rand(5, 12, 17, 3)
     poses = torch.eye(4).repeat(5, 1, 1)
-    bank = P.RayBank(images, poses, [[20.0, 0, 8.5], [0, 20.0, 6], [0, 0, 1]], [0, 2, 4], 0.0, 1.0, seed=3, device="cpu")
+    bank = built.RayBank(images, poses, [[20.0, 0, 8.5], [0, 20.0, 6], [0, 0, 1]], [0, 2, 4], 0.0, 1.0, seed=3, device="cpu")
     assert bank.M == 3 * 12 * 17 and bank.poses.shape == (5, 12) and bank.views.dtype == torch.int32
     assert bank.views.tolist() == [0, 2, 4]
-    t, r, c = P.RayBank.decode(torch.tensor([0, 17, 12 * 17, 2 * 12 * 17 + 5 * 17 + 16]), 12, 17)
+    t, r, c = built.RayBank.decode(torch.tensor([0, 17, 12 * 17, 2 * 12 * 17 + 5 * 17 + 16]), 12, 17)
     assert t.tolist() == [0, 0, 1, 2] and r.tolist() == [0, 1, 0, 5] and c.tolist() == [0, 0, 0, 16]
     with pytest.raises(ValueError):
-        P.RayBank(images, poses, bank.K, [0, 5], 0.0, 1.0, device="cpu")
+        built.RayBank(images, poses, bank.K, [0, 5], 0.0, 1.0, device="cpu")
     with pytest.raises(ValueError):
-        P.RayBank(images, poses, bank.K, [], 0.0, 1.0, device="cpu")
+        built.RayBank(images, poses, bank.K, [], 0.0, 1.0, device="cpu")
 
 
-def test_step_batch_refuses_precrop(P):
-    ts = P.TrainStep.__new__(P.TrainStep)
+def test_step_batch_refuses_precrop(built):
+    ts = built.TrainStep.__new__(built.TrainStep)
     with pytest.raises(ValueError, match="precrop"):
         ts.step_batch(None, 16, precrop=(4, 4))
 
 
 @pytest.mark.parametrize("world", [1, 2, 3, 4, 7, 8])
-def test_shard_batch_is_contiguous_balanced_and_covers_the_batch(P, world):
+def test_shard_batch_is_contiguous_balanced_and_covers_the_batch(built, world):
     from plnerf_amd import dp
     for n in list(range(0, 40)) + [4095, 4096, 32768, 32769]:
         parts = [dp.shard_batch(n, r, world) for r in range(world)]

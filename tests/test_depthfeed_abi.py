@@ -5,12 +5,12 @@ run_nerf_sample_based_depth.py:1104-1161, and the depth checkpoint's wire format
 import os
 import re
 import subprocess
-from argparse import Namespace
 
 import pytest
 import torch
 
 import abi_support as abi
+from run_args import depth_args
 
 HEADER = os.path.join(abi.INCLUDE, "plnerf_hip_depthfeed.h")
 
@@ -84,13 +84,8 @@ def _reference_lr(optimizer_lr, i, lrate, start_decay_lrate, end_decay_lrate):
 
 
 def _depth_args(tmp, **over):
-    a = dict(multires=9, i_embed=0, use_viewdirs=True, multires_views=0, input_ch_cam=0, N_importance=64, N_samples=128,
-             netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, perturb=1.0,
-             white_bkgd=True, raw_noise_std=0.0, mode="linear", color_mode="midpoint", lindisp=False, no_reload=True,
-             space_carving_weight=0.007, warm_start_nerf=0, is_joint=False, norm_p=2, space_carving_threshold=0.0,
-             precision="fp32", bb_center=0.0, bb_scale=1.0, ckpt_dir=str(tmp), expname="exp", ft_path=None, N_rand=64)
-    a.update(over)
-    return Namespace(**a)
+    at = dict(N_importance=64, N_samples=128, precision="fp32", ckpt_dir=str(tmp), expname="exp", ft_path=None, N_rand=64)
+    return depth_args(**dict(at, **over))
 
 
 @pytest.mark.parametrize("s,e", [(400000, 500000), (10, 30), (7, 8)])

@@ -9,37 +9,16 @@ import sys
 import pytest
 import torch
 
+from abi_support import ROOT
+from gpu_support import P, g, nvs_nets, scene
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import g
-from test_gpu_step import _nets
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-def _scene(P, n_views, H, W, forward_facing=False, seed=0):
-    gen = torch.Generator().manual_seed(seed)
-    if forward_facing:
-        poses = torch.eye(4).repeat(n_views, 1, 1)
-        for i in range(n_views):
-            poses[i, :3, 3] = torch.tensor([0.05 * i - 0.1, 0.02 * i, 0.1])
-            poses[i, :3, :3] += 0.01 * torch.randn(3, 3, generator=gen)
-    else:
-        poses = torch.stack([P.rays.pose_spherical(-180.0 + 360.0 * i / n_views + 7.0, -30.0 + 3.0 * i, 4.0)
-                             for i in range(n_views)])
-    images = torch.rand(n_views, H, W, 3, generator=gen)
-    K = [[1.3 * W + 0.37, 0, W / 2 - 0.25], [0, 1.3 * W - 0.61, H / 2 + 0.5], [0, 0, 1]]
-    return poses, images, K
-
-
 def test_bank_rays_are_get_rays_of_the_training_views(P):
     H, W, i_train = 12, 17, [4, 1, 3]
-    poses, images, K = _scene(P, 5, H, W)
+    poses, images, K = scene(P, 5, H, W)
     bank = P.RayBank(images, poses, K, i_train, 2.0, 6.0, seed=7)
     assert bank.M == 3 * H * W
     cols, target, idx = bank.select(0, 0, bank.M, want_index=True)
@@ -77,7 +56,7 @@ def test_bank_rays_are_get_rays_of_the_training_views(P):
 
 def test_one_epoch_is_a_permutation_with_a_short_tail(P):
     H, W = 12, 17
-    poses, images, K = _scene(P, 3, H, W)
+    poses, images, K = scene(P, 3, H, W)
     bank = P.RayBank(g(images), poses, K, [0, 1, 2], 0.0, 1.0, seed=2)
     M, n_rand = 612, 50
     assert bank.M == M
@@ -108,14 +87,14 @@ def test_step_batch_equals_call_on_the_same_columns(P, precision, dataset):
     H, W = 10, 13
     llff = dataset == "llff"
     over = dict(dataset=dataset, white_bkgd=not llff, raw_noise_std=1.0 if llff else 0.0)
-    poses, images, K = _scene(P, 5, H, W, forward_facing=llff, seed=3)
+    poses, images, K = scene(P, 5, H, W, forward_facing=llff, seed=3)
     near, far = (0.0, 1.0) if llff else (2.0, 6.0)
     bank = P.RayBank(images, poses, K, [0, 2, 3], near, far, seed=5)
     n_rand, start = 128, 2                   # M = 390: steps 2, 3, 4 take 128, 6 and (epoch 1) 128 rays
-    args, kw, opt, opt_c = _nets(P, precision, **over)
+    args, kw, opt, opt_c = nvs_nets(P, precision, **over)
     assert bool(kw.get("ndc", True)) == llff
     ts = P.TrainStep(args, kw, opt, opt_c, start=start, distributed=False, seed=5)
-    args2, kw2, opt2, opt_c2 = _nets(P, precision, **over)
+    args2, kw2, opt2, opt_c2 = nvs_nets(P, precision, **over)
     ts2 = P.TrainStep(args2, kw2, opt2, opt_c2, start=start, distributed=False, seed=5)
     sizes = []
     for step in range(start, start + 3):
@@ -135,15 +114,15 @@ def test_step_batch_equals_call_on_the_same_columns(P, precision, dataset):
 
 def test_resume_continues_the_same_order(P):
     H, W = 10, 13
-    poses, images, K = _scene(P, 5, H, W)
+    poses, images, K = scene(P, 5, H, W)
     bank = P.RayBank(images, poses, K, [1, 2, 4], 2.0, 6.0, seed=9)
     n_rand, s = 128, 5                       # M = 390, 4 steps per epoch: step 5 is position 128 of epoch 1
-    args, kw, opt, opt_c = _nets(P)
+    args, kw, opt, opt_c = nvs_nets(P)
     ts = P.TrainStep(args, kw, opt, opt_c, distributed=False, seed=9)
     for _ in range(s + 1):
         ts.step_batch(bank, n_rand)
     from_zero = ts.last_batch
-    args2, kw2, opt2, opt_c2 = _nets(P)
+    args2, kw2, opt2, opt_c2 = nvs_nets(P)
     ts2 = P.TrainStep(args2, kw2, opt2, opt_c2, start=s, distributed=False, seed=9)
     ts2.step_batch(bank, n_rand)
     assert ts2.last_batch == from_zero == (1, 128, 128, 0, 128)
@@ -159,7 +138,7 @@ sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import plnerf_amd as P
 from plnerf_amd import dp
 from oracle import plnerf_oracle as orc
-from test_gpu_step import _args
+from run_args import nvs_args
 VIEWS = [int(v) for v in sys.argv[2].split(",")]
 H, W, N_RAND, START, STEPS = int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), int(sys.argv[6]), 3
 BOUND = float(sys.argv[7])
@@ -170,7 +149,7 @@ torch.cuda.set_device(0)
 
 def make(distributed):
     d = tempfile.mkdtemp(); os.makedirs(os.path.join(d, "exp"))
-    args = _args(d, "f16x3", chunk=32768)
+    args = nvs_args(d, "f16x3", N_rand=256)
     kw, _, _, _, opt, opt_c = P.create_nerf(args, device=dev)
     kw["network_fn"].load_state_dict(orc.closed_form_state_dict(0, False))
     kw["network_fine"].load_state_dict(orc.closed_form_state_dict(1, False))
@@ -264,7 +243,6 @@ def test_data_parallel_batches_across_a_short_tail(P, tmp_path, world, views, H,
     boundary whose last batch is shorter than the world: replicas stay bit-identical, the rank without rays sends an
     exactly zero gradient into the same single collective, and the weights land within `bound` of one process stepping
     the whole global batch."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "dp_batch_worker.py"
     script.write_text(_DP_BATCH_WORKER)
     port = 30300 + (os.getpid() % 200) + 200 * (world > 2)
@@ -272,7 +250,7 @@ def test_data_parallel_batches_across_a_short_tail(P, tmp_path, world, views, H,
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(script), root, views, str(H), str(W), str(n_rand), str(start),
+        procs.append(subprocess.Popen([sys.executable, str(script), ROOT, views, str(H), str(W), str(n_rand), str(start),
                                        str(bound)],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     try:

@@ -23,20 +23,12 @@ import camcode_cases as cases
 import camopt_fp64 as R
 import containment as C
 from camopt_fp64 import CODE_TOL, GRAD_BOUND, LOSS_BOUND
+from gpu_support import P, dev      # (not its helper g: `g` is this file's fixture)
+from run_args import depth_args
 
 pytestmark = pytest.mark.gpu
 GENERIC_TOL = 1e-5      # tests/test_gpu_modes.py: the generic route against fp64, times (1 + max |reference|)
 BOUNDS = {}             # what the sweep cases measured; written to $PLNERF_CAMCODE_BOUNDS_OUT when that is set
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
 
 
 @pytest.fixture(scope="module")
@@ -131,12 +123,9 @@ def test_sweep_zero_rays_and_refusals(P):
 
 # ----------------------------------------------------------------------------- the fixture's scene on the device
 def _args(**over):
-    a = dict(multires=9, i_embed=0, use_viewdirs=True, multires_views=0, input_ch_cam=4, N_importance=8, N_samples=8,
-             netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, perturb=0.0,
-             white_bkgd=True, raw_noise_std=0.0, mode="linear", color_mode="midpoint", lindisp=False, no_reload=True,
-             precision="fp32", bb_center=0.0, bb_scale=1.0, chunk=1024, N_rand=6, dataset="scannet")
-    a.update(over)
-    return Namespace(**a)
+    """The fixture's run: a 4-wide camera code, 8 + 8 samples without jitter, exact fp32; no loss fields."""
+    at = dict(input_ch_cam=4, N_importance=8, N_samples=8, perturb=0.0, precision="fp32", chunk=1024, N_rand=6, dataset="scannet")
+    return depth_args(train=False, **dict(at, **over))
 
 
 def _fixture_scene(P, g, **over):

@@ -8,8 +8,9 @@ import sys
 
 import pytest
 
+from abi_support import ROOT
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("tool,cases,extra", [

@@ -15,7 +15,7 @@ n = S - 2 and of the quadrature's n = S; N in {1, 5, 64, 65}; R in {1, 5, 8}, wh
 import pytest
 import torch
 
-from test_gpu_parity import dev, g, quad_case
+from gpu_support import dev, g, quad_case
 
 pytestmark = pytest.mark.gpu
 GROUP = 4      # PLNERF_QUAD_RAYS_PER_GROUP

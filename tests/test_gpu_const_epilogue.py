@@ -12,8 +12,10 @@ import sys
 import pytest
 import torch
 
+from gpu_support import (P, assert_close, assert_same_losses, assert_same_nvs_state, depth_nets, dev, g, make_net, maxdiff,
+                         nvs_nets, quad_case, scene)
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import assert_close, dev, g, make_net, maxdiff, quad_case
+from run_args import depth_args_of
 
 pytestmark = pytest.mark.gpu
 R_DEFAULT = 133      # (four rays per workgroup: the last one is ragged)
@@ -21,16 +23,9 @@ ZSTD = dict(atol=2e-6, rtol=2e-6)
 
 
 @pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-@pytest.fixture(scope="module")
 def Fn(P):
     from plnerf_amd import functional
     return functional
-
 
 
 def _same(a, b):
@@ -277,13 +272,9 @@ def test_render_rays_takes_the_one_launch_route_and_equals_the_separate_one(P, F
 # ----------------------------------------------------------------------------- depth.render_rays
 def _depth_kw(golden, precision):
     """The depth variant's two networks (closed-form weights) at 16 + 24 samples in constant mode."""
-    from test_gpu_modes import _depth_args
     from plnerf_amd import depth as Dp
-    args = _depth_args(golden("g8b_depth_variant_128_64"), precision)
-    args.N_samples, args.N_importance, args.mode = 16, 24, "constant"
-    kw, _, _, grad_vars, opt = Dp.create_nerf(args, device=dev())
-    kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
-    kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, True))
+    args = depth_args_of(golden("g8b_depth_variant_128_64"), precision, N_samples=16, N_importance=24, mode="constant")
+    kw, _, _, grad_vars, opt = depth_nets(args)
     return Dp, args, kw, grad_vars, opt
 
 
@@ -366,16 +357,13 @@ def test_depth_render_rays_constant_mode_gradients(P, Fn, golden):
 def test_train_step_through_the_constant_init_warm_up(P, Fn, precision):
     """constant_init = 3: the first steps render in constant mode (i < constant_init), the rest in linear mode.  Five steps
     of 64 rays at 16 + 24 samples with the switch on and off: the same run (f16x3: the merged backward; fp32: autograd's)."""
-    from test_gpu_batching import _scene
-    from test_gpu_one_call import _assert_same_losses, _assert_same_state
-    from test_gpu_step import _nets
     Rd = _render_module()
     H, W = 20, 26
-    poses, images, K = _scene(P, 4, H, W, seed=3)
+    poses, images, K = scene(P, 4, H, W, seed=3)
     images = g(images)
     pair = []
     for _ in range(2):
-        args, kw, opt, opt_c = _nets(P, precision, N_samples=16, N_importance=24, constant_init=3)
+        args, kw, opt, opt_c = nvs_nets(P, precision, N_samples=16, N_importance=24, constant_init=3)
         pair.append(P.TrainStep(args, kw, opt, opt_c, distributed=False, seed=5, one_call=False, range_check_every=0))
     logs = ([], [])
     for k in range(5):
@@ -385,8 +373,8 @@ def test_train_step_through_the_constant_init_warm_up(P, Fn, precision):
                 log.append(ts.step_view(H, W, K, poses[k % 4][:3, :4], images[k % 4], near=2.0, far=6.0, n_rand=64))
             finally:
                 Rd.FUSE_CONST_EPILOGUE = True
-    _assert_same_losses(logs)
-    _assert_same_state(pair[0], pair[1], f"constant_init {precision}")
+    assert_same_losses(logs)
+    assert_same_nvs_state(pair[0], pair[1], f"constant_init {precision}")
     assert pair[0].one_call_steps == 0 and pair[0].merged_steps == (5 if precision == "f16x3" else 0)
 
 

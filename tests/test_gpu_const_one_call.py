@@ -16,16 +16,12 @@ import pytest
 import torch
 
 import c_hosts
+from gpu_support import (P, assert_same_depth_state, assert_same_depth_step, assert_same_losses, assert_same_nvs_state,
+                         counting_calls, depth_step, depth_views, g, kernel_timer, nvs_nets, scene, settings)
 from oracle import plnerf_oracle as orc
-from test_gpu_batching import _scene
-from test_gpu_parity import g
-from test_gpu_step import _nets
-from test_gpu_one_call import _Counting, _assert_same_losses, _assert_same_state, _settings
-from test_gpu_depth_one_call import DEV, V, _args as _depth_args, _assert_same_step, _views
-from test_gpu_depth_one_call import _assert_same_state as _assert_same_depth_state
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+V = 3      # (gpu_support.depth_views' default)
 STEPS = 4
 # (rays, N_samples, N_importance): the sampler's smallest row (one interior weight) on a batch that is no multiple of the
 # 4-ray workgroup; one wave per row; several workgroups of every kernel and a second 64-lane pass of the final quadrature
@@ -33,14 +29,8 @@ SHAPES = [(37, 3, 5), (64, 16, 24), (256, 64, 32)]
 H, W, PRECROP = 20, 26, (8, 9)      # 16 x 18 = 288 pixels inside the precrop window: every batch above fits
 
 
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
 def _make(P, precision, flags, start=0, seed=5, **over):
-    args, kw, opt, opt_c = _nets(P, precision, **over)
+    args, kw, opt, opt_c = nvs_nets(P, precision, **over)
     return P.TrainStep(args, kw, opt, opt_c, start=start, distributed=False, seed=seed, range_check_every=0, **flags)
 
 
@@ -50,7 +40,7 @@ def _pair(P, precision, flags=None, **over):
 
 
 def _run_views(P, pair, R, llff=False, near=2.0, far=6.0, steps=STEPS, crop_steps=2, each_step=None):
-    poses, images, K = _scene(P, 4, H, W, forward_facing=llff, seed=3)
+    poses, images, K = scene(P, 4, H, W, forward_facing=llff, seed=3)
     images = g(images)
     logs = ([], [])
     for k in range(steps):
@@ -68,8 +58,8 @@ def _run_views(P, pair, R, llff=False, near=2.0, far=6.0, steps=STEPS, crop_step
 def test_step_view_in_constant_mode_is_the_python_route_bit_for_bit(P, precision, R, Ns, Ni):
     one, ref = _pair(P, precision, mode="constant", N_samples=Ns, N_importance=Ni)
     logs = _run_views(P, (one, ref), R)
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, "step_view")
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, "step_view")
     assert one.one_call_const_steps == STEPS and one.one_call_steps == 0 and one.merged_steps == 0
     assert ref.one_call_const_steps == 0 and ref.merged_steps == STEPS
 
@@ -78,7 +68,7 @@ def test_step_view_in_constant_mode_is_the_python_route_bit_for_bit(P, precision
 @pytest.mark.parametrize("precision", ["f16x3", "f16"])
 def test_step_batch_in_constant_mode_is_the_python_route_bit_for_bit(P, precision, R, Ns, Ni):
     """... through the short last batch of an epoch (3 views x 20 x 26 pixels are no multiple of any R above)."""
-    poses, images, K = _scene(P, 5, H, W, seed=4)
+    poses, images, K = scene(P, 5, H, W, seed=4)
     bank = P.RayBank(images, poses, K, [0, 2, 3], 2.0, 6.0, seed=9)
     per_epoch = -(-bank.M // R)
     assert bank.M % R != 0
@@ -91,8 +81,8 @@ def test_step_batch_in_constant_mode_is_the_python_route_bit_for_bit(P, precisio
         assert one.last_batch == ref.last_batch
         sizes.append(one.last_batch[2])
     assert sizes == [R, bank.M % R, R, R]
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, "step_batch")
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, "step_batch")
     assert one.one_call_const_steps == STEPS and one.one_call_steps == 0
 
 
@@ -105,11 +95,11 @@ def test_warm_up_switches_entries_on_one_plan_and_one_workspace(P):
     seen = []
 
     def each_step(k):
-        _assert_same_state(one, ref, f"warm-up step {k}")
+        assert_same_nvs_state(one, ref, f"warm-up step {k}")
         plan = one._plan
         seen.append((id(plan), plan.workspace.data_ptr(), plan.grad_block.data_ptr()))
     logs = _run_views(P, (one, ref), 64, steps=5, each_step=each_step)
-    _assert_same_losses(logs)
+    assert_same_losses(logs)
     assert one.one_call_const_steps == 2 and one.one_call_steps == 3 and ref.merged_steps == 5
     assert len(set(seen)) == 1, seen
     assert set(one._plan.modes) == {"linear", "constant"}
@@ -120,13 +110,13 @@ def test_warm_up_switches_entries_on_one_plan_and_one_workspace(P):
 def test_settings_ride_along_at_the_smallest_shape(P, variant):
     """Density noise, perturb = 0 (the linspace tables), NDC rays and a black background; the precrop window rides in every
     run of this file (the first two steps draw from it)."""
-    llff, over, (near, far) = _settings("llff" if variant == "ndc" else "blender")
+    llff, over, (near, far) = settings("llff" if variant == "ndc" else "blender")
     over.update(dict(noise=dict(raw_noise_std=1.0), det=dict(perturb=0.0), ndc={}, black=dict(white_bkgd=False))[variant])
     one, ref = _pair(P, "f16x3", mode="constant", N_samples=3, N_importance=5, **over)
     assert bool(one.kw.get("ndc", True)) == llff
     logs = _run_views(P, (one, ref), 37, llff, near, far, steps=3)
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, variant)
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, variant)
     assert one.one_call_const_steps == 3
 
 
@@ -145,8 +135,8 @@ def test_fallbacks_count_no_const_step_and_stay_the_python_route(P):
         finally:
             render_module.STAGE_TAP = None
             render_module.FUSE_CONST_EPILOGUE = True
-        _assert_same_losses(logs)
-        _assert_same_state(one, ref, what)
+        assert_same_losses(logs)
+        assert_same_nvs_state(one, ref, what)
         assert one.one_call_const_steps == 0 and one.one_call_steps == 0 and one.global_step == 2, what
     run("fp32", precision="fp32")
     run("stage tap", tap=True)
@@ -171,13 +161,13 @@ def test_two_coarse_samples_do_not_qualify(P):
     """N_samples = 2 leaves the constant-mode sampler no interior weight: the const entry refuses the shape, so the step keeps
     the Python route -- and meets whatever that route does with such a step, a loss or its error, without counting."""
     one, ref = _pair(P, "f16x3", mode="constant", N_samples=2, N_importance=5)
-    poses, images, K = _scene(P, 2, H, W, seed=3)
+    poses, images, K = scene(P, 2, H, W, seed=3)
     images = g(images)
     assert one._one_call_mode(37) is None
     a, b = (_outcome(lambda: ts.step_view(H, W, K, poses[0][:3, :4], images[0], near=2.0, far=6.0, n_rand=37)) for ts in (one, ref))
     assert _same_outcome(a, b), (a, b)
     assert one.one_call_const_steps == 0 and one.one_call_steps == 0 and one._plan is None
-    views = _views(P, 3, seed=31)
+    views = depth_views(P, 3, seed=31)
     d_one, d_ref = (_dstep(P, flags, N_samples=2, N_importance=5) for flags in (dict(one_call_const=True), {}))
     a, b = (_outcome(lambda: ts.step_view(views, 0, 37)) for ts in (d_one, d_ref))
     assert _same_outcome(a, b), (a, b)
@@ -186,36 +176,24 @@ def test_two_coarse_samples_do_not_qualify(P):
 
 # ------------------------------------------------------------------------------ NVS: one library call
 def test_a_constant_mode_step_is_one_library_call(P):
-    from plnerf_amd import _lib
     one = _make(P, "f16x3", dict(one_call_const=True), mode="constant", N_samples=16, N_importance=24)
-    poses, images, K = _scene(P, 3, H, W, seed=1)
+    poses, images, K = scene(P, 3, H, W, seed=1)
     images = g(images)
     bank = P.RayBank(images, poses, K, [0, 1, 2], 2.0, 6.0, seed=3)
     step = {"view": lambda k: one.step_view(H, W, K, poses[k % 3][:3, :4], images[k % 3], near=2.0, far=6.0, n_rand=64),
             "bank": lambda k: one.step_batch(bank, 64)}
     for kind in ("view", "bank"):
         step[kind](0)                               # (builds the plan: its size queries are calls too)
-        real = _lib._lib
-        proxy = _lib._lib = _Counting(real)
-        try:
+        with counting_calls() as proxy:
             for k in range(5):
                 step[kind](k)
-        finally:
-            _lib._lib = real
         assert proxy.calls == ["plnerf_train_step_const"] * 5, proxy.calls
     assert one.one_call_const_steps == 12 and one.one_call_steps == 0
 
 
 # ------------------------------------------------------------------------------ depth: mode = "constant"
 def _dstep(P, flags, seed=5, load=True, **over):
-    from plnerf_amd import depth
-    args = _depth_args(mode="constant", **over)
-    kw, _, start, grad_vars, opt = depth.create_nerf(args, device=DEV)
-    if load:
-        kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
-        kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, True))
-    return depth.DepthTrainStep(args, kw, opt, grad_vars, distributed=False, seed=seed, start=start, range_check_every=0,
-                                **flags)
+    return depth_step(dict(flags, range_check_every=0), seed=seed, load=load, mode="constant", **over)
 
 
 @pytest.mark.parametrize("R,Ns,Ni", [(37, 6, 5), (64, 16, 24)])
@@ -225,12 +203,12 @@ def test_depth_step_view_in_constant_mode_is_the_python_route_bit_for_bit(P, n_h
     """warm_start_nerf = 2: iterations 1 and 2 run without the space-carving term (the final stage's backward is the
     quadrature's alone), 3 and 4 with it (plnerf_fine_epilogue_const_bwd).  Compared after every step: the three losses, the
     pixels, the twelve rendered outputs, the 48 parameter states, the scales and shifts."""
-    views = _views(P, n_hyp, seed=R + n_hyp)
+    views = depth_views(P, n_hyp, seed=R + n_hyp)
     over = dict(N_samples=Ns, N_importance=Ni, warm_start_nerf=2, is_joint=joint)
     one, ref = _dstep(P, dict(one_call_const=True), **over), _dstep(P, {}, **over)
     for k in range(STEPS):
         a, b = one.step_view(views, (2 * k + 1) % V, R), ref.step_view(views, (2 * k + 1) % V, R)
-        _assert_same_step(one, ref, a, b, f"step {k}")
+        assert_same_depth_step(one, ref, a, b, f"step {k}")
     assert one.one_call_const_steps == STEPS and one.one_call_steps == 0 and one.merged_steps == 0
     assert ref.one_call_const_steps == 0 and ref.merged_steps == STEPS
 
@@ -239,19 +217,15 @@ def test_depth_scale_shift_stepping_in_constant_mode(P):
     """The scales and shifts step too (freeze_ss = 100).  The yardstick is the same class forced onto the Python route at every
     step (a kernel timer is watching), as in tests/test_gpu_depth_one_call.py: with either switch on the scales' Adam is
     plnerf_depth_ss_adam on both routes, so everything is equal, scales and shifts included."""
-    from plnerf_amd import functional as Fn
-    views = _views(P, 3, seed=21)
+    views = depth_views(P, 3, seed=21)
     over = dict(freeze_ss=100, scaleshift_lr=1e-3, scale_init=1.02, shift_init=-0.03, N_samples=6, N_importance=5,
                 warm_start_nerf=1, raw_noise_std=0.5)
     one, forced = _dstep(P, dict(one_call_const=True), **over), _dstep(P, dict(one_call_const=True), **over)
     for k in range(STEPS):
         a = one.step_view(views, k % V, 37)
-        Fn.KERNEL_TIMER = Fn.KernelTimer()
-        try:
+        with kernel_timer():
             b = forced.step_view(views, k % V, 37)
-        finally:
-            Fn.KERNEL_TIMER = None
-        _assert_same_step(one, forced, a, b, f"step {k}")
+        assert_same_depth_step(one, forced, a, b, f"step {k}")
     assert one.one_call_const_steps == STEPS and forced.one_call_const_steps == 0
     assert one._ss_steps == forced._ss_steps == STEPS - 1      # (iteration 1 is the warm start)
     assert bool((one.depth_scales.detach() != 1.02).any())
@@ -259,7 +233,7 @@ def test_depth_scale_shift_stepping_in_constant_mode(P):
 
 
 def test_depth_fallbacks_count_no_const_step(P):
-    views = _views(P, 3, seed=31)
+    views = depth_views(P, 3, seed=31)
     for what, flags, over in (("fp32", dict(one_call_const=True), dict(precision="fp32")),
                               ("one_call alone", dict(one_call=True), {}),
                               ("off", dict(one_call_const=False), {})):
@@ -269,13 +243,13 @@ def test_depth_fallbacks_count_no_const_step(P):
             a, b = one.step_view(views, k, 37), ref.step_view(views, k, 37)
             for x, y in zip(a[:3], b[:3]):
                 assert torch.equal(x, y), what
-        _assert_same_depth_state(one, ref, what)
+        assert_same_depth_state(one, ref, what)
         assert one.one_call_const_steps == 0 and one.one_call_steps == 0 and one.global_step == 2, what
 
 
 def test_depth_checkpoint_after_const_steps_resumes_on_either_route(P, tmp_path):
     from plnerf_amd import depth
-    views = _views(P, 3, seed=71)
+    views = depth_views(P, 3, seed=71)
     R = 37
 
     def run(first, then, tag):
@@ -296,21 +270,16 @@ def test_depth_checkpoint_after_const_steps_resumes_on_either_route(P, tmp_path)
     for first, then in ((True, False), (True, True), (False, True)):
         ts, losses = run(first, then, f"r{int(first)}{int(then)}")
         assert all(torch.equal(a, b) for a, b in zip(losses, ref_losses)), (first, then)
-        _assert_same_depth_state(ts, ref, f"resume {first} {then}")
+        assert_same_depth_state(ts, ref, f"resume {first} {then}")
 
 
 def test_a_constant_mode_depth_step_is_one_library_call(P):
-    from plnerf_amd import _lib
-    views = _views(P, 3, seed=41)
+    views = depth_views(P, 3, seed=41)
     one = _dstep(P, dict(one_call_const=True), N_samples=8, N_importance=8, warm_start_nerf=3, freeze_ss=100, scaleshift_lr=1e-3)
     one.step_view(views, 0, 64)                     # (builds the plan: its size queries are calls too)
-    real = _lib._lib
-    proxy = _lib._lib = _Counting(real)
-    try:
+    with counting_calls() as proxy:
         for k in range(5):                          # (without the term, with it, with the scales' step)
             one.step_view(views, k % V, 64)
-    finally:
-        _lib._lib = real
     assert proxy.calls == ["plnerf_depth_train_step_const"] * 5, proxy.calls
     assert one.one_call_const_steps == 6
 
@@ -330,13 +299,12 @@ def test_c_host_runs_the_warm_up_without_python(P, tmp_path):
     assert len(c_hosts.parse_steps(run.stdout)) == 4
     host = torch.from_numpy(np.fromfile(str(out_path), dtype=np.float32))
 
-    args, kw, opt, opt_c = _nets(P, precision, N_samples=Ns, N_importance=Ni, constant_init=3)
+    args, kw, opt, opt_c = nvs_nets(P, precision, N_samples=Ns, N_importance=Ni, constant_init=3)
     shapes = orc.param_shapes()
     for which, net in enumerate((kw["network_fn"], kw["network_fine"])):
         net.load_state_dict(c_hosts.hashed_state_dict(which, shapes))
-    image = g(torch.from_numpy(c_hosts.hashed(999, IMG_H * IMG_W * 3)).reshape(IMG_H, IMG_W, 3))
-    K = [[60.0, 0, 0.5 * IMG_W], [0, 60.0, 0.5 * IMG_H], [0, 0, 1]]
-    c2w = torch.tensor([[1.0, 0, 0, 0], [0, 1.0, 0, 0], [0, 0, 1.0, 4.0]])
+    K, c2w, image = c_hosts.step_scene(IMG_H, IMG_W)
+    image = g(image)
     ts = P.TrainStep(args, kw, opt, opt_c, start=0, distributed=False, seed=11, range_check_every=0)
     for _ in range(4):
         loss, _ = ts.step_view(IMG_H, IMG_W, K, c2w, image, near=2.0, far=6.0, n_rand=R)

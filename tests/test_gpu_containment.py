@@ -34,6 +34,7 @@ import torch
 
 import containment as C
 from arena import Arena
+from gpu_support import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -43,10 +44,6 @@ def L():
     from plnerf_amd import _lib
     _lib.lib()
     return _lib
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 def _params(cases):

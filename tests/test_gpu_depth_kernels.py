@@ -16,16 +16,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import P, assert_close, depth_setup, dev, g
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import assert_close, dev, g
+from run_args import depth_args_of
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
 
 
 # (the last case: the widest row the entry point admits -- 262 channels, 67 KB of LDS per workgroup, beyond the 64 KB a
@@ -308,14 +303,13 @@ def test_depth_render_one_launch_stages_equal_the_separate_launches(P, golden):
     (depth.FUSE_STAGES), the same call runs plnerf_quad_fwd / plnerf_sample_pl / plnerf_merge_sort / plnerf_ray_points /
     torch.std one after the other: every output must be bit-identical, and so must the gradients of a loss through the
     maps AND pred_hyp (the fused backward = plnerf_sample_pl_bwd + plnerf_quad_bwd, like the separate one)."""
-    from test_gpu_modes import _depth_setup
     from plnerf_amd import depth as Dp
     gd = golden("g8b_depth_variant_128_64")
     batch, _ = orc.synthetic_blender_rays(300, seed=21)
     batch = g(batch)
     outs, grads = [], []
     for fuse in (True, False):
-        _, kw, grad_vars, _ = _depth_setup(gd, "fp32")
+        _, kw, grad_vars, _ = depth_setup(gd, "fp32")
         Dp.FUSE_STAGES = fuse
         try:
             ret = Dp.render_rays(batch, retraw=True, pytest=True, **kw)
@@ -334,7 +328,7 @@ def test_depth_render_one_launch_stages_equal_the_separate_launches(P, golden):
     for a, b in zip(*grads):
         assert torch.equal(a, b)
     # N_importance = 0: the hypotheses come from the one network's own pass
-    _, kw, _, _ = _depth_setup(gd, "fp32")
+    _, kw, _, _ = depth_setup(gd, "fp32")
     kw1 = dict(kw, N_importance=0, network_fine=None)
     single = []
     for fuse in (True, False):
@@ -353,10 +347,9 @@ def test_depth_step_is_invariant_to_sharding_of_the_batch(P, golden):
     samples, the hypotheses' u, is_joint's one row -- is a function of (seed, step, GLOBAL ray id): a batch rendered in
     one piece equals the same rays rendered as two shards (to the MLP kernels' summation-order rounding), and the
     returned draws are bit-equal."""
-    from test_gpu_modes import _depth_setup
     from plnerf_amd import depth as Dp, functional as Fn
     gd = golden("g8b_depth_variant_128_64")
-    _, kw, _, _ = _depth_setup(gd, "f16x3")
+    _, kw, _, _ = depth_setup(gd, "f16x3")
     batch, _ = orc.synthetic_blender_rays(96, seed=22)
     rays = g(batch)
 
@@ -385,7 +378,6 @@ def test_depth_step_with_merged_backward_equals_autograd_order(P, golden):
     of both networks, then plnerf_mlp_bwd_multi with the density activation's derivative applied per job) against the same
     steps through torch.autograd.backward: losses to fp32 summation order, weights after three clipped Adam steps to an
     Adam step's rounding."""
-    from test_gpu_modes import _depth_args, _depth_setup
     gd = golden("g8b_depth_variant_128_64")
     R = 2048
     batch, target = orc.synthetic_blender_rays(R, seed=9)
@@ -393,8 +385,8 @@ def test_depth_step_with_merged_backward_equals_autograd_order(P, golden):
     batch, target, target_h = g(batch), g(target), g(target_h)
 
     def run(merged):
-        Dp, kw, grad_vars, opt = _depth_setup(gd, "f16x3")
-        step = Dp.DepthTrainStep(_depth_args(gd, "f16x3"), kw, opt, grad_vars, distributed=False, seed=2)
+        Dp, kw, grad_vars, opt = depth_setup(gd, "f16x3")
+        step = Dp.DepthTrainStep(depth_args_of(gd, "f16x3"), kw, opt, grad_vars, distributed=False, seed=2)
         step.merged_backward = merged
         out = []
         for _ in range(3):
@@ -419,10 +411,9 @@ def test_depth_variant_on_a_shape_outside_the_trunk(P, golden):
     plnerf_embed_rows, softplus density) goes layer by layer (generic.py) -- against the oracle's restatement of
     model/run_nerf_helpers.py:181-205, which reads its widths off the weights -- and one clipped training step runs."""
     import warnings
-    from test_gpu_modes import _depth_args
     from plnerf_amd import depth as Dp
     gd = golden("g8b_depth_variant_128_64")
-    args = _depth_args(gd, "f16x3")
+    args = depth_args_of(gd, "f16x3")
     args.netwidth = args.netwidth_fine = 320
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")

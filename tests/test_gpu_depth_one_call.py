@@ -10,114 +10,39 @@ The bound between the two routes is exact, not measured: both launch the same ke
 stream (tests/test_gpu_one_call.py's argument).  Against torch.optim.Adam the bound is the one
 tests/test_gpu_parity.py::test_fused_adam_matches_torch holds for plnerf_adam_step (atol = rtol = 1e-6): the same fp32
 expressions, torch's own kernel fusing some of them differently."""
-import ctypes
 import os
-from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
 import c_hosts
+from gpu_support import (P, assert_same_depth_state, assert_same_depth_step, counting_calls, depth_state, depth_step,
+                         depth_views, kernel_timer, stage_tap)
 from oracle import plnerf_oracle as orc
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = torch.device("cuda:0")
-V, H, W = 3, 24, 32
+V, H, W = 3, 24, 32      # (gpu_support.depth_views' defaults)
 STEPS = 4
 # (rays, N_samples, N_importance): 222 and 407 MLP rows -- no multiple of the 32-row tile, below the saved planes' 256-row
 # padding; several workgroups of every kernel; the sample covers the whole view
 SHAPES = [(37, 6, 5), (256, 64, 32), (H * W, 8, 8)]
 
 
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-def _views(P, n_hyp, seed=0, valid_p=0.5):
-    """V views of H x W: random colours, hypotheses in [2, 6), about half the pixels invalid (valid_p None: no mask)."""
-    gen = torch.Generator().manual_seed(seed)
-    poses = torch.stack([P.rays.pose_spherical(-180.0 + 360.0 * i / V + 7.0, -30.0 + 3.0 * i, 4.0) for i in range(V)])
-    intr = torch.stack([torch.tensor([1.1 * W + 0.37 * i, 1.2 * W - 0.61 * i, W / 2 - 0.25 + 0.1 * i, H / 2 + 0.5 - 0.2 * i])
-                        for i in range(V)])
-    images = torch.rand(V, H, W, 3, generator=gen)
-    hyp = 2.0 + 4.0 * torch.rand(V, n_hyp, H, W, 1, generator=gen)
-    valid = None if valid_p is None else (torch.rand(V, 1, H, W, 1, generator=gen) < valid_p).to(DEV)
-    return P.DepthViews(images.to(DEV), poses.to(DEV), intr.to(DEV), hyp.to(DEV), valid, 2.0, 6.0)
-
-
-def _args(**over):
-    a = dict(multires=9, i_embed=0, use_viewdirs=True, multires_views=0, input_ch_cam=0, N_importance=32, N_samples=64,
-             netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, perturb=1.0,
-             white_bkgd=True, raw_noise_std=0.0, mode="linear", color_mode="midpoint", lindisp=False, no_reload=True,
-             space_carving_weight=0.007, warm_start_nerf=0, is_joint=False, norm_p=2, space_carving_threshold=0.0,
-             precision="f16x3", bb_center=0.0, bb_scale=1.0, N_rand=256)
-    a.update(over)
-    return Namespace(**a)
-
-
 def _step(P, one_call, seed=5, load=True, **over):
-    from plnerf_amd import depth
-    args = _args(**over)
-    kw, _, start, grad_vars, opt = depth.create_nerf(args, device=DEV)
-    if load:
-        kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
-        kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, True))
-    return depth.DepthTrainStep(args, kw, opt, grad_vars, distributed=False, seed=seed, start=start, range_check_every=0,
-                                one_call=one_call)
+    return depth_step(dict(range_check_every=0, one_call=one_call), seed=seed, load=load, **over)
 
 
 def _pair(P, **over):
     return _step(P, True, **over), _step(P, False, **over)
 
 
-def _state(ts):
-    out = []
-    for net in ts.nets:
-        for p in net.parameters():
-            st = ts.optimizer.state[p]
-            out.append((p.detach(), st['exp_avg'], st['exp_avg_sq'], p.grad, float(st['step'])))
-    return out
-
-
-def _assert_same_state(ts, ref, what=""):
-    assert ts.global_step == ref.global_step
-    a_all, b_all = _state(ts), _state(ref)
-    assert len(a_all) == len(b_all) == 48
-    for k, (a, b) in enumerate(zip(a_all, b_all)):
-        for name, x, y in zip(("param", "exp_avg", "exp_avg_sq", "grad"), a[:4], b[:4]):
-            assert x is not None and y is not None and torch.equal(x, y), (what, k, name, float((x - y).abs().max()))
-        assert a[4] == b[4], (what, k, "step count", a[4], b[4])
-    assert [gr['lr'] for gr in ts.optimizer.param_groups] == [gr['lr'] for gr in ref.optimizer.param_groups]
-    assert torch.equal(ts.depth_scales.detach(), ref.depth_scales.detach()), what
-    assert torch.equal(ts.depth_shifts.detach(), ref.depth_shifts.detach()), what
-
-
-def _same_bits(x, y):
-    """torch.equal on the bit patterns: a NaN (the disparity of a ray that met no density is 0 / 0) equals itself."""
-    x, y = x.detach(), y.detach()
-    return x.shape == y.shape and torch.equal(x.contiguous().view(torch.int32), y.contiguous().view(torch.int32))
-
-
-def _assert_same_step(one, ref, a, b, what=""):
-    """What one step_view returned and left, after every step."""
-    for name, x, y in zip(("loss", "img_loss", "space_carving"), a[:3], b[:3]):
-        assert torch.isfinite(x) and torch.equal(x, y), (what, name, float(x), float(y))
-    assert torch.equal(one.last_pixels, ref.last_pixels), what
-    for key in ("pred_hyp", "rgb_map", "rgb0", "depth_map", "depth0", "acc_map", "acc0", "disp_map", "disp0", "z_std", "z_vals",
-                "z_vals0"):
-        assert _same_bits(a[3][key], b[3][key]), (what, key)
-    _assert_same_state(one, ref, what)
-
-
 def _run(one, ref, views, R, steps=STEPS):
     for k in range(steps):
         a = one.step_view(views, (2 * k + 1) % V, R)
         b = ref.step_view(views, (2 * k + 1) % V, R)
-        _assert_same_step(one, ref, a, b, f"step {k}")
+        assert_same_depth_step(one, ref, a, b, f"step {k}")
 
 
 # ------------------------------------------------------------------------------ 1. bit equality, scales frozen
@@ -126,7 +51,7 @@ def _run(one, ref, views, R, steps=STEPS):
 @pytest.mark.parametrize("precision", ["f16x3", "bf16x3", "f16"])
 def test_step_view_is_the_existing_route_bit_for_bit(P, precision, n_hyp, R, Ns, Ni):
     """freeze_ss = 0; warm_start_nerf = 2: iterations 1 and 2 run without the space-carving term, 3 and 4 with it."""
-    views = _views(P, n_hyp, seed=R + n_hyp)
+    views = depth_views(P, n_hyp, seed=R + n_hyp)
     one, ref = _pair(P, precision=precision, N_samples=Ns, N_importance=Ni, warm_start_nerf=2)
     _run(one, ref, views, R)
     assert one.one_call_steps == STEPS and ref.one_call_steps == 0 and ref.merged_steps == STEPS and one.merged_steps == 0
@@ -154,7 +79,7 @@ VARIANTS = {
 @pytest.mark.parametrize("variant", sorted(VARIANTS))
 def test_settings_of_the_depth_script_bit_for_bit(P, variant, R, Ns, Ni, precision, n_hyp):
     over = dict(VARIANTS[variant])
-    views = _views(P, n_hyp, seed=11, valid_p=over.pop("valid_p", 0.5))
+    views = depth_views(P, n_hyp, seed=11, valid_p=over.pop("valid_p", 0.5))
     one, ref = _pair(P, precision=precision, N_samples=Ns, N_importance=Ni, **over)
     _run(one, ref, views, R, steps=3)
     assert one.one_call_steps == 3
@@ -168,18 +93,14 @@ SS = dict(freeze_ss=100, scaleshift_lr=1e-3, scale_init=1.02, shift_init=-0.03)
 def test_scale_shift_stepping_one_call_against_its_own_fallback(P, R, Ns, Ni, n_hyp, joint):
     """The same object class forced onto the existing route at every step (a kernel timer is watching): one arithmetic for
     the scales' Adam, so everything is equal, scales and shifts included."""
-    from plnerf_amd import functional as Fn
-    views = _views(P, n_hyp, seed=21)
+    views = depth_views(P, n_hyp, seed=21)
     over = dict(SS, N_samples=Ns, N_importance=Ni, is_joint=joint, warm_start_nerf=1)
     one, forced = _step(P, True, **over), _step(P, True, **over)
     for k in range(STEPS):
         a = one.step_view(views, k % V, R)
-        Fn.KERNEL_TIMER = Fn.KernelTimer()
-        try:
+        with kernel_timer():
             b = forced.step_view(views, k % V, R)
-        finally:
-            Fn.KERNEL_TIMER = None
-        _assert_same_step(one, forced, a, b, f"step {k}")
+        assert_same_depth_step(one, forced, a, b, f"step {k}")
     assert one.one_call_steps == STEPS and forced.one_call_steps == 0
     assert one._ss_steps == forced._ss_steps == STEPS - 1      # (iteration 1 is the warm start)
     moved = (one.depth_scales.detach() != 1.02).reshape(-1)
@@ -190,12 +111,12 @@ def test_scale_shift_stepping_one_call_against_its_own_fallback(P, R, Ns, Ni, n_
 def test_scale_shift_stepping_against_torch_adam(P, R, Ns, Ni, n_hyp):
     """After the FIRST stepping iteration networks and losses are equal to the one_call=False run (the scales only reach the
     next step's target_h) and the scales and shifts are within 1e-6 of torch.optim.Adam's."""
-    views = _views(P, n_hyp, seed=22)
+    views = depth_views(P, n_hyp, seed=22)
     one, ref = _pair(P, N_samples=Ns, N_importance=Ni, **SS)
     a, b = one.step_view(views, 1, R), ref.step_view(views, 1, R)
     for x, y in zip(a[:3], b[:3]):
         assert torch.equal(x, y)
-    for (pa, ma, va, ga, sa), (pb, mb, vb, gb, sb) in zip(_state(one), _state(ref)):
+    for (pa, ma, va, ga, sa), (pb, mb, vb, gb, sb) in zip(depth_state(one), depth_state(ref)):
         assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb) and sa == sb
     assert one.one_call_steps == 1 and ref.optimizer_ss is not None and one.optimizer_ss is None
     for x, y in ((one.depth_scales, ref.depth_scales), (one.depth_shifts, ref.depth_shifts)):
@@ -235,14 +156,14 @@ def test_depth_ss_adam_against_torch(P, n_views, grad_scale):
 
 # ------------------------------------------------------------------------------ 4. fallbacks
 def test_fp32_and_a_bounding_box_keep_the_existing_route(P):
-    views = _views(P, 3, seed=31)
+    views = depth_views(P, 3, seed=31)
     for over in (dict(precision="fp32"), dict(bb_scale=1.5)):
         one, ref = _pair(P, N_samples=6, N_importance=5, **over)
         for k in range(2):
             a, b = one.step_view(views, k, 37), ref.step_view(views, k, 37)
             for x, y in zip(a[:3], b[:3]):
                 assert torch.equal(x, y), over
-        _assert_same_state(one, ref, str(over))
+        assert_same_depth_state(one, ref, str(over))
         assert one.one_call_steps == 0 and one.global_step == 2
 
 
@@ -250,21 +171,18 @@ def test_fallbacks_leave_the_count_alone_and_switch_seamlessly(P):
     """A stage tap and a caller-made batch through __call__ take the existing route; the next qualifying step is one call
     again, and the run equals the all-fallback run."""
     from plnerf_amd import depth
-    views = _views(P, 3, seed=32)
+    views = depth_views(P, 3, seed=32)
     one, ref = _pair(P, N_samples=6, N_importance=5, warm_start_nerf=1)
     R = 37
     a, b = one.step_view(views, 0, R), ref.step_view(views, 0, R)
     assert one.one_call_steps == 1 and torch.equal(a[0], b[0])
-    depth.STAGE_TAP = {}
-    try:
+    with stage_tap(depth):
         a, b = one.step_view(views, 1, R), ref.step_view(views, 1, R)
-    finally:
-        depth.STAGE_TAP = None
     assert one.one_call_steps == 1 and torch.equal(a[0], b[0])
-    _assert_same_state(one, ref, "tap")
+    assert_same_depth_state(one, ref, "tap")
     a, b = one.step_view(views, 2, R), ref.step_view(views, 2, R)
     assert one.one_call_steps == 2
-    _assert_same_step(one, ref, a, b, "after the tap")
+    assert_same_depth_step(one, ref, a, b, "after the tap")
     outs = []
     for ts in (one, ref):
         cols, target, th, mask = views.select(1, ts.global_step, R, 0, scale=ts.depth_scales, shift=ts.depth_shifts, seed=5)
@@ -272,37 +190,17 @@ def test_fallbacks_leave_the_count_alone_and_switch_seamlessly(P):
     assert one.one_call_steps == 2 and torch.equal(outs[0][0], outs[1][0]) and "raw" in outs[0][3]
     a, b = one.step_view(views, 0, R), ref.step_view(views, 0, R)
     assert one.one_call_steps == 3 and one.global_step == 5
-    _assert_same_step(one, ref, a, b, "after __call__")
+    assert_same_depth_step(one, ref, a, b, "after __call__")
 
 
 # ------------------------------------------------------------------------------ 5. one library call
-class _Counting:
-    """Stands in for the loaded library: counts every call of a bound entry point."""
-
-    def __init__(self, handle):
-        self._handle, self.calls = handle, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._handle, name)
-
-        def counted(*args):
-            self.calls.append(name)
-            return fn(*args)
-        return counted
-
-
 def test_a_qualifying_step_is_one_library_call(P):
-    from plnerf_amd import _lib
-    views = _views(P, 3, seed=41)
+    views = depth_views(P, 3, seed=41)
     one = _step(P, True, N_samples=8, N_importance=8, warm_start_nerf=3, **SS)
     one.step_view(views, 0, 256)                    # (builds the plan: its size queries are calls too)
-    real = _lib._lib
-    proxy = _lib._lib = _Counting(real)
-    try:
+    with counting_calls() as proxy:
         for k in range(8):                          # (without the term, with it, with the scales' step)
             one.step_view(views, k % V, 256)
-    finally:
-        _lib._lib = real
     assert proxy.calls == ["plnerf_depth_train_step"] * 8, proxy.calls
     assert one.one_call_steps == 9 and one._ss_steps == 6
 
@@ -316,7 +214,7 @@ def test_range_guard_withholds_a_clamped_step_like_the_existing_route(P):
     sd["pts_linears.0.weight"] = sd["pts_linears.0.weight"] * 6.0e4
     sd["pts_linears.1.weight"] = sd["pts_linears.1.weight"] * 1.0e-5
     assert float(sd["pts_linears.0.weight"].abs().max()) < 65504.0
-    views = _views(P, 3, seed=51)
+    views = depth_views(P, 3, seed=51)
     one, ref = _pair(P, N_samples=6, N_importance=5)
     withheld = []
     for ts in (one, ref):
@@ -340,13 +238,13 @@ def test_range_guard_withholds_a_clamped_step_like_the_existing_route(P):
 
 # ------------------------------------------------------------------------------ 7. buffers that move
 def test_plan_follows_buffers_that_move(P):
-    views = _views(P, 3, seed=61)
+    views = depth_views(P, 3, seed=61)
     one, ref = _pair(P, N_samples=6, N_importance=5)
     R = 37
 
     def both(k, vs):
         a, b = one.step_view(vs, k % V, R), ref.step_view(vs, k % V, R)
-        _assert_same_step(one, ref, a, b, f"step {k}")
+        assert_same_depth_step(one, ref, a, b, f"step {k}")
     both(0, views)
     first = one._plan
     for ts in (one, ref):
@@ -363,7 +261,7 @@ def test_plan_follows_buffers_that_move(P):
     for ts in (one, ref):
         ts.optimizer.load_state_dict(ts.optimizer.state_dict())
     both(3, views)
-    replaced = _views(P, 3, seed=61)
+    replaced = depth_views(P, 3, seed=61)
     both(4, replaced)
     assert one._plan is not second
     third = one._plan
@@ -375,7 +273,7 @@ def test_plan_follows_buffers_that_move(P):
 # ------------------------------------------------------------------------------ 8. checkpoint
 def test_checkpoint_after_one_call_steps_resumes_on_either_route(P, tmp_path):
     from plnerf_amd import depth
-    views = _views(P, 3, seed=71)
+    views = depth_views(P, 3, seed=71)
     R = 37
 
     def run(first_one_call, then_one_call, tag):
@@ -396,7 +294,7 @@ def test_checkpoint_after_one_call_steps_resumes_on_either_route(P, tmp_path):
     for first, then in ((True, False), (True, True), (False, True)):
         ts, losses = run(first, then, f"r{int(first)}{int(then)}")
         assert all(torch.equal(a, b) for a, b in zip(losses, ref_losses)), (first, then)
-        _assert_same_state(ts, ref, f"resume {first} {then}")
+        assert_same_depth_state(ts, ref, f"resume {first} {then}")
 
 
 # ------------------------------------------------------------------------------ 9. the torch-free host

@@ -18,7 +18,6 @@ import ctypes
 import functools
 import math
 import os
-from argparse import Namespace
 
 import numpy as np
 import pytest
@@ -28,35 +27,16 @@ import c_hosts
 import containment as C
 import depthview_cases as cases
 import sampleerr_fp64 as ref64
+from gpu_support import P, depth_nets, dev, g, same_bits
 from oracle import plnerf_oracle as orc
+from run_args import depth_args
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLANES = ("rgb", "disp", "acc", "depth", "rgb0", "disp0", "acc0", "depth0", "z_std")
 H, W, NS, NI = 9, 13, 6, 5
 INTRINSIC = (11.3, 9.7, 6.1, 4.3)      # fx, fy, cx, cy
 NEAR, FAR = 2.0, 6.0
 KERNEL_REL = 1e-12
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def g(t):
-    return t.to(dev())
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-def same_bits(a, b):
-    """torch.equal on the bit patterns: as strict for numbers, and a NaN (the disparity of a ray that met nothing) equals
-    itself."""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def _pose():
@@ -179,22 +159,16 @@ def test_frame_export_u16_nan_and_infinities(P, n, off16):
 
 # ----------------------------------------------------------------------------- networks
 def _args(precision, **over):
-    a = dict(multires=9, i_embed=0, use_viewdirs=True, multires_views=0, input_ch_cam=0, N_importance=NI, N_samples=NS,
-             netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, perturb=1.0,
-             white_bkgd=False, raw_noise_std=0.0, mode="linear", color_mode="midpoint", lindisp=False, no_reload=True,
-             precision=precision, bb_center=0.0, bb_scale=1.0, chunk=50, dataset="scannet")
-    a.update(over)
-    return Namespace(**a)
+    """The evaluation loops' arguments: no loss fields, 6 + 5 samples, a black background, chunks of 50 rays."""
+    at = dict(precision=precision, N_importance=NI, N_samples=NS, white_bkgd=False, chunk=50, dataset="scannet")
+    return depth_args(train=False, **dict(at, **over))
 
 
 @functools.lru_cache(maxsize=None)
 def _networks(precision):
     """depth.create_nerf's (train kwargs, test kwargs) with the closed-form weights of the other depth tests, alpha_linear
     sharpened; 6 + 5 samples."""
-    from plnerf_amd import depth as Dp
-    kw, kw_test, _, _, _ = Dp.create_nerf(_args(precision), device=dev())
-    kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
-    kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, True))
+    kw, kw_test = depth_nets(_args(precision))[:2]
     assert kw["network_fn"].input_ch == 57 and kw["network_fn"].input_ch_views == 3 and kw["network_fn"].density_beta == 10.0
     return kw, kw_test
 

@@ -6,35 +6,15 @@ learning-rate schedule, resuming, and two data-parallel ranks."""
 import os
 import subprocess
 import sys
-from argparse import Namespace
 
 import pytest
 import torch
 
-from oracle import plnerf_oracle as orc
+from abi_support import ROOT
+from gpu_support import P, depth_step, perturbed_depth_views
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-def _views(P, V, H, W, n_hyp, seed=0, pose_rows=4):
-    gen = torch.Generator().manual_seed(seed)
-    poses = torch.stack([P.rays.pose_spherical(-180.0 + 360.0 * i / V + 7.0, -30.0 + 3.0 * i, 4.0) for i in range(V)])
-    poses[:, :3, :3] += 0.01 * torch.randn(V, 3, 3, generator=gen)
-    poses = poses[:, :pose_rows].contiguous()
-    intr = torch.stack([torch.tensor([1.1 * W + 0.37 * i, 1.2 * W - 0.61 * i, W / 2 - 0.25 + 0.1 * i, H / 2 + 0.5 - 0.2 * i])
-                        for i in range(V)])
-    images = torch.rand(V, H, W, 3, generator=gen)
-    hyp = 2.0 + 4.0 * torch.rand(V, n_hyp, H, W, 1, generator=gen)
-    valid = torch.rand(V, 1, H, W, 1, generator=gen) > 0.3
-    views = P.DepthViews(images.to(DEV), poses.to(DEV), intr.to(DEV), hyp.to(DEV), valid.to(DEV), 2.0, 6.0)
-    return views, images, poses, intr, hyp[..., 0], valid.reshape(V, H, W)
 
 
 @pytest.mark.parametrize("H,W,n_hyp,R,pose_rows", [(800, 800, 1, 4096, 4), (800, 800, 3, 1, 4), (37, 53, 3, 37 * 53, 3),
@@ -44,7 +24,7 @@ def test_feed_is_the_depth_scripts_full_image_route(P, H, W, n_hyp, R, pose_rows
     get_ray_batch_from_one_image_hypothesis_idx (:960-1001) and :1120 compute from the full H x W ray grid on the GPU."""
     from plnerf_amd import depth
     V = 3
-    views, images, poses, intr, hyp, valid = _views(P, V, H, W, n_hyp, seed=H + n_hyp, pose_rows=pose_rows)
+    views, images, poses, intr, hyp, valid = perturbed_depth_views(P, V, H, W, n_hyp, seed=H + n_hyp, pose_rows=pose_rows)
     scale = (0.8 + 0.4 * torch.rand(V, 1, generator=torch.Generator().manual_seed(1))).to(DEV)
     shift = (0.3 * torch.randn(V, 1, generator=torch.Generator().manual_seed(2))).to(DEV)
     for v in range(V):
@@ -73,7 +53,7 @@ def test_feed_is_the_depth_scripts_full_image_route(P, H, W, n_hyp, R, pose_rows
 
 def test_pixels_are_distinct_and_ranks_disjoint(P):
     H, W = 37, 53
-    views = _views(P, 2, H, W, 1)[0]
+    views = perturbed_depth_views(P, 2, H, W, 1)[0]
     n = H * W
     for R in (1, 100, n // 2):
         _, _, _, _, _, a = views.select(1, 3, R, 0, want_extras=True)
@@ -168,23 +148,9 @@ def test_scale_shift_gradient_against_autograd(P, joint, n_hyp, threshold, maske
 
 
 # --------------------------------------------------------------------------------------------------------- the step
-def _args(**over):
-    a = dict(multires=9, i_embed=0, use_viewdirs=True, multires_views=0, input_ch_cam=0, N_importance=32, N_samples=64,
-             netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, perturb=1.0,
-             white_bkgd=True, raw_noise_std=0.0, mode="linear", color_mode="midpoint", lindisp=False, no_reload=True,
-             space_carving_weight=0.007, warm_start_nerf=0, is_joint=False, norm_p=2, space_carving_threshold=0.0,
-             precision="f16x3", bb_center=0.0, bb_scale=1.0, N_rand=256)
-    a.update(over)
-    return Namespace(**a)
-
-
 def _step(P, start=0, **over):
-    from plnerf_amd import depth
-    args = _args(**over)
-    kw, _, _, grad_vars, opt = depth.create_nerf(args, device=DEV)
-    kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
-    kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, True))
-    return depth.DepthTrainStep(args, kw, opt, grad_vars, distributed=False, seed=5, start=start)
+    """The step as the loop builds it (its default range poll), at `start` whatever a checkpoint directory holds."""
+    return depth_step({}, start=start, **over)
 
 
 def _params(ts):
@@ -193,7 +159,7 @@ def _params(ts):
 
 @pytest.mark.parametrize("precision", ["f16x3", "fp32"])
 def test_step_view_equals_call_on_the_selected_batch(P, precision):
-    views = _views(P, 4, 48, 64, 3)[0]
+    views = perturbed_depth_views(P, 4, 48, 64, 3)[0]
     a, b = _step(P, precision=precision), _step(P, precision=precision)
     for k, img_i in enumerate((2, 0, 3)):
         la = a.step_view(views, img_i)
@@ -211,7 +177,7 @@ def test_scale_shift_adam_against_torch(P):
     """freeze_ss > 0: the scale / shift Adam after 5 steps against torch.optim.Adam driven by autograd gradients of the
     reference expression (on the pred_hyp each step produced, the rays it drew, the scales before the step)."""
     V = 4
-    views, images, poses, intr, hyp, valid = _views(P, V, 48, 64, 3, seed=9)
+    views, images, poses, intr, hyp, valid = perturbed_depth_views(P, V, 48, 64, 3, seed=9)
     ts = _step(P, freeze_ss=100, scaleshift_lr=1e-3, scale_init=1.02, shift_init=-0.03, space_carving_threshold=0.01)
     S = (torch.ones(V, 1, device=DEV) * 1.02).requires_grad_(True)
     T = (torch.ones(V, 1, device=DEV) * -0.03).requires_grad_(True)
@@ -236,7 +202,7 @@ def test_scale_shift_adam_against_torch(P):
 
 
 def test_learning_rate_follows_the_schedule(P):
-    views = _views(P, 2, 32, 32, 1)[0]
+    views = perturbed_depth_views(P, 2, 32, 32, 1)[0]
     ts = _step(P, start_decay_lrate=2, end_decay_lrate=5, N_rand=64)
     seen = []
     for _ in range(8):
@@ -252,7 +218,7 @@ def test_learning_rate_follows_the_schedule(P):
 
 
 def test_resume_draws_the_pixels_of_the_next_iteration(P):
-    views = _views(P, 3, 32, 40, 1)[0]
+    views = perturbed_depth_views(P, 3, 32, 40, 1)[0]
     k = 3
     a = _step(P, N_rand=64)
     for _ in range(k + 1):
@@ -273,17 +239,17 @@ sys.path.insert(0, sys.argv[1])
 sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import plnerf_amd as P
 from plnerf_amd import dp
-from test_gpu_depthfeed import _step, _views
+from gpu_support import depth_step, perturbed_depth_views
 JOINT, N_RAND, STEPS = bool(int(sys.argv[2])), 128, 3
 rank, world, _ = dp.init_from_env(backend="gloo")          # every rank on cuda:0; gloo moves CUDA tensors through the host
 torch.cuda.set_device(0)
-views = _views(P, 4, 40, 48, 3, seed=4)[0]
+views = perturbed_depth_views(P, 4, 40, 48, 3, seed=4)[0]
 over = dict(freeze_ss=100, scaleshift_lr=1e-3, is_joint=JOINT, N_samples=128, N_importance=64)
 
 
 def make(distributed):
-    ts = _step(P, N_rand=N_RAND, **over)
-    if distributed:      # (_step builds a one-process step: rebuild the same nets as a replica of the group)
+    ts = depth_step({}, start=0, N_rand=N_RAND, **over)
+    if distributed:      # (depth_step builds a one-process step: rebuild the same nets as a replica of the group)
         from plnerf_amd import depth
         ts = depth.DepthTrainStep(ts.args, ts.kw, ts.optimizer, ts.grad_vars, distributed=True, seed=5)
     return ts
@@ -332,14 +298,13 @@ def test_data_parallel_step_view_two_ranks(P, tmp_path, joint):
     stepping the global batch within 1e-6 (scales / shifts) and 2e-4 (weights, but for the few whose Adam step
     flips sign: 2 lr per step).  joint: the hypotheses chosen over the
     global batch (functional.joint_choice) are those the scale / shift gradient differentiates."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "dp_depthfeed_worker.py"
     script.write_text(_DP_WORKER)
     port = 31100 + (os.getpid() % 200) + 200 * joint
     procs = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(script), root, str(int(joint))], env=env, stdout=subprocess.PIPE,
+        procs.append(subprocess.Popen([sys.executable, str(script), ROOT, str(int(joint))], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.STDOUT, text=True))
     try:
         outs = [p.communicate(timeout=600)[0] for p in procs]

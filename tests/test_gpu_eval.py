@@ -1,34 +1,19 @@
 """Held-out view metrics on the GPU: plnerf_eval_metrics against the fp64 restatement (tests/eval_fp64.py) over frame
 sizes, clamping, constant and identical images, rgb0 and depth masks; bit-reproducibility across calls and batch
 sizes; render_images_with_metrics end to end (NVS and depth-supervised variants) on closed-form networks."""
-import os
-import sys
 from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-import eval_fp64 as ref                      # noqa: E402
-from oracle import plnerf_oracle as orc      # noqa: E402
+import eval_fp64 as ref
+from gpu_support import P, dev
+from oracle import plnerf_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 SSIM_ABS, SSE_REL = 1e-6, 1e-6
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
 
 
 def _frame(kind, H, W, seed):

@@ -35,8 +35,9 @@ import os
 import pytest
 import torch
 
+from gpu_support import P, assert_close, depth_setup, g, make_net, maxdiff, same_bits, stage_tap
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import assert_close, g, make_net, maxdiff
+from run_args import depth_args_of
 
 pytestmark = pytest.mark.gpu
 R_FULL = 4096
@@ -53,12 +54,6 @@ MAX_RAYS_BEYOND = {
     ("fp32", 64, 128): {"rgb_map": 0, "acc_map": 2, "depth_map": 7, "z_std": 2},
     ("fp32", 128, 64): {"rgb_map": 0, "acc_map": 2, "depth_map": 3, "z_std": 4},
 }
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
 
 
 @pytest.fixture(scope="module")
@@ -213,10 +208,9 @@ def test_depth_variant_render_at_baseline_size_vs_oracle(P, golden, precision):
     """BASELINE configs[4] per GPU, the render: 4096 rays x (128 + 64) samples through the depth-supervised variant's
     render_rays (run_nerf_sample_based_depth.py:792-958: 57|3-channel network, encoding of x pi 2^k, softplus(beta 10)
     density, pred_hyp from the final weights) -- the `input_scale = pi` route of the fused kernel at 786,432 rows."""
-    from test_gpu_modes import _depth_setup
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     gd = golden("g8b_depth_variant_128_64")
-    Dp, kw, _, _ = _depth_setup(gd, precision)
+    Dp, kw, _, _ = depth_setup(gd, precision)
     batch, _ = orc.synthetic_blender_rays(R_FULL, seed=13)
     sd_c, sd_f = orc.closed_form_state_dict_depth(0, True), orc.closed_form_state_dict_depth(1, True)
     with torch.no_grad():
@@ -282,12 +276,6 @@ def oracle_cases():
             cache[name] = (batch, sd_c, sd_f, ns, ni, kw, ref, internals)
         return cache[name]
     return get
-
-
-def _same_bits(a, b):
-    """Bit-for-bit equality (torch.equal calls two NaNs different: disp_map of an empty ray is 1 / max(1e-10, 0 / 0))."""
-    a, b = a.detach().contiguous(), b.detach().contiguous()
-    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 def _dump(name, **tensors):
@@ -371,18 +359,14 @@ def test_stages_at_baseline_size_vs_oracle(P, oracle_cases, workload, precision)
     net_c, net_f = make_net(P, sd_c, precision), make_net(P, sd_f, precision)
     with torch.no_grad():
         got = P.render_rays(g(batch), net_c, qfn, ns, "linear", "midpoint", network_fine=net_f, **kw)
-        tap = {}
-        R_.STAGE_TAP = tap
-        try:
+        with stage_tap(R_) as tap:
             got_t = P.render_rays(g(batch), net_c, qfn, ns, "linear", "midpoint", network_fine=net_f, **kw)
-        finally:
-            R_.STAGE_TAP = None
     torch.cuda.synchronize()
     t = {k: v.detach().cpu() for k, v in tap.items()}
     tag = f"{precision} {workload}"
     # 0. the tapped route IS the shipped route: every map bit for bit (z_std: torch.std vs the kernel's own reduction)
     for k in ("rgb_map", "disp_map", "acc_map", "depth_map", "raw", "rgb0", "disp0", "acc0", "depth0"):
-        assert _same_bits(got[k], got_t[k]), f"{tag}: fused and separate-launch routes differ in {k}"
+        assert same_bits(got[k], got_t[k]), f"{tag}: fused and separate-launch routes differ in {k}"
     assert_close(got_t["z_std"], got["z_std"].cpu(), atol=2e-6, rtol=1e-5, what=f"{tag} z_std of the two routes")
     _dump(f"{workload}_{precision}", got={k: v for k, v in got.items()}, **t)
     # 1. coarse stage: depths (same draws), the network on them, the quadrature on the HIP raw
@@ -442,10 +426,9 @@ def test_depth_stages_at_baseline_size_vs_oracle(P, golden, precision):
     coarse quadrature, importance sampler, fine stage on identical samples at 1e-5 on every ray, the hypotheses' sampler
     on the HIP path's own final weights / tau / T and draws (indices bit-exact), and the end-to-end counts explained."""
     import sys
-    from test_gpu_modes import _depth_setup
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     gd = golden("g8b_depth_variant_128_64")
-    Dp, kw, _, _ = _depth_setup(gd, precision)
+    Dp, kw, _, _ = depth_setup(gd, precision)
     dmod = sys.modules[Dp.render_rays.__module__]
     batch, _ = orc.synthetic_blender_rays(R_FULL, seed=13)
     near, far, rays_d = batch[:, 6:7], batch[:, 7:8], batch[:, 3:6]
@@ -455,18 +438,14 @@ def test_depth_stages_at_baseline_size_vs_oracle(P, golden, precision):
         ref, oi = orc.render_rays_depth(batch, sd_c, sd_f, ns, "linear", "midpoint", perturb=1.0, N_importance=ni,
                                         white_bkgd=True, pytest=True, return_internals=True)
         got = Dp.render_rays(g(batch), retraw=True, pytest=True, **kw)
-        tap = {}
-        dmod.STAGE_TAP = tap
-        try:
+        with stage_tap(dmod) as tap:
             got_t = Dp.render_rays(g(batch), retraw=True, pytest=True, **kw)
-        finally:
-            dmod.STAGE_TAP = None
     torch.cuda.synchronize()
     t = {k: v.detach().cpu() for k, v in tap.items()}
     tag = f"{precision} depth_128_64"
     for k in ("rgb_map", "disp_map", "acc_map", "depth_map", "raw", "rgb0", "disp0", "acc0", "depth0", "z_vals", "weights",
               "pred_hyp", "weights0", "z_vals0", "u"):
-        assert _same_bits(got[k], got_t[k]), f"{tag}: one-launch and separate-launch stages differ in {k}"
+        assert same_bits(got[k], got_t[k]), f"{tag}: one-launch and separate-launch stages differ in {k}"
     _dump(f"depth_128_64_{precision}", got={k: v for k, v in got.items()}, **t)
     # 1. coarse quadrature on the HIP raw -- the coarse raw is not in the dict: the oracle's own coarse pass stands in for
     #    the network check (coarse maps at 1e-5 on every ray, test above); weights / tau / T against the oracle's
@@ -611,11 +590,10 @@ def test_depth_train_step_at_baseline_size_vs_oracle(P, golden, oracle_depth_ste
     """BASELINE configs[4] per GPU, the whole step: 4096 rays x (128 + 64) samples, loss = mse(rgb) + 0.007 space_carving(
     pred_hyp) + mse(rgb0) (run_nerf_sample_based_depth.py:1126-1150) and its gradients before clipping, against the
     oracle on the reference's `pytest` draws."""
-    from test_gpu_modes import _depth_args, _depth_setup
     gd = golden("g8b_depth_variant_128_64")
-    Dp, kw, grad_vars, opt = _depth_setup(gd, precision)
+    Dp, kw, grad_vars, opt = depth_setup(gd, precision)
     o = oracle_depth_steps
-    args = _depth_args(gd, precision)
+    args = depth_args_of(gd, precision)
     args.space_carving_weight = 0.007
     step = Dp.DepthTrainStep(args, kw, opt, grad_vars, distributed=False)
     loss, img_loss, sc, _ = step(g(o["batch"]), g(o["target"]), g(o["target_h"]), pytest=True)

@@ -19,34 +19,18 @@ Stated tolerances (each asserted below):
 """
 import os
 import tempfile
-from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
+from abi_support import ROOT
+from gpu_support import P, T, assert_close, depth_setup, dev, g, g5_batch, make_net, maxdiff
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import assert_close, dev, g, make_net, maxdiff, _g5_batch
+from run_args import depth_args_of, nvs_args
 
 pytestmark = pytest.mark.gpu
-T = torch.from_numpy
 SPLIT_MODES = ["f16x3", "bf16x3"]
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-def _args(ckpt_dir, precision, n_samples=64, n_importance=128, **over):
-    a = dict(multires=10, i_embed=0, use_viewdirs=True, multires_views=4, N_importance=n_importance,
-             N_samples=n_samples, netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536,
-             lrate=5e-4, coarse_lrate=5e-4, ft_path=None, ckpt_dir=ckpt_dir, expname="exp", no_reload=True, perturb=1.0,
-             white_bkgd=True, raw_noise_std=0.0, mode="linear", color_mode="midpoint", dataset="blender", no_ndc=False,
-             lindisp=False, lrate_decay=250, constant_init=0, chunk=32768, precision=precision)
-    a.update(over)
-    return Namespace(**a)
 
 
 def _ckdir():
@@ -69,7 +53,7 @@ def test_g5_render_rays_all_cases_in_split_modes(P, golden, precision):
     tol, tol_std = G5_FINAL_TOL[precision]
     for c in range(int(gd["n_cases"])):
         p = f"c{c}_"
-        o, d, near, far = _g5_batch(gd, p)
+        o, d, near, far = g5_batch(gd, p)
         net_c = make_net(P, orc.closed_form_state_dict(0, True), precision)
         net_f = make_net(P, orc.closed_form_state_dict(1, True), precision)
         qfn = lambda inputs, viewdirs, fn: P.run_network(inputs, viewdirs, fn, emb_fn, embd_fn)
@@ -103,7 +87,7 @@ def test_g6_train_step_in_split_modes(P, golden, precision):
     stride = int(gd["sample_stride"])
     for c in range(int(gd["n_cases"])):
         p = f"c{c}_"
-        args = _args(_ckdir(), precision, int(gd[p + "N_samples"]), int(gd[p + "N_importance"]))
+        args = nvs_args(_ckdir(), precision, N_samples=int(gd[p + "N_samples"]), N_importance=int(gd[p + "N_importance"]))
         kw, _, _, _, opt, opt_c = P.create_nerf(args, device=dev())
         kw["network_fn"].load_state_dict(orc.closed_form_state_dict(0, False))
         kw["network_fine"].load_state_dict(orc.closed_form_state_dict(1, False))
@@ -149,7 +133,7 @@ def test_hundred_steps_track_fp32_oracle(P):
       * the loss falls by more than a factor 2 on both sides (the run does optimise something)
     """
     n_steps, R = 100, 64
-    args = _args(_ckdir(), "f16x3")
+    args = nvs_args(_ckdir(), "f16x3")
     kw, _, start, _, opt, opt_c = P.create_nerf(args, device=dev())
     sd_c, sd_f = orc.closed_form_state_dict(0, False), orc.closed_form_state_dict(1, False)
     kw["network_fn"].load_state_dict(sd_c)
@@ -205,23 +189,6 @@ def test_two_hundred_steps_psnr_vs_exact_fp32_on_the_analytic_scene(P):
 
 
 # ----------------------------------------------------------------------------- BASELINE configs[4]: depth variant, 128+64
-def _depth_args(gd, precision):
-    return Namespace(multires=9, i_embed=0, use_viewdirs=True, multires_views=0, input_ch_cam=0,
-                     N_importance=int(gd["N_importance"]), N_samples=int(gd["N_samples"]), netdepth=8, netwidth=256,
-                     netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, perturb=1.0, white_bkgd=True,
-                     raw_noise_std=0.0, mode="linear", color_mode="midpoint", lindisp=False, no_reload=True,
-                     space_carving_weight=float(gd["space_carving_weight"]), warm_start_nerf=0, is_joint=False,
-                     norm_p=2, space_carving_threshold=0.0, precision=precision, bb_center=0.0, bb_scale=1.0)
-
-
-def _depth_setup(gd, precision):
-    from plnerf_amd import depth as Dp
-    kw, kw_test, start, grad_vars, opt = Dp.create_nerf(_depth_args(gd, precision), device=dev())
-    kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
-    kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, True))
-    return Dp, kw, grad_vars, opt
-
-
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 def test_depth_variant_config5_sampling_golden(P, golden, precision):
     """The depth-supervised step (run_nerf_sample_based_depth.py:792-958, 1126-1157) at configs[4]'s sampling,
@@ -230,7 +197,7 @@ def test_depth_variant_config5_sampling_golden(P, golden, precision):
     section 6): asserted at 2e-4; everything upstream of it at 1e-5."""
     gd = golden("g8b_depth_variant_128_64")
     stride = int(gd["sample_stride"])
-    Dp, kw, grad_vars, opt = _depth_setup(gd, precision)
+    Dp, kw, grad_vars, opt = depth_setup(gd, precision)
     batch, target, target_h = g(T(gd["ray_batch"])), g(T(gd["target"])), g(T(gd["target_h"]))
     with torch.no_grad():
         ret = Dp.render_rays(batch, retraw=True, pytest=True, **kw)
@@ -242,7 +209,7 @@ def test_depth_variant_config5_sampling_golden(P, golden, precision):
         errs[k] = maxdiff(ret[k], T(gd["render_" + k]))
         assert_close(ret[k], gd["render_" + k], atol=2e-4, rtol=2e-4, what=f"{precision} g8b {k}")
     print(f"{precision} g8b: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
-    step = Dp.DepthTrainStep(_depth_args(gd, precision), kw, opt, grad_vars, distributed=False)
+    step = Dp.DepthTrainStep(depth_args_of(gd, precision), kw, opt, grad_vars, distributed=False)
     loss, img_loss, sc, _ = step(batch, target, target_h, pytest=True)
     assert abs(float(loss) - float(gd["loss"])) <= 1e-5, (float(loss), float(gd["loss"]))
     assert abs(float(sc) - float(gd["space_carving_loss"])) <= 2e-4, (float(sc), float(gd["space_carving_loss"]))
@@ -256,7 +223,7 @@ def test_depth_variant_full_size_properties(P, golden):
     """configs[4]'s per-GPU workload (4096 rays x (128 + 64) samples, space-carving loss through pred_hyp) in the
     benchmarked arithmetic: size-independent invariants of one full training step."""
     gd = golden("g8b_depth_variant_128_64")
-    Dp, kw, grad_vars, opt = _depth_setup(gd, "f16x3")
+    Dp, kw, grad_vars, opt = depth_setup(gd, "f16x3")
     R = 4096
     batch, target = orc.synthetic_blender_rays(R, seed=5)
     rng = np.random.default_rng(5)
@@ -274,7 +241,7 @@ def test_depth_variant_full_size_properties(P, golden):
     assert ((ret["rgb_map"] >= -1e-6) & (ret["rgb_map"] <= 1.0 + 1e-5)).all()
     for k in ("rgb_map", "depth_map", "pred_hyp", "z_vals"):                                   # deterministic given u
         assert torch.equal(first[k], again[k]), k
-    step = Dp.DepthTrainStep(_depth_args(gd, "f16x3"), kw, opt, grad_vars, distributed=False)
+    step = Dp.DepthTrainStep(depth_args_of(gd, "f16x3"), kw, opt, grad_vars, distributed=False)
     before = [p.detach().clone() for p in grad_vars]
     loss, img_loss, sc, _ = step(batch, target, target_h)
     assert torch.isfinite(loss) and float(sc) >= 0.0
@@ -294,7 +261,7 @@ def test_reference_written_checkpoint_loads_and_continues(P, golden, precision, 
     (tmp_path / "exp").mkdir()
     shutil.copyfile(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g9_reference_checkpoint.tar"),
                     str(tmp_path / "exp" / "000001.tar"))
-    args = _args(str(tmp_path), precision, no_reload=False)
+    args = nvs_args(str(tmp_path), precision, no_reload=False)
     kw, _, start, grad_vars, opt, opt_c = P.create_nerf(args, device=dev())
     assert start == int(gd["global_step"]) == 1
     assert all(float(opt.state[p]["step"]) == 1.0 for p in grad_vars)
@@ -370,14 +337,13 @@ def test_register_resident_and_ping_pong_forward_kernels_agree(P, tmp_path):
     bits each writes -- the same parameter gradients; both against the fp32 oracle within the modes' bounds."""
     import subprocess
     import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "probe.py"
     script.write_text(_KERNEL_PROBE)
     res = {}
     for k in ("rr", "pp"):
         path = str(tmp_path / f"{k}.pt")
         env = dict(os.environ, PLNERF_FWD_KERNEL=k)
-        r = subprocess.run([sys.executable, str(script), root, path], env=env, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, str(script), ROOT, path], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout + r.stderr
         res[k] = torch.load(path)
     sd = orc.closed_form_state_dict(3, True)
@@ -531,7 +497,7 @@ def test_network_without_view_directions(P, precision, tmp_path):
     assert worst <= gtol
     # the reference's route
     (tmp_path / "exp").mkdir()
-    args = _args(str(tmp_path), precision, use_viewdirs=False)
+    args = nvs_args(str(tmp_path), precision, use_viewdirs=False)
     kw, _, _, grad_vars, opt, opt_c = P.create_nerf(args, device=dev())
     batch, target = orc.synthetic_blender_rays(64, seed=2)
     K = [[1111.111, 0, 400], [0, 1111.111, 400], [0, 0, 1]]
@@ -600,7 +566,7 @@ def test_narrower_and_shallower_networks(P, shape):
     if len(shape) > 3:      # (create_nerf always builds skips=[4], run_plnerf.py:425-437: the route below has no other skip)
         return
     # the reference's route with these arguments: create_nerf, render, backward, both Adams (f16x3, the default mode)
-    args = _args(_ckdir(), "f16x3", netdepth=D, netwidth=Wd, netdepth_fine=D, netwidth_fine=Wd, use_viewdirs=use_viewdirs)
+    args = nvs_args(_ckdir(), "f16x3", netdepth=D, netwidth=Wd, netdepth_fine=D, netwidth_fine=Wd, use_viewdirs=use_viewdirs)
     kw, _, _, grad_vars, opt, opt_c = P.create_nerf(args, device=dev())
     batch, target = orc.synthetic_blender_rays(64, seed=4)
     K = [[1111.111, 0, 400], [0, 1111.111, 400], [0, 0, 1]]
@@ -872,7 +838,7 @@ def test_create_nerf_trains_a_shape_outside_the_trunk(P):
     """The reference's route end to end with netwidth 512 / netdepth 10 (create_nerf warns once per network and serves them
     on the generic route): render, loss, backward, both Adams -- finite, the weights move by an Adam step."""
     import warnings
-    args = _args(_ckdir(), "f16x3", netdepth=10, netwidth=512, netdepth_fine=9, netwidth_fine=320)
+    args = nvs_args(_ckdir(), "f16x3", netdepth=10, netwidth=512, netdepth_fine=9, netwidth_fine=320)
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")
         kw, _, _, grad_vars, opt, opt_c = P.create_nerf(args, device=dev())

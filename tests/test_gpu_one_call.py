@@ -14,67 +14,28 @@ import pytest
 import torch
 
 import c_hosts
+from gpu_support import (P, assert_same_losses, assert_same_nvs_state, counting_calls, g, kernel_timer, nvs_nets, scene, settings,
+                         size, stage_tap)
 from oracle import plnerf_oracle as orc
-from test_gpu_batching import _scene
-from test_gpu_parity import g
-from test_gpu_step import _args, _nets
+from run_args import nvs_args
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = 5
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-def _settings(dataset):
-    """blender-like: white background, no NDC, near 2 / far 6; llff-like: NDC rays, near 0 / far 1, density noise."""
-    llff = dataset == "llff"
-    over = dict(dataset=dataset, white_bkgd=not llff, raw_noise_std=1.0 if llff else 0.0)
-    return llff, over, ((0.0, 1.0) if llff else (2.0, 6.0))
-
-
-def _size(R):
-    """(H, W, precrop) with at least R pixels inside the precrop window."""
-    return {256: (20, 26, (8, 9)), 1024: (40, 50, (16, 17)), 4096: (90, 110, (33, 35))}[R]
-
-
-def _state(ts):
-    """Everything a step leaves behind on the device and in the optimizers."""
-    out = []
-    for net, opt in ((ts.nets[0], ts.optimizer_coarse), (ts.nets[1], ts.optimizer)):
-        for p in net.parameters():
-            st = opt.state[p]
-            out.append((p.detach(), st['exp_avg'], st['exp_avg_sq'], p.grad, float(st['step'])))
-    return out
-
-
-def _assert_same_state(ts, ref, what=""):
-    assert ts.global_step == ref.global_step
-    for k, (a, b) in enumerate(zip(_state(ts), _state(ref))):
-        for name, x, y in zip(("param", "exp_avg", "exp_avg_sq", "grad"), a[:4], b[:4]):
-            assert x is not None and y is not None and torch.equal(x, y), (what, k, name, float((x - y).abs().max()))
-        assert a[4] == b[4], (what, k, "step count", a[4], b[4])
-    for opt_a, opt_b in ((ts.optimizer, ref.optimizer), (ts.optimizer_coarse, ref.optimizer_coarse)):
-        assert [gr['lr'] for gr in opt_a.param_groups] == [gr['lr'] for gr in opt_b.param_groups]
 
 
 def _pair(P, precision, start=0, seed=5, **over):
     """The same networks and optimizers twice: (one-call TrainStep, existing-route TrainStep)."""
     out = []
     for one_call in (True, False):
-        args, kw, opt, opt_c = _nets(P, precision, **over)
+        args, kw, opt, opt_c = nvs_nets(P, precision, **over)
         out.append(P.TrainStep(args, kw, opt, opt_c, start=start, distributed=False, seed=seed, one_call=one_call,
                                range_check_every=0))
     return out
 
 
 def _run_views(P, pair, R, llff, near, far, steps=STEPS, crop_steps=2, scene_seed=3):
-    H, W, precrop = _size(R)
-    poses, images, K = _scene(P, 4, H, W, forward_facing=llff, seed=scene_seed)
+    H, W, precrop = size(R)
+    poses, images, K = scene(P, 4, H, W, forward_facing=llff, seed=scene_seed)
     images = g(images)
     logs = ([], [])
     for k in range(steps):
@@ -83,11 +44,6 @@ def _run_views(P, pair, R, llff, near, far, steps=STEPS, crop_steps=2, scene_see
         for ts, log in zip(pair, logs):
             log.append(ts.step_view(H, W, K, poses[view][:3, :4], images[view], near=near, far=far, n_rand=R, precrop=crop))
     return logs
-
-
-def _assert_same_losses(logs):
-    for k, ((la, pa), (lb, pb)) in enumerate(zip(*logs)):
-        assert torch.isfinite(la) and torch.equal(la, lb) and torch.equal(pa, pb), (k, float(la), float(lb), float(pa), float(pb))
 
 
 CASES = [
@@ -107,12 +63,12 @@ CASES = [
 
 @pytest.mark.parametrize("precision,dataset,R,Ns,Ni", CASES)
 def test_step_view_is_the_existing_route_bit_for_bit(P, precision, dataset, R, Ns, Ni):
-    llff, over, (near, far) = _settings(dataset)
+    llff, over, (near, far) = settings(dataset)
     one, ref = _pair(P, precision, N_samples=Ns, N_importance=Ni, **over)
     assert bool(one.kw.get("ndc", True)) == llff
     logs = _run_views(P, (one, ref), R, llff, near, far)
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, "step_view")
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, "step_view")
     assert one.one_call_steps == STEPS and ref.one_call_steps == 0 and ref.merged_steps == STEPS and one.merged_steps == 0
     # `.grad` are slices of the plan's one flat buffer, in parameter order
     for net in one.nets:
@@ -124,9 +80,9 @@ def test_step_view_is_the_existing_route_bit_for_bit(P, precision, dataset, R, N
 def test_step_batch_is_the_existing_route_bit_for_bit(P, precision, dataset, R, Ns, Ni):
     """... through the short last batch of an epoch: with M bank pixels an epoch has ceil(M / R) steps; the run starts
     two steps before its last one."""
-    llff, over, (near, far) = _settings(dataset)
-    H, W, _ = _size(R)
-    poses, images, K = _scene(P, 5, H, W, forward_facing=llff, seed=4)
+    llff, over, (near, far) = settings(dataset)
+    H, W, _ = size(R)
+    poses, images, K = scene(P, 5, H, W, forward_facing=llff, seed=4)
     bank = P.RayBank(images, poses, K, [0, 2, 3], near, far, seed=9)
     per_epoch = -(-bank.M // R)
     assert bank.M % R != 0
@@ -139,8 +95,8 @@ def test_step_batch_is_the_existing_route_bit_for_bit(P, precision, dataset, R, 
         assert one.last_batch == ref.last_batch
         sizes.append(one.last_batch[2])
     assert sizes == [R, R, bank.M % R, R, R]
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, "step_batch")
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, "step_batch")
     assert one.one_call_steps == STEPS and ref.one_call_steps == 0 and ref.merged_steps == STEPS
 
 
@@ -149,8 +105,8 @@ def test_exact_fp32_keeps_the_existing_route(P):
     step, and is today's run."""
     one, ref = _pair(P, "fp32")
     logs = _run_views(P, (one, ref), 256, False, 2.0, 6.0, steps=3)
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, "fp32")
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, "fp32")
     assert one.one_call_steps == 0 and one.merged_steps == 0 and one.global_step == 3
 
 
@@ -159,8 +115,8 @@ def test_constant_init_steps_fall_back_and_the_switch_is_seamless(P):
     steps take the existing route, the rest the library's, and the run equals the existing route's across the switch."""
     one, ref = _pair(P, "f16x3", constant_init=3)
     logs = _run_views(P, (one, ref), 256, False, 2.0, 6.0)
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, "constant_init")
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, "constant_init")
     qualifying = sum(1 for step in range(STEPS) if not step + 1 < 3)
     assert qualifying == 3 and one.one_call_steps == qualifying and ref.one_call_steps == 0
 
@@ -168,26 +124,19 @@ def test_constant_init_steps_fall_back_and_the_switch_is_seamless(P):
 def test_other_fallbacks_leave_the_count_alone(P):
     """A stage tap, a kernel timer, mode = constant: today's route, silently, per step."""
     import sys
-    from plnerf_amd import functional as Fn
     render_module = sys.modules["plnerf_amd.render"]      # (the package attribute `render` is the function)
     one, ref = _pair(P, "f16x3")
-    H, W, _ = _size(256)
-    poses, images, K = _scene(P, 2, H, W, seed=2)
+    H, W, _ = size(256)
+    poses, images, K = scene(P, 2, H, W, seed=2)
     images = g(images)
     view = lambda ts: ts.step_view(H, W, K, poses[0][:3, :4], images[0], near=2.0, far=6.0, n_rand=256)
-    Fn.KERNEL_TIMER = Fn.KernelTimer()
-    try:
+    with kernel_timer():
         a, b = view(one), view(ref)
-    finally:
-        Fn.KERNEL_TIMER = None
     assert one.one_call_steps == 0 and torch.equal(a[0], b[0])
     a, b = view(one), view(ref)
     assert one.one_call_steps == 1 and torch.equal(a[0], b[0])
-    render_module.STAGE_TAP = {}
-    try:
+    with stage_tap(render_module):
         a, b = view(one), view(ref)
-    finally:
-        render_module.STAGE_TAP = None
     assert one.one_call_steps == 1 and torch.equal(a[0], b[0])
     one.kw["mode"] = ref.kw["mode"] = "constant"
     a, b = view(one), view(ref)
@@ -195,20 +144,20 @@ def test_other_fallbacks_leave_the_count_alone(P):
     one.kw["mode"] = ref.kw["mode"] = "linear"
     a, b = view(one), view(ref)
     assert one.one_call_steps == 2 and torch.equal(a[0], b[0])
-    _assert_same_state(one, ref, "fallbacks")
+    assert_same_nvs_state(one, ref, "fallbacks")
 
 
 def test_checkpoint_after_one_call_steps_resumes_on_either_route(P, tmp_path):
     """The reference's checkpoint (both networks, the fine optimizer) written after 3 steps and resumed for 2 more: the run
     is the same whichever route took the first three and whichever takes the last two."""
-    H, W, _ = _size(256)
-    poses, images, K = _scene(P, 4, H, W, seed=6)
+    H, W, _ = size(256)
+    poses, images, K = scene(P, 4, H, W, seed=6)
     images = g(images)
 
     def run(first_one_call, then_one_call, tag):
         d = tmp_path / tag
         os.makedirs(d / "exp")
-        args = _args(str(d), "f16x3")
+        args = nvs_args(str(d), "f16x3", N_rand=256)
         kw, _, start, _, opt, opt_c = P.create_nerf(args, device=torch.device("cuda:0"))
         kw["network_fn"].load_state_dict(orc.closed_form_state_dict(0, False))
         kw["network_fine"].load_state_dict(orc.closed_form_state_dict(1, False))
@@ -216,7 +165,7 @@ def test_checkpoint_after_one_call_steps_resumes_on_either_route(P, tmp_path):
         losses = [ts.step_view(H, W, K, poses[k % 4][:3, :4], images[k % 4], near=2.0, far=6.0, n_rand=256)[0] for k in range(3)]
         assert ts.one_call_steps == (3 if first_one_call else 0)
         P.save_checkpoint(P.checkpoint_path(str(d), "exp", ts.global_step), ts.global_step, kw["network_fn"], kw["network_fine"], opt)
-        args2 = _args(str(d), "f16x3", no_reload=False)
+        args2 = nvs_args(str(d), "f16x3", N_rand=256, no_reload=False)
         kw2, _, start2, _, opt2, opt_c2 = P.create_nerf(args2, device=torch.device("cuda:0"))
         assert start2 == 3
         ts2 = P.TrainStep(args2, kw2, opt2, opt_c2, start=start2, distributed=False, seed=5, one_call=then_one_call,
@@ -228,7 +177,7 @@ def test_checkpoint_after_one_call_steps_resumes_on_either_route(P, tmp_path):
     for first, then in ((True, False), (True, True), (False, True)):
         ts, losses = run(first, then, f"r{int(first)}{int(then)}")
         assert all(torch.equal(a, b) for a, b in zip(losses, ref_losses)), (first, then)
-        _assert_same_state(ts, ref, f"resume {first} {then}")
+        assert_same_nvs_state(ts, ref, f"resume {first} {then}")
 
 
 def test_range_guard_withholds_a_clamped_step_like_the_existing_route(P):
@@ -240,8 +189,8 @@ def test_range_guard_withholds_a_clamped_step_like_the_existing_route(P):
     sd["pts_linears.1.weight"] = sd["pts_linears.1.weight"] * 1.0e-5
     assert float(sd["pts_linears.0.weight"].abs().max()) < 65504.0
     one, ref = _pair(P, "f16x3")
-    H, W, _ = _size(256)
-    poses, images, K = _scene(P, 2, H, W, seed=8)
+    H, W, _ = size(256)
+    poses, images, K = scene(P, 2, H, W, seed=8)
     images = g(images)
     for ts in (one, ref):
         ts.nets[0].load_state_dict(sd)
@@ -263,8 +212,8 @@ def test_range_guard_withholds_a_clamped_step_like_the_existing_route(P):
     logs = ([], [])
     for ts, log in zip((one, ref), logs):
         log.append(ts.step_view(H, W, K, poses[1][:3, :4], images[1], near=2.0, far=6.0, n_rand=256))
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, "after the guard")
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, "after the guard")
     assert one.one_call_steps == 2
 
 
@@ -274,47 +223,27 @@ def test_range_poll_runs_on_the_one_call_route(P):
     polls = []
     check = one.check_range
     one.check_range = lambda: (polls.append(one.global_step), check())
-    H, W, _ = _size(256)
-    poses, images, K = _scene(P, 2, H, W, seed=8)
+    H, W, _ = size(256)
+    poses, images, K = scene(P, 2, H, W, seed=8)
     images = g(images)
     for _ in range(4):
         one.step_view(H, W, K, poses[0][:3, :4], images[0], near=2.0, far=6.0, n_rand=256)
     assert polls == [2, 4] and one.one_call_steps == 4
 
 
-class _Counting:
-    """Stands in for the loaded library: counts every call of a bound entry point."""
-
-    def __init__(self, handle):
-        self._handle, self.calls = handle, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._handle, name)
-
-        def counted(*args):
-            self.calls.append(name)
-            return fn(*args)
-        return counted
-
-
 def test_a_qualifying_step_is_one_library_call(P):
-    from plnerf_amd import _lib
     one, _ = _pair(P, "f16x3")
-    H, W, _ = _size(1024)
-    poses, images, K = _scene(P, 3, H, W, seed=1)
+    H, W, _ = size(1024)
+    poses, images, K = scene(P, 3, H, W, seed=1)
     images = g(images)
     bank = P.RayBank(images, poses, K, [0, 1, 2], 2.0, 6.0, seed=3)
     step = {"view": lambda k: one.step_view(H, W, K, poses[k % 3][:3, :4], images[k % 3], near=2.0, far=6.0, n_rand=1024),
             "bank": lambda k: one.step_batch(bank, 1024)}
     for kind in ("view", "bank"):
         step[kind](0)                               # (builds the plan: its size queries are calls too)
-        real = _lib._lib
-        proxy = _lib._lib = _Counting(real)
-        try:
+        with counting_calls() as proxy:
             for k in range(10):
                 step[kind](k)
-        finally:
-            _lib._lib = real
         assert proxy.calls == ["plnerf_train_step"] * 10, proxy.calls
     assert one.one_call_steps == 22
 
@@ -323,8 +252,8 @@ def test_plan_follows_buffers_that_move(P):
     """A precision change re-allocates the packed buffers; a load_state_dict replaces the optimizer's step tensors: the plan
     is rebuilt or refreshed, never stepped against dead memory, and the run stays the existing route's."""
     one, ref = _pair(P, "f16x3")
-    H, W, _ = _size(256)
-    poses, images, K = _scene(P, 2, H, W, seed=12)
+    H, W, _ = size(256)
+    poses, images, K = scene(P, 2, H, W, seed=12)
     images = g(images)
     logs = ([], [])
 
@@ -341,8 +270,8 @@ def test_plan_follows_buffers_that_move(P):
     for ts in (one, ref):
         ts.optimizer.load_state_dict(ts.optimizer.state_dict())
     both(2)
-    _assert_same_losses(logs)
-    _assert_same_state(one, ref, "moved buffers")
+    assert_same_losses(logs)
+    assert_same_nvs_state(one, ref, "moved buffers")
     assert one.one_call_steps == 3
 
 
@@ -360,12 +289,11 @@ def test_c_host_trains_without_python(P, precision, tmp_path):
     host_losses, host_sums = c_hosts.parse_steps(run.stdout), c_hosts.parse_sums(run.stdout, "params")
     assert len(host_losses) == STEPS
 
-    args, kw, opt, opt_c = _nets(P, precision, N_samples=Ns, N_importance=Ni)
+    args, kw, opt, opt_c = nvs_nets(P, precision, N_samples=Ns, N_importance=Ni)
     for which, net in enumerate((kw["network_fn"], kw["network_fine"])):
         net.load_state_dict(c_hosts.hashed_state_dict(which, orc.param_shapes()))
-    image = g(torch.from_numpy(c_hosts.hashed(999, IMG_H * IMG_W * 3)).reshape(IMG_H, IMG_W, 3))
-    K = [[60.0, 0, 0.5 * IMG_W], [0, 60.0, 0.5 * IMG_H], [0, 0, 1]]
-    c2w = torch.tensor([[1.0, 0, 0, 0], [0, 1.0, 0, 0], [0, 0, 1.0, 4.0]])
+    K, c2w, image = c_hosts.step_scene(IMG_H, IMG_W)
+    image = g(image)
     ts = P.TrainStep(args, kw, opt, opt_c, start=0, distributed=False, seed=11, one_call=True, range_check_every=0)
     ours = [ts.step_view(IMG_H, IMG_W, K, c2w, image, near=2.0, far=6.0, n_rand=R) for _ in range(STEPS)]
     assert ts.one_call_steps == STEPS

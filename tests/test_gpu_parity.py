@@ -11,50 +11,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import P, T, assert_close, depth_setup, dev, g, g5_batch, make_net, maxdiff, quad_case
 from oracle import plnerf_oracle as orc
+from run_args import depth_args_of
 
 pytestmark = pytest.mark.gpu
-T = torch.from_numpy
-ATOL = RTOL = 1e-5
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def g(x):
-    return x.to(dev())
-
-
-def maxdiff(a, b):
-    a, b = a.detach().cpu().double(), b.detach().cpu().double()
-    return float((a - b).abs().max()) if a.numel() else 0.0
-
-
-def assert_close(a, b, atol=ATOL, rtol=RTOL, what=""):
-    a, b = a.detach().cpu(), (b.detach().cpu() if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b)))
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    err = (a.double() - b.double()).abs()
-    bound = atol + rtol * b.double().abs()
-    bad = err > bound
-    # NaN positions must agree
-    nan_a, nan_b = torch.isnan(a), torch.isnan(b)
-    assert torch.equal(nan_a, nan_b), f"{what}: NaN pattern differs"
-    bad = bad & ~nan_a
-    assert not bad.any(), f"{what}: {int(bad.sum())}/{bad.numel()} elements off, max abs err {float(err[~nan_a].max()):.3e}"
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-def make_net(P, sd, precision="fp32"):
-    net = P.NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=5, skips=[4], use_viewdirs=True,
-                 precision=precision)
-    net.load_state_dict(sd)
-    return net.to(dev())
 
 
 # ----------------------------------------------------------------------------- quadrature
@@ -74,18 +35,6 @@ def test_quad_fwd_golden(P, golden):
             else:
                 # tau holds 1e10 sentinels; disp can be huge when depth ~ 0: relative bound carries those
                 assert_close(v, gd[p + nme], what=f"g2 case {c} {nme}")
-
-
-def quad_case(R, S, seed):
-    gen = torch.Generator().manual_seed(seed)
-    raw = torch.randn(R, S, 4, generator=gen)
-    raw[..., 3] = raw[..., 3] * 4.0 + 1.0
-    raw[: R // 2, S // 4: S // 2, 3] += 30.0
-    z, _ = torch.sort(2.0 + 4.0 * torch.rand(R, S, generator=gen), -1)
-    near, far = torch.full((R, 1), 2.0), torch.full((R, 1), 6.0)
-    d = torch.randn(R, 3, generator=gen)
-    noise = torch.randn(R, S, generator=gen)
-    return raw, z, near, far, d, noise
 
 
 @pytest.mark.parametrize("mode,cmode", [("linear", "midpoint"), ("linear", "left"), ("constant", "midpoint")])
@@ -595,7 +544,7 @@ def test_render_rays_golden_bf16x3(P, golden):
     embd_fn, _ = P.get_embedder(4, 0)
     for c in (0, 1):
         p = f"c{c}_"
-        o, d, near, far = _g5_batch(gd, p)
+        o, d, near, far = g5_batch(gd, p)
         net_c = make_net(P, orc.closed_form_state_dict(0, True), "bf16x3")
         net_f = make_net(P, orc.closed_form_state_dict(1, True), "bf16x3")
         qfn = lambda inputs, viewdirs, fn: P.run_network(inputs, viewdirs, fn, emb_fn, embd_fn)
@@ -649,11 +598,6 @@ def test_unsupported_and_cpu_fail_loudly(P):
 
 
 # ----------------------------------------------------------------------------- render_rays
-def _g5_batch(gd, p):
-    o, d = T(gd[p + "rays_o"]), T(gd[p + "rays_d"])
-    return o, d, float(gd[p + "near"]), float(gd[p + "far"])
-
-
 def test_render_rays_golden(P, golden):
     """render() end to end on the reference's deterministic (pytest=True) draws.  The sampler is
     discontinuous, so end-to-end agreement is asserted at 1e-4 on the maps, and the
@@ -663,7 +607,7 @@ def test_render_rays_golden(P, golden):
     embd_fn, _ = P.get_embedder(4, 0)
     for c in range(int(gd["n_cases"])):
         p = f"c{c}_"
-        o, d, near, far = _g5_batch(gd, p)
+        o, d, near, far = g5_batch(gd, p)
         net_c = make_net(P, orc.closed_form_state_dict(0, True))
         net_f = make_net(P, orc.closed_form_state_dict(1, True))
         qfn = lambda inputs, viewdirs, fn: P.run_network(inputs, viewdirs, fn, emb_fn, embd_fn)
@@ -766,37 +710,18 @@ def test_train_step_golden_and_oracle(P, golden):
 
 
 # ----------------------------------------------------------------------------- depth-supervised variant (8f-1)
-def _depth_args(gd, precision="fp32"):
-    from argparse import Namespace
-    return Namespace(multires=9, i_embed=0, use_viewdirs=True, multires_views=0, input_ch_cam=0,
-                     N_importance=int(gd["N_importance"]), N_samples=int(gd["N_samples"]), netdepth=8, netwidth=256,
-                     netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, perturb=1.0, white_bkgd=True,
-                     raw_noise_std=0.0, mode="linear", color_mode="midpoint", lindisp=False, no_reload=True,
-                     space_carving_weight=float(gd["space_carving_weight"]), warm_start_nerf=0, is_joint=False,
-                     norm_p=2, space_carving_threshold=0.0, precision=precision, bb_center=0.0, bb_scale=1.0)
-
-
-def _depth_setup(P, gd, precision="fp32"):
-    from plnerf_amd import depth as Dp
-    kw, kw_test, start, grad_vars, opt = Dp.create_nerf(_depth_args(gd, precision), device=dev())
-    assert (kw["network_fn"].input_ch, kw["network_fn"].input_ch_views) == (57, 3)
-    kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
-    kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, True))
-    return Dp, kw, grad_vars, opt
-
-
 def test_depth_variant_network_golden(P, golden):
     """57 | 3 input channels, pi-scaled encoder, softplus density (depth_supervised_exps/model/
     run_nerf_helpers.py:100-205) through the same fused MLP, against the reference's own outputs (G8);
     also the non-default widths' weight gradients against the oracle."""
     gd = golden("g8_depth_variant")
-    Dp, kw, _, _ = _depth_setup(P, gd)
+    Dp, kw, _, _ = depth_setup(gd)
     pts, vd = g(T(gd["mlp_pts"])), g(T(gd["mlp_viewdirs"]))
     with torch.no_grad():
         raw = kw["network_query_fn"](pts, vd, kw["embedded_cam"], kw["network_fn"])
     assert_close(raw, gd["mlp_raw"], what="g8 network output")
     for prec, tol in (("f16x3", 1e-5), ("bf16x3", 2e-5)):
-        Dp2, kw2, _, _ = _depth_setup(P, gd, prec)
+        Dp2, kw2, _, _ = depth_setup(gd, prec)
         with torch.no_grad():
             raw2 = kw2["network_query_fn"](pts, vd, kw2["embedded_cam"], kw2["network_fn"])
         err = maxdiff(raw2, T(gd["mlp_raw"]))
@@ -815,7 +740,7 @@ def test_depth_variant_network_golden(P, golden):
         err = float((prm.grad.cpu() - ref).abs().max()) / (float(ref.abs().max()) + 1e-30)
         assert err <= 1e-4, (name, err)
     # the same through the half backward of the 16-bit modes (57 | 3 wide weight-gradient blocks included)
-    Dp3, kw3, _, _ = _depth_setup(P, gd, "f16x3")
+    Dp3, kw3, _, _ = depth_setup(gd, "f16x3")
     net3 = kw3["network_fn"]
     (net3(emb) * g(cot)).sum().backward()
     worst = 0.0
@@ -832,9 +757,9 @@ def test_depth_variant_render_and_train_step_golden(P, golden):
     (run_nerf_sample_based_depth.py:792-958, 1126-1157) against the reference (G8)."""
     gd = golden("g8_depth_variant")
     stride = int(gd["sample_stride"])
-    Dp, kw, grad_vars, opt = _depth_setup(P, gd)
+    Dp, kw, grad_vars, opt = depth_setup(gd)
     batch, target, target_h = g(T(gd["ray_batch"])), g(T(gd["target"])), g(T(gd["target_h"]))
-    args = _depth_args(gd)
+    args = depth_args_of(gd)
     step = Dp.DepthTrainStep(args, kw, opt, grad_vars, distributed=False)
     # forward only first: every output of the dict
     with torch.no_grad():
@@ -871,7 +796,7 @@ def test_depth_variant_gradients_vs_oracle(P):
     from plnerf_amd import depth as Dp
     R, Ns, Ni = 48, 32, 48
     gdummy = {"N_importance": Ni, "N_samples": Ns, "space_carving_weight": 0.05}
-    Dp, kw, grad_vars, opt = _depth_setup(P, gdummy)
+    Dp, kw, grad_vars, opt = depth_setup(gdummy)
     batch, target = orc.synthetic_blender_rays(R, seed=11)
     gen = torch.Generator().manual_seed(11)
     t_rand, u_fine, u_hyp = torch.rand(R, Ns, generator=gen), torch.rand(R, Ni, generator=gen) * 0.999, \
@@ -928,7 +853,7 @@ def test_depth_variant_constant_mode_vs_oracle(P):
     from plnerf_amd import depth as Dp
     R, Ns, Ni = 40, 32, 48
     gdummy = {"N_importance": Ni, "N_samples": Ns, "space_carving_weight": 0.05}
-    Dp, kw, grad_vars, opt = _depth_setup(P, gdummy)
+    Dp, kw, grad_vars, opt = depth_setup(gdummy)
     kw = dict(kw, mode="constant")
     kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, False))
     kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, False))
@@ -981,7 +906,7 @@ def test_depth_variant_render_wrappers(P, golden):
     """depth.render / render_hyp (run_nerf_sample_based_depth.py:85-248): ray packing from c2w or from a ray batch,
     chunking, the 5.33:9 crop, reshape of every dict entry -- equal to render_rays on the packed batch."""
     gd = golden("g8_depth_variant")
-    Dp, kw, _, _ = _depth_setup(P, gd)
+    Dp, kw, _, _ = depth_setup(gd)
     kw = dict(kw, perturb=0.0)                    # deterministic draws: chunking must not change anything
     H, W = 6, 16
     intr = torch.tensor([14.0, 14.0, W / 2, H / 2], device=dev())
@@ -1041,7 +966,7 @@ def test_single_pass_variants_vs_oracle(P):
 def _depth_setup_single(P, gd):
     """_depth_setup for N_importance = 0: one network."""
     from plnerf_amd import depth as Dp
-    kw, kw_test, start, grad_vars, opt = Dp.create_nerf(_depth_args(gd), device=dev())
+    kw, kw_test, start, grad_vars, opt = Dp.create_nerf(depth_args_of(gd), device=dev())
     assert kw["network_fine"] is None and len(grad_vars) == 24
     kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
     return Dp, kw, grad_vars, opt

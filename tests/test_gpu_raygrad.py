@@ -20,16 +20,10 @@ import functools
 import pytest
 import torch
 
+from gpu_support import P, depth_setup, g, make_net, quad_case, stage_tap
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import assert_close, g, make_net, quad_case
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
 
 
 @pytest.mark.parametrize("mode,cmode", [("linear", "midpoint"), ("linear", "left"), ("constant", "midpoint")])
@@ -210,12 +204,8 @@ def _both_gradients(P, batch, sd_c, sd_f, precision, mode, Ns, Ni, cot, **extra)
     sd_f64 = {k: v.double() for k, v in sd_f.items()}
     net_c, net_f = make_net(P, sd_c, precision), make_net(P, sd_f, precision)
     b_h = g(batch).clone().requires_grad_(True)
-    tap = {}
-    render_mod.STAGE_TAP = tap
-    try:
+    with stage_tap(render_mod) as tap:
         got = P.render_rays(b_h, net_c, _query_fn(P), Ns, mode, "midpoint", network_fine=net_f, **kw)
-    finally:
-        render_mod.STAGE_TAP = None
     sum((got[k] * g(cot[k])).sum() for k in KEYS).backward()
     assert b_h.grad is not None and b_h.grad.shape == batch.shape and bool(torch.isfinite(b_h.grad).all())
 
@@ -376,9 +366,8 @@ def test_depth_variant_ray_batch_gradient_vs_oracle(P, mode, Ni):
     explains; the single-pass case has no merge and checks them)."""
     import sys
     from plnerf_amd import depth as Dp
-    from test_gpu_parity import _depth_setup
     R, Ns = 24, 32
-    Dp, kw, _, _ = _depth_setup(P, {"N_importance": 40, "N_samples": Ns, "space_carving_weight": 0.05})      # (both networks exist)
+    Dp, kw, _, _ = depth_setup({"N_importance": 40, "N_samples": Ns, "space_carving_weight": 0.05})      # (both networks exist)
     # (piecewise-constant mode on default-initialised networks, as test_depth_variant_constant_mode_vs_oracle: with the
     # "sharpened" ones most bins are empty and sample_pdf divides by cdf steps of ~1e-5 -- fp32 noise, the reference's too)
     sharp = mode == "linear"

@@ -3,34 +3,19 @@ ray counts, hypothesis counts and valid masks; bit-reproducibility; a frame scor
 against one call; R = 0; the error codes; and depth.test_images_samples end to end against a restatement of the
 reference's loop (whole-frame render, then :396-411 in torch) on closed-form networks, linear and constant modes."""
 import math
-import os
-import sys
 from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-import sampleerr_fp64 as ref                 # noqa: E402
-from oracle import plnerf_oracle as orc      # noqa: E402
+import sampleerr_fp64 as ref
+from gpu_support import P, dev
+from oracle import plnerf_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 KERNEL_REL = 1e-12      # the kernel's fp64 sum against the fp64 restatement (another order of the same additions)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
 
 
 def _rays(R, N, seed, offset=0):

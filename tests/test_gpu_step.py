@@ -5,22 +5,17 @@ step built from them.
 """
 import os
 import tempfile
-from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
+from abi_support import ROOT
+from gpu_support import P, assert_close, dev, g, make_net, maxdiff, nvs_nets, quad_case
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import assert_close, dev, g, make_net, maxdiff, quad_case
+from run_args import nvs_args
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
 
 
 # ----------------------------------------------------------------------------- Philox (host restatement for the KAT)
@@ -216,26 +211,6 @@ def test_image_loss_matches_torch(P):
 
 
 # ----------------------------------------------------------------------------- the step built from them
-def _args(ckpt_dir, precision="f16x3", **over):
-    a = dict(multires=10, i_embed=0, use_viewdirs=True, multires_views=4, N_importance=128, N_samples=64, netdepth=8,
-             netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, coarse_lrate=5e-4,
-             ft_path=None, ckpt_dir=ckpt_dir, expname="exp", no_reload=True, perturb=1.0, white_bkgd=True,
-             raw_noise_std=0.0, mode="linear", color_mode="midpoint", dataset="blender", no_ndc=False, lindisp=False,
-             lrate_decay=250, constant_init=0, chunk=32768, precision=precision, N_rand=256)
-    a.update(over)
-    return Namespace(**a)
-
-
-def _nets(P, precision="f16x3", **over):
-    d = tempfile.mkdtemp()
-    os.makedirs(os.path.join(d, "exp"))
-    args = _args(d, precision, **over)
-    kw, _, start, _, opt, opt_c = P.create_nerf(args, device=dev())
-    kw["network_fn"].load_state_dict(orc.closed_form_state_dict(0, False))
-    kw["network_fine"].load_state_dict(orc.closed_form_state_dict(1, False))
-    return args, kw, opt, opt_c
-
-
 def test_render_is_invariant_to_sharding_of_the_batch(P):
     """Counter-based draws: rendering a global batch in one piece, as two "ranks" (ray_id0 offsets), or in chunks gives
     the same per-ray results -- what makes a data-parallel step independent of the world size.  The DRAWS are
@@ -243,7 +218,7 @@ def test_render_is_invariant_to_sharding_of_the_batch(P):
     rendered values agree to rounding only, because the 16-bit MLP kernels rotate the k-step order by workgroup
     (DESIGN.md section 4), so a row's fp32 summation order depends on its position in the launch."""
     from plnerf_amd import functional as Fn
-    args, kw, _, _ = _nets(P)
+    args, kw, _, _ = nvs_nets(P)
     batch, _ = orc.synthetic_blender_rays(96, seed=21)
     rays = g(batch)
     rkw = {k: v for k, v in kw.items() if k not in ("ndc", "use_viewdirs")}
@@ -293,10 +268,10 @@ def test_train_step_from_a_view(P, dataset):
         near, far = 2.0, 6.0
     yy, xx = torch.meshgrid(torch.linspace(0, 1, H), torch.linspace(0, 1, W), indexing="ij")
     image = g(torch.stack([xx, yy, 0.5 * (xx + yy)], -1))
-    args, kw, opt, opt_c = _nets(P, dataset=dataset)
+    args, kw, opt, opt_c = nvs_nets(P, dataset=dataset)
     assert bool(kw.get("ndc", True)) == (dataset == "llff")
     ts = P.TrainStep(args, kw, opt, opt_c, distributed=False, seed=5)
-    args2, kw2, opt2, opt_c2 = _nets(P, dataset=dataset)
+    args2, kw2, opt2, opt_c2 = nvs_nets(P, dataset=dataset)
     ts2 = P.TrainStep(args2, kw2, opt2, opt_c2, distributed=False, seed=5)
     losses = []
     for step in range(6):
@@ -318,7 +293,7 @@ def test_single_pass_configuration_steps_two_adams_over_one_flat_buffer(P):
     from plnerf_amd.optim import FlatAdam, flat_view_of
     d = tempfile.mkdtemp()
     os.makedirs(os.path.join(d, "exp"))
-    args = _args(d, "fp32", N_importance=0)
+    args = nvs_args(d, "fp32", N_importance=0, N_rand=256)
     torch.manual_seed(0)
     kw, _, _, grad_vars, opt, opt_c = P.create_nerf(args, device=dev())
     assert kw["network_fine"] is None and isinstance(opt, FlatAdam) and isinstance(opt_c, FlatAdam)
@@ -359,7 +334,7 @@ def test_training_step_is_bitwise_reproducible(P):
     poses = [P.rays.pose_spherical(-180.0 + 90.0 * i, -30.0, 4.0)[:3, :4] for i in range(4)]
 
     def run():
-        args, kw, opt, opt_c = _nets(P)
+        args, kw, opt, opt_c = nvs_nets(P)
         ts = P.TrainStep(args, kw, opt, opt_c, distributed=False, seed=11)
         digests = []
         for step in range(8):
@@ -402,7 +377,7 @@ sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import plnerf_amd as P
 from plnerf_amd import dp
 from oracle import plnerf_oracle as orc
-from test_gpu_step import _args
+from run_args import nvs_args
 HW, N_RAND, STEPS = int(sys.argv[2]), int(sys.argv[3]), 3      # view size, rays PER RANK
 rank, world, _ = dp.init_from_env(backend="gloo")          # every rank on cuda:0; gloo moves CUDA tensors through the host
 dev = torch.device("cuda:0")
@@ -412,7 +387,7 @@ FLAGGED = [r for r in (1, 3) if r < world]                  # ranks whose fine f
 
 def make(distributed):
     d = tempfile.mkdtemp(); os.makedirs(os.path.join(d, "exp"))
-    args = _args(d, "f16x3", chunk=32768)
+    args = nvs_args(d, "f16x3", N_rand=256)
     kw, _, _, _, opt, opt_c = P.create_nerf(args, device=dev)
     kw["network_fn"].load_state_dict(orc.closed_form_state_dict(0, False))
     kw["network_fine"].load_state_dict(orc.closed_form_state_dict(1, False))
@@ -513,7 +488,6 @@ dist.destroy_process_group()
 def _run_dp_ranks(tmp_path, world, hw, n_rand, timeout):
     import subprocess
     import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "dp_gpu_worker.py"
     script.write_text(_DP_GPU_WORKER)
     port = 29700 + (os.getpid() % 200) + 200 * (world > 2)
@@ -521,7 +495,7 @@ def _run_dp_ranks(tmp_path, world, hw, n_rand, timeout):
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(script), root, str(hw), str(n_rand)], env=env,
+        procs.append(subprocess.Popen([sys.executable, str(script), ROOT, str(hw), str(n_rand)], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     outs = [p.communicate(timeout=timeout)[0] for p in procs]
     for rank, (p, out) in enumerate(zip(procs, outs)):
@@ -552,26 +526,21 @@ def test_baseline_config2_global_batch_four_shards_equal_one_rank(P, tmp_path):
 # ----------------------------------------------------------------------------- the depth-supervised step, data parallel
 _DP_DEPTH_WORKER = r"""
 import os, sys, torch, torch.distributed as dist
-from argparse import Namespace
 sys.path.insert(0, sys.argv[1])
 sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import plnerf_amd as P
 from plnerf_amd import dp, depth as Dp, functional as Fn
 from oracle import plnerf_oracle as orc
+from run_args import depth_args
 HW, N_RAND, JOINT, STEPS = int(sys.argv[2]), int(sys.argv[3]), bool(int(sys.argv[4])), 3
 rank, world, _ = dp.init_from_env(backend="gloo")          # every rank on cuda:0; gloo moves CUDA tensors through the host
 dev = torch.device("cuda:0")
 torch.cuda.set_device(0)
-# BASELINE configs[4]'s sampling: N_samples 128 / N_importance 64, mode linear, depth loss; the 57 | 3-channel network
-ARGS = dict(multires=9, i_embed=0, use_viewdirs=True, multires_views=0, input_ch_cam=0, N_importance=64, N_samples=128,
-            netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, perturb=1.0,
-            white_bkgd=True, raw_noise_std=0.0, mode="linear", color_mode="midpoint", lindisp=False, no_reload=True,
-            space_carving_weight=0.007, warm_start_nerf=0, is_joint=JOINT, norm_p=2, space_carving_threshold=0.0,
-            precision="f16x3", bb_center=0.0, bb_scale=1.0)
 
 
 def make(distributed):
-    args = Namespace(**ARGS)
+    # BASELINE configs[4]'s sampling: N_samples 128 / N_importance 64, mode linear, depth loss; the 57 | 3-channel network
+    args = depth_args(N_importance=64, N_samples=128, is_joint=JOINT)
     kw, _, _, grad_vars, opt = Dp.create_nerf(args, device=dev)
     kw["network_fn"].load_state_dict(orc.closed_form_state_dict_depth(0, True))
     kw["network_fine"].load_state_dict(orc.closed_form_state_dict_depth(1, True))
@@ -667,7 +636,6 @@ dist.destroy_process_group()
 def _run_dp_depth_ranks(tmp_path, world, hw, n_rand, joint, timeout):
     import subprocess
     import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "dp_depth_worker.py"
     script.write_text(_DP_DEPTH_WORKER)
     port = 28700 + (os.getpid() % 200) + 200 * (world > 2) + 400 * joint
@@ -675,7 +643,7 @@ def _run_dp_depth_ranks(tmp_path, world, hw, n_rand, joint, timeout):
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(script), root, str(hw), str(n_rand), str(int(joint))], env=env,
+        procs.append(subprocess.Popen([sys.executable, str(script), ROOT, str(hw), str(n_rand), str(int(joint))], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     outs = [p.communicate(timeout=timeout)[0] for p in procs]
     for rank, (p, out) in enumerate(zip(procs, outs)):
@@ -880,7 +848,7 @@ def test_training_step_with_merged_backward_equals_autograd_order(P):
     poses = [P.rays.pose_spherical(-180.0 + 90.0 * i, -30.0, 4.0)[:3, :4] for i in range(4)]
 
     def run(merged):
-        args, kw, opt, opt_c = _nets(P)
+        args, kw, opt, opt_c = nvs_nets(P)
         ts = P.TrainStep(args, kw, opt, opt_c, distributed=False, seed=11)
         ts.merged_backward = merged
         hits0 = Fn.ABSMAX_HITS

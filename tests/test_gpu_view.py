@@ -15,25 +15,11 @@ import pytest
 import torch
 
 import c_hosts
+from gpu_support import P, dev, g, nvs_nets, same_bits
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import dev, g
-from test_gpu_step import _nets
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLANES = ("rgb", "disp", "acc", "depth", "rgb0", "disp0", "acc0", "depth0", "z_std")
-
-
-@pytest.fixture(scope="module")
-def P():
-    import plnerf_amd
-    return plnerf_amd
-
-
-def same_bits(a, b):
-    """torch.equal on the bit patterns: as strict for numbers, and a NaN (the disparity of a ray that met nothing, 1 / max(1e-10,
-    0 / 0), in both routes) equals itself."""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def to8b(x):
@@ -187,7 +173,7 @@ K_VIEW = [[11.3, 0, 4.1], [0, 9.7, 6.6], [0, 0, 1]]
 def _networks(precision):
     """create_nerf's render kwargs with the closed-form weights of the other GPU tests, (64, 128) samples."""
     import plnerf_amd as P_
-    _, kw, _, _ = _nets(P_, precision, N_samples=64, N_importance=128)
+    _, kw, _, _ = nvs_nets(P_, precision, N_samples=64, N_importance=128)
     return kw
 
 
@@ -405,7 +391,7 @@ def test_c_host_renders_without_python(P, precision, tmp_path):
     host, _fnv1a = c_hosts.parse_planes(run.stdout), c_hosts.fnv1a
     assert set(host) == {"rgb8", "rgb", "depth16"}
 
-    _, kw, _, _ = _nets(P, precision, N_samples=Ns, N_importance=Ni)
+    _, kw, _, _ = nvs_nets(P, precision, N_samples=Ns, N_importance=Ni)
     for which, net in enumerate((kw["network_fn"], kw["network_fine"])):
         net.load_state_dict(c_hosts.hashed_state_dict(which, orc.param_shapes()))
     kw = dict(kw, mode="linear", color_mode="midpoint", perturb=1.0, white_bkgd=True, raw_noise_std=0.0)

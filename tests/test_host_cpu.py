@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import abi_support as abi
+from run_args import nvs_args
 
 ROOT = abi.ROOT
 MAIN_HEADER = os.path.join(abi.INCLUDE, "plnerf_hip.h")
@@ -181,17 +182,6 @@ def test_unsupported_network_shapes_are_refused(built):
             net.param_list() if False else net._require_supported()
 
 
-def _nvs_args(tmp, **over):
-    from argparse import Namespace
-    a = dict(multires=10, i_embed=0, use_viewdirs=True, multires_views=4, N_importance=128, N_samples=64, netdepth=8,
-             netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, coarse_lrate=5e-4,
-             ft_path=None, ckpt_dir=str(tmp), expname="exp", no_reload=True, perturb=1.0, white_bkgd=True,
-             raw_noise_std=0.0, mode="linear", color_mode="midpoint", dataset="blender", no_ndc=False, lindisp=False,
-             lrate_decay=250, constant_init=0, chunk=32768, precision="f16x3", N_rand=256)
-    a.update(over)
-    return Namespace(**a)
-
-
 # create_nerf flag combinations: (overrides, route).  INTEGRATION.md's table is this list.
 CREATE_NERF_SHAPES = [
     (dict(), "fused"),                                                  # the reference's configs: 8 x 256, skip after 4, 63 | 27
@@ -218,7 +208,7 @@ def test_create_nerf_routes_every_shape_at_the_boundary(built, tmp_path, over, r
     reference's own forward cannot run raises there.  NeRF.__init__ stays permissive (same state_dict as the reference)."""
     import warnings
     (tmp_path / "exp").mkdir()
-    args = _nvs_args(tmp_path, **over)
+    args = nvs_args(str(tmp_path), "f16x3", N_rand=256, **over)
     if route == "refused":
         with pytest.raises(NotImplementedError, match="after the last trunk layer"):
             built.create_nerf(args, device=torch.device("cpu"))
@@ -520,14 +510,8 @@ def test_data_parallel_per_network_inplace_allreduce_gloo(tmp_path):
 
 
 def _args(ckpt_dir, **over):
-    from argparse import Namespace
-    a = dict(multires=10, i_embed=0, use_viewdirs=True, multires_views=4, N_importance=128, N_samples=64, netdepth=8,
-             netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, coarse_lrate=5e-4,
-             ft_path=None, ckpt_dir=ckpt_dir, expname="exp", no_reload=False, perturb=1.0, white_bkgd=True,
-             raw_noise_std=0.0, mode="linear", color_mode="midpoint", dataset="blender", no_ndc=False, lindisp=False,
-             lrate_decay=500, constant_init=1000, chunk=32768)
-    a.update(over)
-    return Namespace(**a)
+    """The reference's configuration files where run_args' defaults are not theirs: checkpoints are reloaded."""
+    return nvs_args(ckpt_dir, **dict(dict(no_reload=False, lrate_decay=500, constant_init=1000), **over))
 
 
 def test_checkpoint_wire_format_roundtrip(built, tmp_path, capsys):
