@@ -8,6 +8,8 @@
 // Measured against sin/cos evaluated in double precision of the same fp32 argument (tests/test_host_cpu.py,
 // tools/probes/pe_sincos_check.cpp): <= 1.2e-7 absolute (2 ulp of one) for |x 2^f| < 2^22; beyond that callers
 // fall back to sincosf.  ~30 VALU instructions per band against ~65 for a library sincosf.
+// On the device both paths are read channel by channel out of every forward kernel, arguments up to 2^39
+// (tests/test_gpu_encoding.py against tests/pe_fp64.py; the measured figures: DESIGN.md section 6, LABNOTES.md "PEERR").
 #pragma once
 #include <math.h>
 
