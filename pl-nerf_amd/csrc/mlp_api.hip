@@ -1,7 +1,9 @@
 // MLP entry points of the C ABI (include/plnerf_hip.h): argument validation and dispatch on
-// the precision mode.  Kernels live in mlp_f32.hip (exact fp32 MFMA; also the shared
-// weight-gradient stage) and mlp_bf16.hip (bf16 / 3-term bf16 split MFMA).
+// the precision mode.  Kernels live in mlp_f32.hip (exact fp32 MFMA), mlp_wgrad.hip (the weight-gradient stage of every
+// mode), mlp_h16.hip (the 16-bit-operand MFMA modes, bf16 and IEEE-half elements, plain and 3-term split: ping-pong
+// forward and dgrad chain) and mlp_rr.hip (their register-resident forward).
 #include "common.h"
+#include "mlp_fwd_route.h"
 #include "mlp_internal.h"
 #include "mlp_layout.h"
 
@@ -13,28 +15,18 @@ inline int ns_of(int precision) {
            : (precision == PLNERF_PREC_BF16X3 || precision == PLNERF_PREC_F16X3) ? 2 : 0;
 }
 inline int f16_of(int precision) { return precision == PLNERF_PREC_F16X3 || precision == PLNERF_PREC_F16; }
+inline int elem_of(int precision) { return f16_of(precision) ? route::ELEM_f16 : route::ELEM_bf16; }      // (16-bit modes)
 inline bool known(int precision) { return precision >= PLNERF_PREC_FP32 && precision <= PLNERF_PREC_F16; }
 // network input widths the padded GEMMs can hold (the reference's defaults are 63 / 27)
 inline bool geometry_ok(int input_ch, int input_ch_views) {
     return input_ch >= 1 && input_ch <= lay::PE_K && input_ch_views >= 1 && input_ch_views <= lay::DPE_K;
 }
-// Forward kernels of the half-element modes.  The split mode (f16x3) runs on the register-resident kernel (mlp_rr.hip),
-// inference (+20 % over the ping-pong kernel) and training (-15 % per launch), with the in-kernel encoding or a
-// caller-embedded input; its saved planes leave in the tiled layout of mlp_layout.h, which the weight-gradient stage
-// reads as it is.  The plain mode (f16) uses it for inference with the in-kernel encoding (two row tiles per wave:
-// +18 %) and keeps the ping-pong kernel for the training forward (its 5.3 KB of plane stores per row come out of eight
-// waves per CU there, out of four here: 1.22 vs 1.39 ms) and for embedded inputs.  `fwd_kernel` (an ABI argument:
-// PLNERF_FWD_KERNEL_AUTO / _RR / _PP) forces one kernel wherever it exists (A/B measurements, and the test suite's
-// other passes); the library itself reads no environment.
+// Forward kernel of the 16-bit modes: `fwd_kernel` is an ABI argument (PLNERF_FWD_KERNEL_AUTO / _RR / _PP; the library
+// itself reads no environment); which kernel a call runs on is route::fwd_uses_rr (mlp_fwd_route.h) and nothing else.
 inline bool kernel_arg_ok(int k) { return k == PLNERF_FWD_KERNEL_AUTO || k == PLNERF_FWD_KERNEL_RR || k == PLNERF_FWD_KERNEL_PP; }
-inline bool use_rr(bool training, int ns, bool embedded, int forced) {
-    if (embedded && !impl::rr_embedded_ok(ns)) return false;      // a caller-embedded input: split mode only
-    return forced == PLNERF_FWD_KERNEL_RR || (forced == PLNERF_FWD_KERNEL_AUTO && (ns == 2 || !training));
-}
-// bf16 elements: inference of both modes; the split mode also for the training forward and caller-embedded inputs
-inline bool use_rr_bf16(bool training, int ns, bool embedded, int forced) {
-    if (forced == PLNERF_FWD_KERNEL_PP) return false;
-    return ns == 2 || (!training && !embedded);
+static_assert(route::FWD_AUTO == PLNERF_FWD_KERNEL_AUTO && route::FWD_RR == PLNERF_FWD_KERNEL_RR && route::FWD_PP == PLNERF_FWD_KERNEL_PP, "");
+inline bool use_rr(int precision, bool training, bool embedded, int forced) {      // (16-bit modes)
+    return route::fwd_uses_rr(elem_of(precision), ns_of(precision), training, embedded, forced);
 }
 }  // namespace
 
@@ -42,7 +34,7 @@ inline bool use_rr_bf16(bool training, int ns, bool embedded, int forced) {
 inline size_t sections_bytes(int precision) {
     if (precision == PLNERF_PREC_FP32) return impl::f32_packed_bytes();
     if (ns_of(precision))
-        return impl::bf16_packed_bytes(ns_of(precision)) + impl::rr_packed_bytes(ns_of(precision));      // (+ the register-resident section)
+        return impl::h16_packed_bytes(ns_of(precision)) + impl::rr_packed_bytes(ns_of(precision));      // (+ the register-resident section)
     return 0;
 }
 inline unsigned* status_word(void* packed, int precision) {
@@ -50,7 +42,7 @@ inline unsigned* status_word(void* packed, int precision) {
 }
 
 inline float* compose_block(const void* packed, int precision) {      // (16-bit modes)
-    return (float*)((unsigned char*)const_cast<void*>(packed) + impl::bf16_compose_offset(ns_of(precision)));
+    return (float*)((unsigned char*)const_cast<void*>(packed) + impl::h16_compose_offset(ns_of(precision)));
 }
 
 extern "C" size_t plnerf_mlp_packed_bytes(int precision) {
@@ -72,11 +64,11 @@ extern "C" int plnerf_mlp_pack_weights(const float* const* params, int precision
     float* cb = compose_block(packed, precision);
     int rc = impl::compose_pack(params, input_ch_views, cb, (hipStream_t)stream);
     if (rc) return rc;
-    rc = impl::bf16_pack(params, input_ch, input_ch_views, ns_of(precision), f16_of(precision), packed,
-                         status_word(packed, precision), (hipStream_t)stream);
+    rc = impl::h16_pack(params, input_ch, input_ch_views, ns_of(precision), f16_of(precision), packed,
+                        status_word(packed, precision), (hipStream_t)stream);
     if (rc) return rc;
-    void* rr_section = (unsigned char*)packed + impl::bf16_packed_bytes(ns_of(precision));
-    return f16_of(precision) ? impl::rr_pack(params, input_ch, input_ch_views, ns_of(precision), cb, rr_section, (hipStream_t)stream)
+    void* rr_section = (unsigned char*)packed + impl::h16_packed_bytes(ns_of(precision));
+    return f16_of(precision) ? impl::rr_pack_f16(params, input_ch, input_ch_views, ns_of(precision), cb, rr_section, (hipStream_t)stream)
                              : impl::rr_pack_bf16(params, input_ch, input_ch_views, ns_of(precision), cb, rr_section, (hipStream_t)stream);
 }
 
@@ -92,8 +84,7 @@ extern "C" size_t plnerf_mlp_saved_bytes(int n_rows, int precision) {
 extern "C" int plnerf_mlp_saved_layout(int precision, int has_embedded, int fwd_kernel) {
     if (!known(precision) || !kernel_arg_ok(fwd_kernel)) return PLNERF_EINVAL;
     if (!ns_of(precision)) return lay::SV_LAYOUT_ROWS;
-    if (f16_of(precision)) return use_rr(true, ns_of(precision), has_embedded != 0, fwd_kernel) ? lay::SV_LAYOUT_TILED : lay::SV_LAYOUT_ROWS;
-    return use_rr_bf16(true, ns_of(precision), has_embedded != 0, fwd_kernel) ? lay::SV_LAYOUT_TILED : lay::SV_LAYOUT_ROWS;
+    return use_rr(precision, true, has_embedded != 0, fwd_kernel) ? lay::SV_LAYOUT_TILED : lay::SV_LAYOUT_ROWS;
 }
 
 extern "C" size_t plnerf_mlp_bwd_workspace_bytes(int n_rows, int precision) {
@@ -124,18 +115,13 @@ extern "C" int plnerf_mlp_fwd(const void* packed, int precision, const float* pt
     if (precision == PLNERF_PREC_FP32)
         return impl::f32_fwd(packed, pts, viewdirs, embedded, input_ch, input_ch_views, n_rows, samples_per_ray,
                              opt, raw_out, saved, (hipStream_t)stream);
-    if (f16_of(precision) && use_rr(saved != nullptr, ns_of(precision), embedded != nullptr, fwd_kernel))
-        return impl::rr_fwd(packed, (const unsigned char*)packed + impl::bf16_packed_bytes(ns_of(precision)),
+    if (use_rr(precision, saved != nullptr, embedded != nullptr, fwd_kernel))
+        return impl::rr_fwd(elem_of(precision), packed, (const unsigned char*)packed + impl::h16_packed_bytes(ns_of(precision)),
                             ns_of(precision), pts, viewdirs, embedded, input_ch, input_ch_views, n_rows, samples_per_ray,
                             opt, raw_out, saved, status_word(const_cast<void*>(packed), precision), (hipStream_t)stream);
-    // bf16 elements: the register-resident kernel serves inference with the in-kernel encoding (unless pp is forced)
-    if (!f16_of(precision) && use_rr_bf16(saved != nullptr, ns_of(precision), embedded != nullptr, fwd_kernel))
-        return impl::rr_fwd_bf16(packed, (const unsigned char*)packed + impl::bf16_packed_bytes(ns_of(precision)),
-                                 ns_of(precision), pts, viewdirs, embedded, input_ch, input_ch_views, n_rows, samples_per_ray,
-                                 opt, raw_out, saved, status_word(const_cast<void*>(packed), precision), (hipStream_t)stream);
-    return impl::bf16_fwd(packed, ns_of(precision), f16_of(precision), pts, viewdirs, embedded, input_ch,
-                          input_ch_views, n_rows, samples_per_ray, opt, raw_out, saved,
-                          status_word(const_cast<void*>(packed), precision), (hipStream_t)stream);
+    return impl::h16_fwd(packed, ns_of(precision), f16_of(precision), pts, viewdirs, embedded, input_ch,
+                         input_ch_views, n_rows, samples_per_ray, opt, raw_out, saved,
+                         status_word(const_cast<void*>(packed), precision), (hipStream_t)stream);
 }
 
 // The backward of up to PLNERF_MAX_BWD_JOBS networks that share precision, input widths and density activation (the
@@ -214,7 +200,7 @@ extern "C" int plnerf_mlp_bwd_multi(int n_jobs, const void* const* packed, int p
                                status_out ? status_out[j] : nullptr, compose_block(packed[j], precision),
                                (float*)((unsigned char*)partials + part_only)};
     }
-    const int rc = impl::bf16_dgrad(n_jobs, dj, st);
+    const int rc = impl::h16_dgrad(n_jobs, dj, st);
     if (rc) return rc;
     return impl::wgrad_h16_multi(n_jobs, wj, st);
 }

@@ -55,11 +55,11 @@ using namespace plnerf::lay;
 namespace plnerf {
 namespace impl {
 
-size_t bf16_packed_bytes(int ns) { return plnerf_h16_bf16::h16_packed_bytes(ns); }
-size_t bf16_compose_offset(int ns) { return plnerf_h16_bf16::h16_compose_offset(ns); }
+size_t h16_packed_bytes(int ns) { return plnerf_h16_bf16::h16_packed_bytes(ns); }
+size_t h16_compose_offset(int ns) { return plnerf_h16_bf16::h16_compose_offset(ns); }
 
-int bf16_pack(const float* const* params, int xyz_ch, int dir_ch, int ns, int f16, void* packed, unsigned* status,
-              hipStream_t st) {
+int h16_pack(const float* const* params, int xyz_ch, int dir_ch, int ns, int f16, void* packed, unsigned* status,
+             hipStream_t st) {
     // forward section in the mode's element type (ns planes), dgrad section always one half plane: one launch
     // when the forward section is half too, two otherwise
     if (f16) return plnerf_h16_f16::h16_pack(params, xyz_ch, dir_ch, ns, 3, ns, packed, status, st);
@@ -67,16 +67,16 @@ int bf16_pack(const float* const* params, int xyz_ch, int dir_ch, int ns, int f1
     return rc ? rc : plnerf_h16_f16::h16_pack(params, xyz_ch, dir_ch, 1, 2, ns, packed, status, st);
 }
 
-int bf16_fwd(const void* packed, int ns, int f16, const float* pts, const float* viewdirs, const float* embedded,
-             int xyz_ch, int dir_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out, void* saved,
-             unsigned* status, hipStream_t st) {
+int h16_fwd(const void* packed, int ns, int f16, const float* pts, const float* viewdirs, const float* embedded,
+            int xyz_ch, int dir_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out, void* saved,
+            unsigned* status, hipStream_t st) {
     return f16 ? plnerf_h16_f16::h16_fwd(packed, ns, pts, viewdirs, embedded, xyz_ch, dir_ch, n_rows, samples_per_ray,
                                          opt, raw_out, saved, status, st)
                : plnerf_h16_bf16::h16_fwd(packed, ns, pts, viewdirs, embedded, xyz_ch, dir_ch, n_rows, samples_per_ray,
                                           opt, raw_out, saved, status, st);      // (bf16 elements: PLNERF_RANGE_SAVED only)
 }
 
-int bf16_dgrad(int n, const DgradJob* jobs, hipStream_t st) {
+int h16_dgrad(int n, const DgradJob* jobs, hipStream_t st) {
     if (n < 1 || n > MAX_BWD_JOBS) return PLNERF_EINVAL;
     return plnerf_h16_f16::h16_dgrad(n, jobs, st);
 }

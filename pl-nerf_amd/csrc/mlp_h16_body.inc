@@ -1,4 +1,4 @@
-// Body of the 16-bit-operand MFMA MLP kernels, compiled once per element type (see mlp_bf16.hip):
+// Body of the 16-bit-operand MFMA MLP kernels, compiled once per element type (see mlp_h16.hip):
 //   H16T     element type (__bf16 or _Float16)      H16_MFMA  the matching 32x32x16 MFMA builtin
 typedef H16T bf16x8 __attribute__((ext_vector_type(8)));
 typedef H16T bf16x4 __attribute__((ext_vector_type(4)));
@@ -590,7 +590,7 @@ inline int bwd_launch(const BwdArgs* jobs, int n, hipStream_t st) {
 
 }  // namespace
 
-// ---- entry points of this element type (called from the dispatchers in mlp_bf16.hip) ----
+// ---- entry points of this element type (called from the dispatchers in mlp_h16.hip) ----
 inline size_t h16_compose_offset(int ns) {   // head + forward section (ns planes) + dgrad section (one half plane)
     return HEAD_BYTES + (size_t)FWDC_FLOATS * ns * 2 + (size_t)BWDC_FLOATS * 2;
 }

@@ -87,21 +87,23 @@ inline size_t h16_dz_bytes(int n_rows) {      // (lay::dz_rows)
     return (size_t)4352 * (((size_t)n_rows + PLNERF_BWD_TM - 1) / PLNERF_BWD_TM * PLNERF_BWD_TM);
 }
 
-// 16-bit-operand MFMA modes.  ns = 1: plain operands; ns = 2: 3-term split (hi/lo planes).
-// f16 = 0: bf16 elements; f16 = 1: IEEE half elements.
-size_t bf16_packed_bytes(int ns);
-size_t bf16_compose_offset(int ns);      // byte offset of the compose block (lay::CB_FLOATS floats) inside the packed buffer
-int bf16_pack(const float* const* params, int xyz_ch, int dir_ch, int ns, int f16, void* packed, unsigned* status,
-              hipStream_t st);
-int bf16_fwd(const void* packed, int ns, int f16, const float* pts, const float* viewdirs, const float* embedded,
-             int xyz_ch, int dir_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out, void* saved,
-             unsigned* status, hipStream_t st);
-int bf16_dgrad(int n, const DgradJob* jobs, hipStream_t st);
+// 16-bit-operand MFMA modes, both element types (mlp_h16.hip).  ns = 1: plain operands; ns = 2: 3-term split (hi/lo
+// planes).  f16 = 0: bf16 elements; f16 = 1: IEEE half elements (the dgrad chain runs on half operands in every mode).
+size_t h16_packed_bytes(int ns);
+size_t h16_compose_offset(int ns);      // byte offset of the compose block (lay::CB_FLOATS floats) inside the packed buffer
+int h16_pack(const float* const* params, int xyz_ch, int dir_ch, int ns, int f16, void* packed, unsigned* status,
+             hipStream_t st);
+int h16_fwd(const void* packed, int ns, int f16, const float* pts, const float* viewdirs, const float* embedded,
+            int xyz_ch, int dir_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out, void* saved,
+            unsigned* status, hipStream_t st);
+int h16_dgrad(int n, const DgradJob* jobs, hipStream_t st);
 
-// Register-resident forward kernel (mlp_rr.hip; IEEE-half elements): its own weight section (k order permuted to the
-// accumulator layout) appended to the packed buffer of the half modes.  (cb: the compose block, written before the call)
+// Register-resident forward kernel (mlp_rr.hip), both element types: its own weight section (k order permuted to the
+// accumulator layout) appended to the packed buffer of the 16-bit modes, packed per element type.  (cb: the compose
+// block, written before the call)
 size_t rr_packed_bytes(int ns);
-int rr_pack(const float* const* params, int xyz_ch, int dir_ch, int ns, const float* cb, void* section, hipStream_t st);
+int rr_pack_f16(const float* const* params, int xyz_ch, int dir_ch, int ns, const float* cb, void* section, hipStream_t st);
+int rr_pack_bf16(const float* const* params, int xyz_ch, int dir_ch, int ns, const float* cb, void* section, hipStream_t st);
 struct RrFwdArgs {
     const void* packed;     // head block at the start
     const void* wrr;        // the register-resident section of the packed weights
@@ -116,16 +118,10 @@ struct RrFwdArgs {
     float pe_scale;         // in-kernel encoding: sin / cos(x * pe_scale * 2^k)
     float act_beta;         // > 0: sigma leaves as softplus(beta)(sigma)
 };
-bool rr_embedded_ok(int ns);
-int rr_fwd(const void* packed, const void* section, int ns, const float* pts, const float* viewdirs, const float* embedded,
-           int in_ch, int view_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out, void* saved,
-           unsigned* status, hipStream_t st);
-// the same kernel on bf16 elements (mlp_rr_body.inc compiled with RR_BF16): inference, and -- split mode only -- the
-// training forward and caller-embedded inputs
-int rr_pack_bf16(const float* const* params, int xyz_ch, int dir_ch, int ns, const float* cb, void* section, hipStream_t st);
-int rr_fwd_bf16(const void* packed, const void* section, int ns, const float* pts, const float* viewdirs,
-                const float* embedded, int in_ch, int view_ch, int n_rows, int samples_per_ray, FwdOpt opt,
-                float* raw_out, void* saved, unsigned* status, hipStream_t st);
+// elem: route::ELEM_* (mlp_fwd_route.h, which lists the instantiations that exist and decides who is sent here)
+int rr_fwd(int elem, const void* packed, const void* section, int ns, const float* pts, const float* viewdirs,
+           const float* embedded, int in_ch, int view_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out,
+           void* saved, unsigned* status, hipStream_t st);
 
 }  // namespace impl
 }  // namespace plnerf

@@ -32,8 +32,8 @@
 // the next MFMA waits for (accumulator set-up and head weights are requested ahead), no branch and no uncounted store
 // in the stream (saved rows are padded to whole workgroup tiles; stores share vmcnt with the weight DMA and are
 // counted in the hand-over waits), non-temporal plane stores, accumulators in architectural VGPRs (Makefile).
-// (This file is the kernel's body, included by mlp_rr.hip -- packing, dispatch -- and by mlp_rr_k*.hip, one instantiation
-// each: six instantiations of 20-30 thousand instructions compile in parallel instead of one after the other.)
+// (This file is the kernel's body, included by mlp_rr.hip -- packing, dispatch -- and by mlp_rr_inst.hip, one instantiation
+// per object: instantiations of 20-30 thousand instructions compile in parallel instead of one after the other.)
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -44,7 +44,7 @@
 #include "mlp_pack_src.h"
 #include "pe_sincos.h"
 
-// RR_BF16 (defined by the mlp_rr_kb_*.hip translation units): the same kernel on bf16 elements -- fp32's exponent
+// RR_BF16 (-DRR_BF16: the bf16 objects of csrc/Makefile): the same kernel on bf16 elements -- fp32's exponent
 // range, so no clamp in the forward; the lo halves by shift / subtract / convert (v_fma_mix knows IEEE half only).
 // Inference of both modes; the split mode also trains on it: the saved state of every 16-bit mode is IEEE half, so the
 // training variant converts every pair a second time, saturating, and remembers the largest magnitude it converted --
@@ -87,7 +87,7 @@ typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
 
 #ifdef RR_TRACE
 #ifndef RR_SINGLE_TU
-#error "trace builds are single-translation-unit builds (tools/build_rr.sh)"
+#error "trace builds are single-translation-unit builds (tools/build_variant.sh)"
 #endif
 __device__ unsigned long long g_rr_trace[128];     // [0..3] walk begin / end (shader clock, wall clock); [8 + u] start of unit u
 #endif

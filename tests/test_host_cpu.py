@@ -81,18 +81,21 @@ def test_buffer_size_queries(built):
     assert L.plnerf_mlp_bwd_workspace_bytes(961, 3) - 961 * 16 == L.plnerf_mlp_bwd_workspace_bytes(1152, 3) - 1152 * 16      # 6 x 192
     assert L.plnerf_mlp_bwd_workspace_bytes(1153, 3) - L.plnerf_mlp_bwd_workspace_bytes(1152, 3) == 192 * 2176 * 2 + 16
     assert L.plnerf_mlp_saved_bytes(1025, 3) - L.plnerf_mlp_saved_bytes(1024, 3) == 256 * (2272 * 2 + 272)
-    # the layout tag a caller hands back to plnerf_mlp_bwd: the split modes write tiled planes (with or without a
-    # caller-embedded input); exact fp32 and the plain 16-bit modes row-major
-    # the saved layout is a pure function of (precision, embedded input, forward-kernel argument): no environment
+    # the layout tag a caller hands back to plnerf_mlp_bwd (1 = tiled planes: the register-resident training forward; 0 =
+    # row-major): a pure function of (precision, embedded input, forward-kernel argument), no environment.  The whole
+    # table, (embedded 0, embedded 1) per cell: the split modes tiled unless the ping-pong kernel is forced; plain f16
+    # only where the register-resident kernel is forced and encodes itself (no plain embedded variant); plain bf16 never
+    # (no plain bf16 training variant)
     AUTO, RR, PP = 0, 1, 2
-    for k in (AUTO, RR, PP):
-        assert L.plnerf_mlp_saved_layout(0, 0, k) == 0 and L.plnerf_mlp_saved_layout(0, 1, k) == 0       # fp32: rows
-    assert L.plnerf_mlp_saved_layout(3, 0, AUTO) == 1 and L.plnerf_mlp_saved_layout(3, 1, AUTO) == 1     # f16x3: tiled
-    assert L.plnerf_mlp_saved_layout(1, 0, AUTO) == 1 and L.plnerf_mlp_saved_layout(1, 1, AUTO) == 1     # bf16x3
-    assert L.plnerf_mlp_saved_layout(4, 0, AUTO) == 0 and L.plnerf_mlp_saved_layout(4, 1, AUTO) == 0     # f16: ping-pong
-    assert L.plnerf_mlp_saved_layout(2, 0, AUTO) == 0 and L.plnerf_mlp_saved_layout(2, 1, AUTO) == 0
-    assert L.plnerf_mlp_saved_layout(3, 0, PP) == 0 and L.plnerf_mlp_saved_layout(1, 0, PP) == 0
-    assert L.plnerf_mlp_saved_layout(4, 0, RR) == 1 and L.plnerf_mlp_saved_layout(4, 1, RR) == 0         # no plain embedded rr
+    table = {0: {AUTO: (0, 0), RR: (0, 0), PP: (0, 0)},      # fp32
+             1: {AUTO: (1, 1), RR: (1, 1), PP: (0, 0)},      # bf16x3
+             2: {AUTO: (0, 0), RR: (0, 0), PP: (0, 0)},      # bf16
+             3: {AUTO: (1, 1), RR: (1, 1), PP: (0, 0)},      # f16x3
+             4: {AUTO: (0, 0), RR: (1, 0), PP: (0, 0)}}      # f16
+    for precision, row in table.items():
+        for k, want in row.items():
+            got = tuple(L.plnerf_mlp_saved_layout(precision, emb, k) for emb in (0, 1))
+            assert got == want, (precision, k, got, want)
     assert L.plnerf_mlp_saved_layout(3, 0, 7) < 0 and L.plnerf_mlp_saved_layout(9, 0, AUTO) < 0
     assert L.plnerf_mlp_packed_bytes(7) == 0
 
