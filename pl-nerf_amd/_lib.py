@@ -390,6 +390,30 @@ CAMCODE_TABLE_SIGNATURES = _merge(CAMCODE_HEADERS)
 _disjoint(CAMCODE_TABLE_SIGNATURES, ALL_SIGNATURES)
 _disjoint(CAMCODE_TABLE_SIGNATURES, EXPERIMENTAL_SIGNATURES)
 
+# ---- a fourth table, for include/experimental/plnerf_hip_dpstep.h: the one-call training steps cut in two at the gradient
+# exchange of a data-parallel run (stepplan's run_grads / apply).  Experimental, and apart from the three tables above for the
+# reason the third is apart from the first two.  The structs are the registered steps' (no mirrors of its own); the workspace
+# is theirs too, so there is no size query.
+_STEP_GRADS = (c_i, [ctypes.POINTER(StepConfig), ctypes.POINTER(StepIo), ctypes.POINTER(StepArgs), c_f, ctypes.c_size_t, c_s])
+_DEPTH_STEP_GRADS = (c_i, [ctypes.POINTER(DepthStepConfig), ctypes.POINTER(DepthStepIo), ctypes.POINTER(DepthStepArgs), c_f,
+                           ctypes.c_size_t, c_s])
+DPSTEP_SIGNATURES = {
+    "plnerf_train_step_grads": _STEP_GRADS,
+    "plnerf_train_step_const_grads": _STEP_GRADS,
+    "plnerf_train_step_apply": (c_i, [ctypes.POINTER(StepConfig), ctypes.POINTER(StepIo), ctypes.POINTER(StepArgs), c_fl, c_s]),
+    "plnerf_depth_train_step_grads": _DEPTH_STEP_GRADS,
+    "plnerf_depth_train_step_const_grads": _DEPTH_STEP_GRADS,
+    "plnerf_depth_train_step_apply": (c_i, [ctypes.POINTER(DepthStepConfig), ctypes.POINTER(DepthStepIo),
+                                            ctypes.POINTER(DepthStepArgs), c_fl, c_s]),
+}
+DPSTEP_HEADERS = (
+    ("experimental/plnerf_hip_dpstep.h", DPSTEP_SIGNATURES, {}),
+)
+DPSTEP_TABLE_SIGNATURES = _merge(DPSTEP_HEADERS)
+_disjoint(DPSTEP_TABLE_SIGNATURES, ALL_SIGNATURES)
+_disjoint(DPSTEP_TABLE_SIGNATURES, EXPERIMENTAL_SIGNATURES)
+_disjoint(DPSTEP_TABLE_SIGNATURES, CAMCODE_TABLE_SIGNATURES)
+
 _lib = None
 
 
@@ -404,7 +428,8 @@ def lib():
                 "plnerf_amd has no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
-        for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES}.items():
+        for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES,
+                                  **DPSTEP_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -14,6 +14,7 @@
 #include "ray_bwd_dev.h"
 #include "../../include/plnerf_hip_depthstep.h"
 #include "../../include/plnerf_hip_conststep.h"
+#include "../../include/experimental/plnerf_hip_dpstep.h"
 
 namespace {
 
@@ -139,21 +140,60 @@ extern "C" int plnerf_depth_ss_adam(float* scale, float* shift, const float* gra
 
 namespace {
 
-// mode: the entry's.  The Plan is the same in either (depth_last_stage says what lies where).
-int depth_train_step(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io, const plnerf_depth_step_args* a,
-                     void* workspace, size_t workspace_bytes, plnerf_stream_t stream, const int mode) {
+// The step in two halves (include/experimental/plnerf_hip_dpstep.h), as train_step.hip's: `grads` ends with both networks'
+// gradients (and, on a step of theirs, the scales' and shifts') complete, `apply` is the optimizers.
+
+// apply's own checks (with_config: not behind grads' checks, which have looked at the structs already)
+int check_apply(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io, const plnerf_depth_step_args* a,
+                const float grad_scale, const bool with_config) {
+    int rc;
+    if (with_config && (!c || !io || !a)) return PLNERF_EINVAL;
+    if (!(grad_scale > 0.0f) || !isfinite(grad_scale)) return PLNERF_EINVAL;
+    if (a->adam_step < 1) return PLNERF_EINVAL;
+    if (with_config) {
+        if ((rc = check_net(&io->coarse)) || (rc = check_net(&io->fine))) return rc;
+        if (a->ss_step && (c->n_views < 1 || a->ss_adam_step < 1 || !io->scale || !io->shift || !io->ss_grad || !io->ss_exp_avg ||
+                           !io->ss_exp_avg_sq))
+            return PLNERF_EINVAL;
+        if (a->ss_step && c->n_views > (1 << 24)) return PLNERF_ERANGE;      // (plnerf_depth_ss_adam's limit: before the first launch)
+    }
+    return PLNERF_OK;
+}
+
+int enqueue_apply(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io, const plnerf_depth_step_args* a,
+                  const float grad_scale, plnerf_stream_t stream) {
+    int rc;
+    // ---- the one optimizer over both networks: its gradient lies in two runs, the coarse network's first
+    //      (optim.FlatAdam.step), clipped inside the kernel (run_nerf_sample_based_depth.py:1155-1157) ----
+    const plnerf_step_net* nets[2] = {&io->coarse, &io->fine};
+    for (int j = 0; j < 2; ++j)
+        STEP_OK(plnerf_adam_step(nets[j]->param_flat, nets[j]->grad_flat, nets[j]->exp_avg, nets[j]->exp_avg_sq, nets[j]->n_params,
+                                 a->lr, c->beta1, c->beta2, c->adam_eps, a->adam_step, grad_scale, c->clip_value,
+                                 nets[j]->skip_if_set, nets[j]->skip_if_set2, nets[j]->withheld, stream));
+    // ---- the depth scales and shifts, unclipped (:1159-1161) ----
+    if (a->ss_step)
+        STEP_OK(plnerf_depth_ss_adam(io->scale, io->shift, io->ss_grad, io->ss_exp_avg, io->ss_exp_avg_sq, c->n_views, a->ss_lr,
+                                     c->ss_beta1, c->ss_beta2, c->ss_adam_eps, a->ss_adam_step, grad_scale, stream));
+    return PLNERF_OK;
+}
+
+// mode: the entry's.  The Plan is the same in either (depth_last_stage says what lies where).  whole_step: the one-call
+// entry, whose optimizer launches follow -- their checks stand where they always stood.
+int depth_train_step_grads(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io, const plnerf_depth_step_args* a,
+                           void* workspace, size_t workspace_bytes, plnerf_stream_t stream, const int mode,
+                           const bool whole_step) {
     // ---- every check first: a refused call enqueues nothing ----
     int rc = check_config(c, mode);
     if (rc) return rc;
     if (!io || !a || !workspace || ((uintptr_t)workspace % ALIGN) != 0) return PLNERF_EINVAL;
     if (a->rays < 1 || a->rays > c->max_rays || a->ray_id0 < 0 || a->view < 0 || a->view >= c->n_views) return PLNERF_EINVAL;
-    if (a->adam_step < 1) return PLNERF_EINVAL;
+    if (whole_step && (rc = check_apply(c, io, a, 1.0f, false))) return rc;
     if ((rc = check_net(&io->coarse)) || (rc = check_net(&io->fine))) return rc;
     if (!io->t_vals || !io->loss5 || (!c->perturb && !io->u_vals)) return PLNERF_EINVAL;
     if (!io->images || !io->hyp || !io->poses || !io->intrinsics) return PLNERF_EINVAL;
     const bool carve_on = a->carve != 0, ss = a->ss_step != 0;
-    if (ss && (!carve_on || a->ss_adam_step < 1 || !io->scale || !io->shift || !io->ss_grad || !io->ss_exp_avg ||
-               !io->ss_exp_avg_sq))
+    if (ss && (!carve_on || (whole_step && a->ss_adam_step < 1) || !io->scale || !io->shift || !io->ss_grad ||
+               (whole_step && (!io->ss_exp_avg || !io->ss_exp_avg_sq))))
         return PLNERF_EINVAL;
     if ((uint64_t)a->ray_id0 + (uint64_t)a->rays > (uint64_t)c->H * (uint64_t)c->W) return PLNERF_ERANGE;
     const Plan p = carve(c, workspace);
@@ -216,23 +256,35 @@ int depth_train_step(const plnerf_depth_step_config* c, const plnerf_depth_step_
                                 ps.white_bkgd, 0, p.g_rgb, nullptr, nullptr, nullptr, carve_on ? p.g_tau : nullptr,
                                 carve_on ? p.g_T : nullptr, p.bwd.g_raw_f, p.bwd.absmax_f, stream));
     }
-    STEP_OK(backward_nets(ps, r, p.coarse, p.fine, p.g_rgb0, p.bwd, layout, &io->coarse, &io->fine, stream));
+    return backward_nets(ps, r, p.coarse, p.fine, p.g_rgb0, p.bwd, layout, &io->coarse, &io->fine, stream);
+}
 
-    // ---- the one optimizer over both networks: its gradient lies in two runs, the coarse network's first
-    //      (optim.FlatAdam.step), clipped inside the kernel (run_nerf_sample_based_depth.py:1155-1157) ----
-    const plnerf_step_net* nets[2] = {&io->coarse, &io->fine};
-    for (int j = 0; j < 2; ++j)
-        STEP_OK(plnerf_adam_step(nets[j]->param_flat, nets[j]->grad_flat, nets[j]->exp_avg, nets[j]->exp_avg_sq, nets[j]->n_params,
-                                 a->lr, c->beta1, c->beta2, c->adam_eps, a->adam_step, 1.0f, c->clip_value, nets[j]->skip_if_set,
-                                 nets[j]->skip_if_set2, nets[j]->withheld, stream));
-    // ---- the depth scales and shifts, unclipped (:1159-1161) ----
-    if (ss)
-        STEP_OK(plnerf_depth_ss_adam(io->scale, io->shift, io->ss_grad, io->ss_exp_avg, io->ss_exp_avg_sq, c->n_views, a->ss_lr,
-                                     c->ss_beta1, c->ss_beta2, c->ss_adam_eps, a->ss_adam_step, 1.0f, stream));
-    return PLNERF_OK;
+int depth_train_step(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io, const plnerf_depth_step_args* a,
+                     void* workspace, size_t workspace_bytes, plnerf_stream_t stream, const int mode) {
+    const int rc = depth_train_step_grads(c, io, a, workspace, workspace_bytes, stream, mode, true);
+    return rc ? rc : enqueue_apply(c, io, a, 1.0f, stream);
 }
 
 }  // namespace
+
+// ---- the two halves on their own (include/experimental/plnerf_hip_dpstep.h) ----
+extern "C" int plnerf_depth_train_step_grads(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io,
+                                             const plnerf_depth_step_args* a, void* workspace, size_t workspace_bytes,
+                                             plnerf_stream_t stream) {
+    return depth_train_step_grads(c, io, a, workspace, workspace_bytes, stream, PLNERF_MODE_LINEAR, false);
+}
+
+extern "C" int plnerf_depth_train_step_const_grads(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io,
+                                                   const plnerf_depth_step_args* a, void* workspace, size_t workspace_bytes,
+                                                   plnerf_stream_t stream) {
+    return depth_train_step_grads(c, io, a, workspace, workspace_bytes, stream, PLNERF_MODE_CONSTANT, false);
+}
+
+extern "C" int plnerf_depth_train_step_apply(const plnerf_depth_step_config* c, const plnerf_depth_step_io* io,
+                                             const plnerf_depth_step_args* a, float grad_scale, plnerf_stream_t stream) {
+    const int rc = check_apply(c, io, a, grad_scale, true);
+    return rc ? rc : enqueue_apply(c, io, a, grad_scale, stream);
+}
 
 extern "C" size_t plnerf_depth_train_step_workspace_bytes(const plnerf_depth_step_config* config) {
     return workspace_bytes_of(config, PLNERF_MODE_LINEAR);

@@ -9,9 +9,14 @@
 // is duplicated here.
 // plnerf_train_step_const (include/plnerf_hip_conststep.h) is the same sequence in piecewise-constant mode -- the route
 // TrainStep._step takes for mode == "constant" and under constant_init: one function serves both, `mode` says which.
+// The sequence is written as two halves, up to the complete gradients and the optimizers: a data-parallel caller takes them
+// one by one with its exchange in between (include/experimental/plnerf_hip_dpstep.h), the one-call entries back to back.
+#include <math.h>
+
 #include "step_common.h"
 #include "../../include/plnerf_hip_batching.h"
 #include "../../include/plnerf_hip_conststep.h"
+#include "../../include/experimental/plnerf_hip_dpstep.h"
 
 namespace {
 
@@ -66,14 +71,46 @@ int check_config(const plnerf_step_config* c, const int mode) {
     return PLNERF_OK;
 }
 
-int train_step(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a, void* workspace,
-               size_t workspace_bytes, plnerf_stream_t stream, const int mode) {
+// The step in two halves (include/experimental/plnerf_hip_dpstep.h): `grads` ends with both networks' gradients complete,
+// `apply` is the optimizers.  A data-parallel caller sums the gradients over the ranks in between; the one-call entries are
+// grads + apply(1.0f).
+
+// apply's own checks (with_config: not behind grads' checks, which have looked at the structs already)
+int check_apply(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a, const float grad_scale,
+                const bool with_config) {
+    int rc;
+    if (with_config) {
+        if (!c || !io || !a) return PLNERF_EINVAL;
+        if ((rc = check_config(c, c->mode))) return rc;
+    }
+    if (!(grad_scale > 0.0f) || !isfinite(grad_scale)) return PLNERF_EINVAL;
+    if (a->adam_step_fine < 1 || a->adam_step_coarse < 1) return PLNERF_EINVAL;
+    if (with_config && ((rc = check_net(&io->coarse)) || (rc = check_net(&io->fine)))) return rc;
+    return PLNERF_OK;
+}
+
+// both optimizers, the fine network's first (run_plnerf.py:1302-1303)
+int enqueue_apply(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a, const float grad_scale,
+                  plnerf_stream_t stream) {
+    int rc;
+    STEP_OK(plnerf_adam_step(io->fine.param_flat, io->fine.grad_flat, io->fine.exp_avg, io->fine.exp_avg_sq, io->fine.n_params,
+                             a->lr_fine, c->beta1, c->beta2, c->adam_eps, a->adam_step_fine, grad_scale, 0.0f, io->fine.skip_if_set,
+                             io->fine.skip_if_set2, io->fine.withheld, stream));
+    STEP_OK(plnerf_adam_step(io->coarse.param_flat, io->coarse.grad_flat, io->coarse.exp_avg, io->coarse.exp_avg_sq,
+                             io->coarse.n_params, a->lr_coarse, c->beta1, c->beta2, c->adam_eps, a->adam_step_coarse, grad_scale,
+                             0.0f, io->coarse.skip_if_set, io->coarse.skip_if_set2, io->coarse.withheld, stream));
+    return PLNERF_OK;
+}
+
+// whole_step: the one-call entry, whose optimizer launches follow -- their checks stand where they always stood
+int train_step_grads(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a, void* workspace,
+                     size_t workspace_bytes, plnerf_stream_t stream, const int mode, const bool whole_step) {
     // ---- every check first: a refused call enqueues nothing ----
     int rc = check_config(c, mode);
     if (rc) return rc;
     if (!io || !a || !workspace || ((uintptr_t)workspace % ALIGN) != 0) return PLNERF_EINVAL;
     if (a->rays < 1 || a->rays > c->max_rays || a->ray_id0 < 0) return PLNERF_EINVAL;
-    if (a->adam_step_fine < 1 || a->adam_step_coarse < 1) return PLNERF_EINVAL;
+    if (whole_step && (rc = check_apply(c, io, a, 1.0f, false))) return rc;
     if ((rc = check_net(&io->coarse)) || (rc = check_net(&io->fine))) return rc;
     if (!io->t_vals || !io->loss4 || (!c->perturb && !io->u_vals)) return PLNERF_EINVAL;
     const int R = a->rays;
@@ -129,16 +166,13 @@ int train_step(const plnerf_step_config* c, const plnerf_step_io* io, const plne
     STEP_OK(plnerf_quad_bwd(p.fine.raw, p.fine.z, r.near, r.far, r.d, p.fine.noise, R, F, mode, ps.color_mode, ps.white_bkgd,
                             ps.farcolorfix, p.g_rgb, nullptr, nullptr, nullptr, nullptr, nullptr, p.bwd.g_raw_f, p.bwd.absmax_f,
                             stream));
-    STEP_OK(backward_nets(ps, r, p.coarse, p.fine, p.g_rgb0, p.bwd, layout, &io->coarse, &io->fine, stream));
+    return backward_nets(ps, r, p.coarse, p.fine, p.g_rgb0, p.bwd, layout, &io->coarse, &io->fine, stream);
+}
 
-    // ---- both optimizers, the fine network's first (run_plnerf.py:1302-1303) ----
-    STEP_OK(plnerf_adam_step(io->fine.param_flat, io->fine.grad_flat, io->fine.exp_avg, io->fine.exp_avg_sq, io->fine.n_params,
-                             a->lr_fine, c->beta1, c->beta2, c->adam_eps, a->adam_step_fine, 1.0f, 0.0f, io->fine.skip_if_set,
-                             io->fine.skip_if_set2, io->fine.withheld, stream));
-    STEP_OK(plnerf_adam_step(io->coarse.param_flat, io->coarse.grad_flat, io->coarse.exp_avg, io->coarse.exp_avg_sq,
-                             io->coarse.n_params, a->lr_coarse, c->beta1, c->beta2, c->adam_eps, a->adam_step_coarse, 1.0f, 0.0f,
-                             io->coarse.skip_if_set, io->coarse.skip_if_set2, io->coarse.withheld, stream));
-    return PLNERF_OK;
+int train_step(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a, void* workspace,
+               size_t workspace_bytes, plnerf_stream_t stream, const int mode) {
+    const int rc = train_step_grads(c, io, a, workspace, workspace_bytes, stream, mode, true);
+    return rc ? rc : enqueue_apply(c, io, a, 1.0f, stream);
 }
 
 }  // namespace
@@ -162,4 +196,21 @@ extern "C" size_t plnerf_train_step_const_workspace_bytes(const plnerf_step_conf
 extern "C" int plnerf_train_step_const(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a,
                                        void* workspace, size_t workspace_bytes, plnerf_stream_t stream) {
     return train_step(c, io, a, workspace, workspace_bytes, stream, PLNERF_MODE_CONSTANT);
+}
+
+// ---- the two halves on their own (include/experimental/plnerf_hip_dpstep.h) ----
+extern "C" int plnerf_train_step_grads(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a,
+                                       void* workspace, size_t workspace_bytes, plnerf_stream_t stream) {
+    return train_step_grads(c, io, a, workspace, workspace_bytes, stream, PLNERF_MODE_LINEAR, false);
+}
+
+extern "C" int plnerf_train_step_const_grads(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a,
+                                             void* workspace, size_t workspace_bytes, plnerf_stream_t stream) {
+    return train_step_grads(c, io, a, workspace, workspace_bytes, stream, PLNERF_MODE_CONSTANT, false);
+}
+
+extern "C" int plnerf_train_step_apply(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a,
+                                       float grad_scale, plnerf_stream_t stream) {
+    const int rc = check_apply(c, io, a, grad_scale, true);
+    return rc ? rc : enqueue_apply(c, io, a, grad_scale, stream);
 }

@@ -802,7 +802,8 @@ class DepthTrainStep:
     z_vals and z_vals0 as VIEWS of the plan's workspace -- valid until that plan's next step, like last_pixels; `raw`,
     `weights`, `weights0` and `u` are not provided on this route.  With one_call=True the depth scales' and shifts' Adam is
     plnerf_depth_ss_adam on EVERY step of this object, one-call or not (moments in a [2, V] pair the step owns: a mixed run
-    has one arithmetic); with one_call=False it stays torch.optim.Adam."""
+    has one arithmetic); with one_call=False it stays torch.optim.Adam.  Under data parallelism a qualifying step (not
+    is_joint; train.ONE_CALL_DP) is two library calls around the gradient all-reduce (_run_plan) and counts the same."""
 
     def __init__(self, args, render_kwargs_train, optimizer, grad_vars, distributed=None, range_check_every=100, seed=0,
                  counter_rng=True, start=0, n_views=None, one_call=False, one_call_const=False):
@@ -922,13 +923,19 @@ class DepthTrainStep:
         """Can this step go to the library as one call (plnerf_depth_train_step)?  What the entry enqueues is the fused route
         of _step with the merged backward: two native networks in one 16-bit guarded precision and with one density
         activation, piecewise-linear mode with importance sampling, counter-based draws, the kernels' own encoding on an
-        identity bounding box, no camera code, a batch that fits one launch per network, one process, nobody watching the
-        stages (STAGE_TAP, functional.KERNEL_TIMER), not `pytest`.  kw["mode"] == "constant" qualifies the same way for
+        identity bounding box, no camera code, a batch that fits one launch per network, nobody watching the stages
+        (STAGE_TAP, functional.KERNEL_TIMER), not `pytest`, and one process -- or, with train.ONE_CALL_DP, a rank of a
+        data-parallel run without is_joint (whose hypothesis choice needs a collective in the middle of the forward,
+        functional.joint_choice): its step is then two library calls around the gradient exchange (_run_plan).  kw["mode"] == "constant" qualifies the same way for
         plnerf_depth_train_step_const when one_call_const is set (N_samples >= 3), piecewise-linear mode when one_call is.
         Returns the networks' input scale, or None."""
         kw = self.kw
-        if not (self.merged_backward and self.draws is not None and self.bucket is None and len(self.nets) == 2):
+        if not (self.merged_backward and self.draws is not None and len(self.nets) == 2):
             return None
+        if self.bucket is not None:
+            from . import train
+            if not train.ONE_CALL_DP or getattr(self.args, "is_joint", False):
+                return None
         if STAGE_TAP is not None or Fn.KERNEL_TIMER is not None or not FUSE_STAGES or not isinstance(views, DepthViews):
             return None
         S, N = int(kw.get("N_samples", 0)), int(kw.get("N_importance", 0))
@@ -964,7 +971,8 @@ class DepthTrainStep:
         """The DepthStepPlan of this configuration: the one in hand while it still describes the live buffers, else a new
         one (None: the optimizer is not a FlatAdam over exactly the two networks)."""
         from . import stepplan
-        key = stepplan.depth_plan_key(self.args, self.kw, max_rays, views, self.seed) + (input_scale,) + tuple(
+        sharded = self.bucket is not None      # (a data-parallel plan is guarded by the reduced status tails)
+        key = stepplan.depth_plan_key(self.args, self.kw, max_rays, views, self.seed) + (input_scale, sharded) + tuple(
             t.data_ptr() for t in (self.depth_scales, self.depth_shifts, self._ss_grad, self._ss_m, self._ss_v))
         plan = self._plan
         if plan is not None and key == self._plan_key and plan.current():
@@ -974,9 +982,28 @@ class DepthTrainStep:
             return None
         self._plan = stepplan.DepthStepPlan(self.args, self.kw, self.nets, self.optimizer, views, max_rays, self.seed,
                                             input_scale, self.depth_scales.detach(), self.depth_shifts.detach(), self._ss_grad,
-                                            self._ss_m, self._ss_v)
+                                            self._ss_m, self._ss_v, data_parallel=sharded)
         self._plan_key = key
         return self._plan
+
+    def _run_plan(self, plan, *args, ss_step=False, **kw):
+        """One step through `plan` (DepthStepPlan.run's arguments and return value).  One process: ONE library call.  A rank
+        of a data-parallel run: the gradients' half; ONE in-place SUM all-reduce of the plan's gradient block (both
+        networks' gradients and status tails; dp.GradientBucket.reduce_block) and, on a step of the scales and shifts, the
+        small one of their gradient, as _scale_shift_grad issues it; then the optimizers' half with 1 / world inside the
+        step kernels, guarded by the reduced tails -- what _step does on the Python-driven route."""
+        if self.bucket is None:
+            return plan.run(*args, ss_step=ss_step, **kw)
+        loss5 = plan.run_grads(*args, ss_step=ss_step, **kw)
+        ss_work = None
+        if ss_step:
+            ss_work = torch.distributed.all_reduce(self._ss_grad, op=torch.distributed.ReduceOp.SUM, group=self.bucket.group,
+                                                   async_op=True)
+        scale = self.bucket.reduce_block(plan.grad_block)
+        if ss_work is not None:
+            ss_work.wait()
+        plan.apply(scale)
+        return loss5
 
     def _step_view_one_call(self, views, img_i, n_rand, i):
         """step_view through plnerf_depth_train_step; None when the step does not qualify (nothing has happened then)."""
@@ -993,9 +1020,9 @@ class DepthTrainStep:
         ss_step = scaleshift_steps(i, warm, getattr(a, "freeze_ss", 0), weight)
         if ss_step:
             self._ss_steps += 1
-        loss5 = plan.run(int(img_i), n_rand, self.global_step, self.rank * n_rand, self.optimizer.param_groups[0]['lr'],
-                         adam_step, weight > 0. and i > warm, ss_step, float(getattr(a, "scaleshift_lr", 1e-6)), self._ss_steps,
-                         mode=mode)
+        loss5 = self._run_plan(plan, int(img_i), n_rand, self.global_step, self.rank * n_rand,
+                               self.optimizer.param_groups[0]['lr'], adam_step, weight > 0. and i > warm, ss_step=ss_step,
+                               ss_lr=float(getattr(a, "scaleshift_lr", 1e-6)), ss_adam_step=self._ss_steps, mode=mode)
         self.last_pixels = plan.view_of("pixels", (n_rand, 2), torch.int32)
         self.global_step += 1
         if mode == "constant":

@@ -153,6 +153,21 @@ class GradientBucket:
         for mi in idx:
             self._launch(mi)
 
+    def reduce_block(self, block, group=None):
+        """A caller-owned flat block -- stepplan's grad_block: both networks' gradients, a status tail behind each, back to
+        back as the merged backward lays them -- summed over the ranks IN PLACE as ONE collective, issued as this bucket
+        issues its own (async; the current stream then waits for it) and counted in `collectives`.  Returns the factor the
+        caller still owes the gradients: 1 / world (the block holds the SUM, tails included: a non-zero tail = some rank's
+        forward of that network left the half range)."""
+        group = group if group is not None else self.group
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.collectives = 0
+        if world == 1:
+            return 1.0
+        dist.all_reduce(block, op=dist.ReduceOp.SUM, group=group, async_op=True).wait()
+        self.collectives = 1
+        return 1.0 / world
+
     def _flat_with_tail(self, m):
         """The module's gradient as ONE buffer with its status tail (functional._grad_buffer's layout), or None."""
         from .optim import flat_view_of

@@ -13,6 +13,11 @@ live objects, and train.TrainStep builds a new one when it does not.  A plan nev
 written once: the config fields in onecall's fillers (which the frame renderers use too, and from whose tuples the plan
 keys are built), and in `_Plan` below the workspace that serves both modes' entries, the gradient block, the two _NetSlots
 and the tail of a step; `_flat_adam_over` is the test both supported() start from.
+
+A rank of a data-parallel run takes the step as its two halves (include/experimental/plnerf_hip_dpstep.h): `run_grads(...)`
+enqueues everything up to the complete gradients, the caller sums `grad_block` over the ranks (ONE all-reduce: both networks'
+gradients and their status tails lie back to back there), and `apply(1 / world)` enqueues the optimizers.  A plan built with
+`data_parallel=True` guards those optimizers by the reduced tails instead of the networks' own status words.
 """
 import ctypes
 
@@ -36,7 +41,10 @@ class _NetSlot:
     parameters `first` .. `first + 23` of the optimizer's one flat group: all of it (an optimizer per network, StepPlan)
     or one half (the depth loop's one optimizer over both networks, DepthStepPlan)."""
 
-    def __init__(self, net, opt, grad_flat, io_net, others, first=0, launches=1):
+    def __init__(self, net, opt, grad_flat, io_net, others, first=0, launches=1, tails=None):
+        """tails: a data-parallel step's guard words instead of the optimizer's own -- 1-element views of the reduced range
+        status tails in the plan's gradient block (_Plan._build), what FlatAdam.step takes as `guards=` on the Python
+        route."""
         self.net, self.opt, self.io = net, opt, io_net
         self.group = opt.param_groups[0]
         self.all_ps = self.group['params']
@@ -68,7 +76,10 @@ class _NetSlot:
                 words.append(g.data_ptr())
             else:
                 raise ValueError("a guard that is neither of the step's networks nor a device word")
-        opt._guarded_now = bool(self.guards)
+        if tails is not None:
+            words = [t.data_ptr() for t in tails]
+        self.guarded = bool(words)         # what FlatAdam.step leaves in _guarded_now: was this step's launch guarded at all
+        opt._guarded_now = self.guarded
         wptr = opt._withheld_ptr(self.fl['param'].device)
         self.withheld = opt._withheld
         self.steps = None
@@ -107,7 +118,7 @@ class _NetSlot:
         """What FlatAdam.step leaves on the host after its one launch."""
         torch._foreach_add_(self.steps, 1.0)
         self.fl['uniform_step'] = float(self.steps[0])
-        self.opt._guarded_now = bool(self.guards)
+        self.opt._guarded_now = self.guarded
         self.opt._launches_per_step = self.launches
         ps, grads = self.ps, self.grads
         if ps[0].grad is not grads[0] or ps[-1].grad is not grads[-1]:      # (the other route, or a zero_grad, replaced them)
@@ -132,10 +143,14 @@ def _flat_adam_over(opt, params, nets):
 class _Plan:
     """What both plans are made of behind their filled config."""
     ENTRY = ENTRY_CONST = None      # the entry point and its piecewise-constant sibling: same structs, same workspace
+    # (include/experimental/plnerf_hip_dpstep.h: ENTRY + "_grads" / ENTRY_CONST + "_grads", then ENTRY + "_apply" for both)
 
-    def _build(self, cfg, io, args, nets, opts, firsts, launches):
+    def _build(self, cfg, io, args, nets, opts, firsts, launches, guarded_by=None):
         """opts[k], firsts[k]: network k's optimizer and the index of its first parameter in that optimizer's flat group;
-        launches: _NetSlot's."""
+        launches: _NetSlot's.  guarded_by: a data-parallel plan -- guarded_by[k] are the networks (0 coarse, 1 fine) whose
+        reduced status tails guard network k's optimizer launch, instead of the optimizer's own guards: the tail of network
+        j is the float behind its gradients in grad_block, which the caller's SUM all-reduce of grad_block leaves non-zero
+        as a 32-bit word exactly when some rank's forward of that network left the half range."""
         dev = self.device = nets[0].param_list()[0].device
         self.config, self.io, self.args = cfg, io, args
         # ONE workspace for both entries (they carve it alike): a constant_init warm-up switches entries between steps on
@@ -159,15 +174,32 @@ class _Plan:
         n24 = L.N_PARAM_TENSORS
         sizes = [sum(o._flat[0]['sizes'][first:first + n24]) + Fn.GRAD_TAIL for o, first in zip(opts, firsts)]
         self.grad_block = torch.zeros(sum(sizes), device=dev, dtype=torch.float32)
-        self.slots = (_NetSlot(nets[0], opts[0], self.grad_block[:sizes[0]], io.coarse, nets, firsts[0], launches),
-                      _NetSlot(nets[1], opts[1], self.grad_block[sizes[0]:], io.fine, nets, firsts[1], launches))
+        blocks = (self.grad_block[:sizes[0]], self.grad_block[sizes[0]:])
+        self.tails = tuple(b[-Fn.GRAD_TAIL:-Fn.GRAD_TAIL + 1] for b in blocks)      # (coarse, fine): [n_params] of each block
+        self.data_parallel = guarded_by is not None
+        by = guarded_by if guarded_by is not None else (None, None)
+        self.slots = tuple(_NetSlot(nets[k], opts[k], blocks[k], (io.coarse, io.fine)[k], nets, firsts[k], launches,
+                                    None if by[k] is None else [self.tails[j] for j in by[k]]) for k in (0, 1))
         self._refs = (ctypes.byref(cfg), ctypes.byref(io), ctypes.byref(args), ctypes.c_void_p(self.workspace.data_ptr()))
+
+    def _enqueue(self, mode, suffix=""):
+        entry = (self.ENTRY_CONST if mode == "constant" else self.ENTRY) + suffix
+        cfg, io, args, ws = self._refs
+        L.check(getattr(L.lib(), entry)(cfg, io, args, ws, self.workspace_bytes, L.stream()), entry)
 
     def _step(self, mode):
         """Enqueue the step the structs describe through `mode`'s entry; leave on the host what FlatAdam.step would."""
-        entry = self.ENTRY_CONST if mode == "constant" else self.ENTRY
-        cfg, io, args, ws = self._refs
-        L.check(getattr(L.lib(), entry)(cfg, io, args, ws, self.workspace_bytes, L.stream()), entry)
+        self._enqueue(mode)
+        self.slots[0].advance()
+        self.slots[1].advance()
+
+    def apply(self, grad_scale=1.0):
+        """The second half of a step begun by run_grads (the structs still describe it): the optimizer launches, every
+        gradient entry multiplied by grad_scale (1 / world once grad_block holds the SUM over the ranks); leaves on the
+        host what FlatAdam.step would."""
+        entry = self.ENTRY + "_apply"
+        cfg, io, args, _ = self._refs
+        L.check(getattr(L.lib(), entry)(cfg, io, args, float(grad_scale), L.stream()), entry)
         self.slots[0].advance()
         self.slots[1].advance()
 
@@ -184,7 +216,10 @@ class StepPlan(_Plan):
             opts[0].param_groups[0]['betas'] == opts[1].param_groups[0]['betas'] and \
             opts[0].param_groups[0]['eps'] == opts[1].param_groups[0]['eps']
 
-    def __init__(self, kw, nets, opts, kind, max_rays, H, W, K, near, far, seed, bank=None):
+    def __init__(self, kw, nets, opts, kind, max_rays, H, W, K, near, far, seed, bank=None, data_parallel=False):
+        """data_parallel: the plan of a rank's share of a step (run_grads, the caller's SUM all-reduce of grad_block,
+        apply(1 / world)): the fine optimizer is guarded by both networks' reduced status tails, the coarse one by the
+        coarse network's, as train.TrainStep._exchange_and_step guards them."""
         self.kind = kind
         self.bank = bank
         cfg = L.StepConfig()
@@ -195,7 +230,7 @@ class StepPlan(_Plan):
         cfg.n_views = len(bank.i_train) if bank is not None else 0
         cfg.bank_seed = int(bank.seed) if bank is not None else 0
         io, args = L.StepIo(), L.StepArgs()
-        self._build(cfg, io, args, nets, opts, (0, 0), 1)
+        self._build(cfg, io, args, nets, opts, (0, 0), 1, ((0,), (0, 1)) if data_parallel else None)
         if bank is not None:
             io.views, io.poses, io.images = bank.views.data_ptr(), bank.poses.data_ptr(), bank.images.data_ptr()
             self.bank_ptrs = (io.views, io.poses, io.images)
@@ -213,12 +248,26 @@ class StepPlan(_Plan):
         c, f = self.slots[0].next_adam_step(), self.slots[1].next_adam_step()
         return None if (c is None or f is None) else (c, f)
 
-    def run(self, rays, step, ray_id0, lr_coarse, lr_fine, adam_steps, loss_scale=1.0, c2w=None, image=None, crop=None,
-            epoch=0, pos0=0, mode="linear"):
+    def run(self, *args, mode="linear", **kw):
         """Enqueue one step on the current stream; returns its loss4 = [total, fine, coarse, psnr] (a fresh tensor: an
-        earlier step's stays what it was).  c2w: 12 host floats; image: the view's [H, W, 3] fp32 device tensor; crop:
-        (r0, c0, rows, cols).  mode "constant": the step in piecewise-constant mode (plnerf_train_step_const), one of
-        self.modes."""
+        earlier step's stays what it was).  Arguments: _describe's.  mode "constant": the step in piecewise-constant mode
+        (plnerf_train_step_const), one of self.modes."""
+        loss4 = self._describe(*args, mode=mode, **kw)
+        self._step(mode)
+        return loss4
+
+    def run_grads(self, *args, mode="linear", **kw):
+        """run's first half (plnerf_train_step_grads / plnerf_train_step_const_grads): everything up to the complete
+        gradients in grad_block, no optimizer launch and nothing advanced on the host; apply() is the second half.
+        Same arguments, same return value."""
+        loss4 = self._describe(*args, mode=mode, **kw)
+        self._enqueue(mode, "_grads")
+        return loss4
+
+    def _describe(self, rays, step, ray_id0, lr_coarse, lr_fine, adam_steps, loss_scale=1.0, c2w=None, image=None, crop=None,
+                  epoch=0, pos0=0, mode="linear"):
+        """Write one step into the structs.  c2w: 12 host floats; image: the view's [H, W, 3] fp32 device tensor; crop:
+        (r0, c0, rows, cols).  Returns the tensor the step's loss4 goes to."""
         a = self.args
         a.rays, a.step, a.ray_id0 = rays, step, ray_id0
         if self.kind == "view":
@@ -233,7 +282,6 @@ class StepPlan(_Plan):
         loss4 = torch.empty(4, device=self.device)
         self.io.loss4 = loss4.data_ptr()
         self.config.mode = L.MODE[mode]
-        self._step(mode)
         return loss4
 
 
@@ -259,7 +307,8 @@ class DepthStepPlan(_Plan):
         return _flat_adam_over(opt, list(nets[0].param_list()) + list(nets[1].param_list()), nets)
 
     def __init__(self, args, kw, nets, opt, views, max_rays, seed, input_scale, scale, shift, ss_grad, ss_m, ss_v,
-                 ss_betas=(0.9, 0.999), ss_eps=1e-8):
+                 ss_betas=(0.9, 0.999), ss_eps=1e-8, data_parallel=False):
+        """data_parallel: as StepPlan's; both halves of the one optimizer are guarded by both networks' reduced tails."""
         g = lambda name, default: getattr(args, name, default)
         self.views = views
         cfg = L.DepthStepConfig()
@@ -276,7 +325,8 @@ class DepthStepPlan(_Plan):
         cfg.ss_beta1, cfg.ss_beta2, cfg.ss_adam_eps = float(ss_betas[0]), float(ss_betas[1]), float(ss_eps)
         io = L.DepthStepIo()
         # the flat group's two halves, which FlatAdam.step walks as two runs (one plnerf_adam_step launch each)
-        self._build(cfg, io, L.DepthStepArgs(), nets, (opt, opt), (0, L.N_PARAM_TENSORS), 2)
+        self._build(cfg, io, L.DepthStepArgs(), nets, (opt, opt), (0, L.N_PARAM_TENSORS), 2,
+                    ((0, 1), (0, 1)) if data_parallel else None)
         # (both entries carve the workspace alike, so one layout serves either)
         entry = self.ENTRY if "linear" in self.modes else self.ENTRY_CONST
         self.layout = L.DepthStepViews()
@@ -302,17 +352,29 @@ class DepthStepPlan(_Plan):
         c, f = self.slots[0].next_adam_step(), self.slots[1].next_adam_step()
         return c if (c is not None and c == f) else None
 
-    def run(self, view, rays, step, ray_id0, lr, adam_step, carve, ss_step=False, ss_lr=0.0, ss_adam_step=0, mode="linear"):
+    def run(self, *args, mode="linear", **kw):
         """Enqueue one step on the current stream; returns its loss5 = [total, image, image (coarse), space carving, psnr]
-        (a fresh tensor: an earlier step's stays what it was).  mode "constant": plnerf_depth_train_step_const (one of
-        self.modes)."""
+        (a fresh tensor: an earlier step's stays what it was).  Arguments: _describe's.  mode "constant":
+        plnerf_depth_train_step_const (one of self.modes)."""
+        loss5 = self._describe(*args, **kw)
+        self._step(mode)
+        return loss5
+
+    def run_grads(self, *args, mode="linear", **kw):
+        """run's first half (plnerf_depth_train_step_grads / _const_grads): up to the complete gradients in grad_block and,
+        with ss_step, ss_grad; no optimizer launch, nothing advanced on the host; apply() is the second half."""
+        loss5 = self._describe(*args, **kw)
+        self._enqueue(mode, "_grads")
+        return loss5
+
+    def _describe(self, view, rays, step, ray_id0, lr, adam_step, carve, ss_step=False, ss_lr=0.0, ss_adam_step=0):
+        """Write one step into the structs; returns the tensor its loss5 goes to."""
         a = self.args
         a.view, a.rays, a.step, a.ray_id0 = view, rays, step, ray_id0
         a.lr, a.adam_step = lr, adam_step
         a.carve, a.ss_step, a.ss_lr, a.ss_adam_step = int(carve), int(ss_step), ss_lr, ss_adam_step
         loss5 = torch.empty(5, device=self.device)
         self.io.loss5 = loss5.data_ptr()
-        self._step(mode)
         return loss5
 
     def view_of(self, name, shape, dtype=torch.float32):

@@ -29,6 +29,11 @@ from .render import render, render_rays
 
 Rn = sys.modules[render_rays.__module__]      # (the module: the package attribute `render` is the function)
 
+# Data-parallel steps of a TrainStep / depth.DepthTrainStep with one_call / one_call_const take the one-call route too, as two
+# library calls around the ONE gradient all-reduce (stepplan's run_grads / apply; include/experimental/plnerf_hip_dpstep.h).
+# False: they take the Python-driven route, as before (tests and tools/bench_one_call_dp.py build their yardstick so).
+ONE_CALL_DP = True
+
 
 class _MseFn(torch.autograd.Function):
     """mean((x - y) ** 2) with a two-launch backward (autograd's chain for the expression is seven)."""
@@ -279,7 +284,9 @@ class TrainStep:
         # one_call=True: step_view / step_batch hand every step that qualifies (_one_call_ok) to the library as ONE call --
         # plnerf_train_step enqueues the launch sequence of the fused route below itself, bit for bit the same step, without
         # the ~23 Python -> ctypes -> autograd round trips between the launches (stepplan.StepPlan holds its buffers).  A
-        # step that does not qualify takes the route below, silently; one_call_steps counts the ones that did.
+        # step that does not qualify takes the route below, silently; one_call_steps counts the ones that did.  Under data
+        # parallelism (ONE_CALL_DP) a qualifying step is two library calls around the gradient all-reduce (_run_plan) and
+        # counts the same.
         self.one_call = bool(one_call)
         self.one_call_steps = 0
         # one_call_const=True (on its own or beside one_call): a step that qualifies in every respect but renders in
@@ -333,17 +340,23 @@ class TrainStep:
         n_rand = int(n_rand if n_rand is not None else self.args.N_rand)
         want_vd = bool(self.kw.get("use_viewdirs", True))
         epoch, p0, n = bank.schedule(self.global_step, n_rand * self.world)
-        # (one process: the whole batch, weight 1)
-        mode = self._one_call_mode(n) if ((self.one_call or self.one_call_const) and n <= n_rand) else None
+        begin, end = dp.shard_batch(n, self.rank, self.world)
+        # (one process: the whole batch, weight 1; a rank without rays: the stand-in ray at weight 0, as below)
+        rays = max(end - begin, 1)
+        mode = self._one_call_mode(rays) if ((self.one_call or self.one_call_const) and rays <= n_rand) else None
         if mode is not None:
             plan = self._plan_for("bank", n_rand, bank.H, bank.W, bank.K, bank.near, bank.far, bank)
             steps = plan.adam_steps() if (plan is not None and mode in plan.modes) else None
             if steps is not None:
-                self.last_batch = (epoch, p0, n, 0, n)
-                return self._one_call_done(plan.run(n, self.global_step, 0, self.optimizer_coarse.param_groups[0]['lr'],
-                                                    self.optimizer.param_groups[0]['lr'], steps, epoch=epoch, pos0=p0,
-                                                    mode=mode), mode)
-        begin, end = dp.shard_batch(n, self.rank, self.world)
+                self.last_batch = (epoch, p0 + begin, end - begin, begin, n)
+                out = self._one_call_done(self._run_plan(
+                    plan, rays, self.global_step, begin, self.optimizer_coarse.param_groups[0]['lr'],
+                    self.optimizer.param_groups[0]['lr'], steps, loss_scale=self.world * (end - begin) / n, epoch=epoch,
+                    pos0=p0 + begin if end > begin else p0, mode=mode), mode)
+                if end == begin:
+                    nan = torch.full((), float("nan"), device=out[0].device)
+                    return nan, nan.clone()
+                return out
         self.last_batch = (epoch, p0 + begin, end - begin, begin, n)      # (epoch, first position, rays, offset, global n)
         if end > begin:
             cols, target, _ = bank.select(epoch, p0 + begin, end - begin, want_vd)
@@ -370,11 +383,13 @@ class TrainStep:
         "constant" (plnerf_train_step_const, with one_call_const) or None?  What an entry enqueues is the fused route of
         _step with the merged backward: the reference's two native networks in one 16-bit precision (merged_backward_ok's
         conditions, known here before anything runs), importance sampling, counter-based draws, the kernels' own encoding,
-        a batch that fits one launch per network, one process, nobody watching the stages (render.STAGE_TAP,
-        functional.KERNEL_TIMER).  The step's mode is the render's: kw["mode"], or constant under the constant_init warm-up;
+        a batch that fits one launch per network, nobody watching the stages (render.STAGE_TAP, functional.KERNEL_TIMER),
+        and one process -- or, with ONE_CALL_DP, a rank of a data-parallel run, whose step is then the two calls of
+        _run_plan around the gradient exchange.  The step's mode is the render's: kw["mode"], or constant under the constant_init warm-up;
         constant mode also needs its one-launch coarse stage (render.FUSE_CONST_EPILOGUE, N_samples >= 3)."""
         kw = self.kw
-        if not (self.merged_backward and self.draws is not None and self.bucket is None and len(self.nets) == 2):
+        if not (self.merged_backward and self.draws is not None and (self.bucket is None or ONE_CALL_DP) and
+                len(self.nets) == 2):
             return None
         if Rn.STAGE_TAP is not None or Fn.KERNEL_TIMER is not None:
             return None
@@ -405,7 +420,8 @@ class TrainStep:
     def _plan_for(self, kind, max_rays, H, W, K, near, far, bank):
         """The StepPlan of this configuration: the one in hand while it still describes the live buffers, else a new one
         (None: the optimizers are not FlatAdams over exactly the two networks)."""
-        key = stepplan.plan_key(self.kw, kind, max_rays, H, W, K, near, far, bank, self.seed)
+        sharded = self.bucket is not None      # (a data-parallel plan is guarded by the reduced status tails)
+        key = stepplan.plan_key(self.kw, kind, max_rays, H, W, K, near, far, bank, self.seed) + (sharded,)
         plan = self._plan
         if plan is not None and key == self._plan_key and plan.current():
             return plan
@@ -413,9 +429,21 @@ class TrainStep:
         opts = (self.optimizer_coarse, self.optimizer)
         if not stepplan.StepPlan.supported(self.nets, opts):
             return None
-        self._plan = stepplan.StepPlan(self.kw, self.nets, opts, kind, max_rays, H, W, K, near, far, self.seed, bank)
+        self._plan = stepplan.StepPlan(self.kw, self.nets, opts, kind, max_rays, H, W, K, near, far, self.seed, bank,
+                                       data_parallel=sharded)
         self._plan_key = key
         return self._plan
+
+    def _run_plan(self, plan, *args, **kw):
+        """One step through `plan` (StepPlan.run's arguments and return value).  One process: ONE library call.  A rank of a
+        data-parallel run: the gradients' half, ONE in-place SUM all-reduce of the plan's gradient block (both networks'
+        gradients and their status tails; dp.GradientBucket.reduce_block), then the optimizers' half with 1 / world inside
+        the step kernels, guarded by the reduced tails -- what _exchange_and_step does on the Python-driven route."""
+        if self.bucket is None:
+            return plan.run(*args, **kw)
+        loss4 = plan.run_grads(*args, **kw)
+        plan.apply(self.bucket.reduce_block(plan.grad_block))
+        return loss4
 
     def _step_view_one_call(self, H, W, K, c2w, image, near, far, n_rand, precrop):
         """step_view through plnerf_train_step or plnerf_train_step_const; None when the step does not qualify (nothing has
@@ -434,9 +462,10 @@ class TrainStep:
             crop = (0, 0, H, W)
         c2w_host = [float(v) for v in torch.as_tensor(c2w, device="cpu")[:3, :4].reshape(-1)]
         img = image.detach().to(torch.float32).contiguous()
-        return self._one_call_done(plan.run(n_rand, self.global_step, self.rank * n_rand,
-                                            self.optimizer_coarse.param_groups[0]['lr'], self.optimizer.param_groups[0]['lr'],
-                                            steps, c2w=c2w_host, image=img, crop=crop, mode=mode), mode)
+        return self._one_call_done(self._run_plan(plan, n_rand, self.global_step, self.rank * n_rand,
+                                                  self.optimizer_coarse.param_groups[0]['lr'],
+                                                  self.optimizer.param_groups[0]['lr'], steps, c2w=c2w_host, image=img,
+                                                  crop=crop, mode=mode), mode)
 
     def _one_call_done(self, loss4, mode="linear"):
         """The host state _step leaves behind: both learning rates, the step count, the range poll."""
