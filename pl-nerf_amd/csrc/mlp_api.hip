@@ -3,6 +3,7 @@
 // mode), mlp_h16.hip (the 16-bit-operand MFMA modes, bf16 and IEEE-half elements, plain and 3-term split: ping-pong
 // forward and dgrad chain) and mlp_rr.hip (their register-resident forward).
 #include "common.h"
+#include "mlp_bwd_plan.h"
 #include "mlp_fwd_route.h"
 #include "mlp_internal.h"
 #include "mlp_layout.h"
@@ -89,11 +90,7 @@ extern "C" int plnerf_mlp_saved_layout(int precision, int has_embedded, int fwd_
 
 extern "C" size_t plnerf_mlp_bwd_workspace_bytes(int n_rows, int precision) {
     if (!known(precision) || n_rows < 0) return 0;
-    const size_t partials = ((size_t)lay::MAX_SPLITS * lay::PART_PER_SPLIT + (size_t)lay::MAX_HEAD_WGS * lay::HEAD_PART +
-                             (size_t)lay::GRED_FLOATS) * sizeof(float);      // (+ the reduced G and s of the composed view layer)
-    const size_t g_eff = (size_t)n_rows * 16;      // the upstream gradient after the density activation's derivative
-    if (precision == PLNERF_PREC_FP32) return (size_t)lay::DZ_PER_ROW * (size_t)n_rows * sizeof(float) + partials + g_eff;
-    return impl::h16_dz_bytes(n_rows) + lay::WSH_SCALARS_BYTES + partials + g_eff;
+    return bwdplan::workspace((size_t)n_rows, ns_of(precision) != 0).total;
 }
 
 extern "C" int plnerf_mlp_fwd(const void* packed, int precision, const float* pts, const float* viewdirs,
@@ -149,57 +146,45 @@ extern "C" int plnerf_mlp_bwd_multi(int n_jobs, const void* const* packed, int p
             if (!grads[j * PLNERF_N_PARAM_TENSORS + i]) return PLNERF_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
-    const size_t part_only = ((size_t)lay::MAX_SPLITS * lay::PART_PER_SPLIT + (size_t)lay::MAX_HEAD_WGS * lay::HEAD_PART) * sizeof(float);
-    const size_t part_bytes = part_only + (size_t)lay::GRED_FLOATS * sizeof(float);
-    if (precision == PLNERF_PREC_FP32) {
-        for (int j = 0; j < n_jobs; ++j) {
-            float* dz = (float*)workspace[j];
-            float* partials = dz + (size_t)lay::DZ_PER_ROW * (size_t)n_rows[j];
-            const float* g = g_raw[j];
-            if (act) {      // the activation's derivative first: every kernel below reads the effective gradient
-                float* g_eff = (float*)((unsigned char*)partials + part_bytes);
-                const int rc0 = impl::absmax_act(g, raw_out[j], density_beta, n_rows[j], g_eff, nullptr, st);
-                if (rc0) return rc0;
-                g = g_eff;
-            }
-            int rc = impl::f32_dgrad(packed[j], g, n_rows[j], (const float*)saved[j], dz, st);
-            if (rc) return rc;
-            rc = impl::wgrad(g, n_rows[j], saved[j], dz, nullptr, partials, grads + j * PLNERF_N_PARAM_TENSORS, input_ch,
-                             input_ch_views, false, lay::SV_LAYOUT_ROWS, nullptr, status_out ? status_out[j] : nullptr, st);
-            if (rc) return rc;
-        }
-        return PLNERF_OK;
-    }
-    // 16-bit modes: [dz half planes][max |g_raw|][partials][g_eff]
+    // The job's workspace, carved by the one layout (mlp_bwd_plan.h).  The exact-fp32 mode runs each job to its end in
+    // turn; the 16-bit modes collect the jobs for the launches they share.
+    const bool half = ns_of(precision) != 0;
     impl::DgradJob dj[PLNERF_MAX_BWD_JOBS];
     impl::WgradJob wj[PLNERF_MAX_BWD_JOBS];
     for (int j = 0; j < n_jobs; ++j) {
+        const bwdplan::Workspace lo = bwdplan::workspace((size_t)n_rows[j], half);
         unsigned char* ws = (unsigned char*)workspace[j];
-        unsigned* gmax = (unsigned*)(ws + impl::h16_dz_bytes(n_rows[j]));
+        unsigned* gmax = half ? (unsigned*)(ws + lo.gmax) : nullptr;      // (fp32 planes carry no launch scale)
         const unsigned* cand = nullptr;
         int n_cand = 0;
-        float* partials = (float*)(ws + impl::h16_dz_bytes(n_rows[j]) + lay::WSH_SCALARS_BYTES);
         const float* g = g_raw[j];
         int rc = PLNERF_OK;
-        if (act) {      // one pass: the activation's derivative and the launch scale's maximum
-            float* g_eff = (float*)((unsigned char*)partials + part_bytes);
+        if (act) {      // one pass, first: the activation's derivative (every kernel below reads the effective gradient) and the launch scale's maximum
+            float* g_eff = (float*)(ws + lo.g_eff);
             rc = impl::absmax_act(g, raw_out[j], density_beta, n_rows[j], g_eff, gmax, st);
             g = g_eff;
-        } else if (g_absmax && g_absmax[j] && n_absmax && n_absmax[j] > 0) {
+        } else if (half && g_absmax && g_absmax[j] && n_absmax && n_absmax[j] > 0) {
             // the caller's producer kernel left the candidates (plnerf_quad_bwd's absmax_out): no pass, no memset -- the
             // gradient chain's workgroups take their maximum and leave it in the workspace's word for the kernels behind
             cand = g_absmax[j];
             n_cand = n_absmax[j];
-        } else {
+        } else if (half) {
             rc = impl::absmax(g, (size_t)n_rows[j] * 4, gmax, st);
         }
         if (rc) return rc;
-        dj[j] = impl::DgradJob{packed[j], ns_of(precision), g, n_rows[j], saved[j], ws, gmax, cand, n_cand};
-        wj[j] = impl::WgradJob{g, n_rows[j], saved[j], ws, gmax, partials, grads + j * PLNERF_N_PARAM_TENSORS, input_ch,
-                               input_ch_views, saved_layout[j], status_word(const_cast<void*>(packed[j]), precision),
-                               status_out ? status_out[j] : nullptr, compose_block(packed[j], precision),
-                               (float*)((unsigned char*)partials + part_only)};
+        wj[j] = impl::WgradJob{g, n_rows[j], saved[j], ws + lo.dz, gmax, (float*)(ws + lo.partials), (float*)(ws + lo.head_part),
+                               grads + j * PLNERF_N_PARAM_TENSORS, input_ch, input_ch_views, saved_layout[j],
+                               status_word(const_cast<void*>(packed[j]), precision), status_out ? status_out[j] : nullptr,
+                               half ? compose_block(packed[j], precision) : nullptr, half ? (float*)(ws + lo.gred) : nullptr};
+        if (half) {
+            dj[j] = impl::DgradJob{packed[j], ns_of(precision), g, n_rows[j], saved[j], ws + lo.dz, gmax, cand, n_cand};
+        } else {
+            rc = impl::f32_dgrad(packed[j], g, n_rows[j], (const float*)saved[j], (float*)(ws + lo.dz), st);
+            if (!rc) rc = impl::wgrad_f32(wj[j], st);
+            if (rc) return rc;
+        }
     }
+    if (!half) return PLNERF_OK;
     const int rc = impl::h16_dgrad(n_jobs, dj, st);
     if (rc) return rc;
     return impl::wgrad_h16_multi(n_jobs, wj, st);
@@ -222,7 +207,8 @@ extern "C" int plnerf_mlp_input_grad(const float* const* params, int precision, 
         if (!params[i]) return PLNERF_EINVAL;
     if (precision == PLNERF_PREC_FP32)
         return impl::input_grad(params, n_rows, workspace, nullptr, false, input_ch, input_ch_views, g_embedded, (hipStream_t)stream);
-    const unsigned char* ws = (const unsigned char*)workspace;      // [dz half planes][max |g_raw|] ... as plnerf_mlp_bwd laid them out
-    return impl::input_grad(params, n_rows, ws, (const unsigned*)(ws + impl::h16_dz_bytes(n_rows)), true, input_ch,
-                            input_ch_views, g_embedded, (hipStream_t)stream);
+    const unsigned char* ws = (const unsigned char*)workspace;      // the dz planes and the launch scale's word, where plnerf_mlp_bwd left them
+    const bwdplan::Workspace lo = bwdplan::workspace((size_t)n_rows, true);
+    return impl::input_grad(params, n_rows, ws + lo.dz, (const unsigned*)(ws + lo.gmax), true, input_ch, input_ch_views, g_embedded,
+                            (hipStream_t)stream);
 }

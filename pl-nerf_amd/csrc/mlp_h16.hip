@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mlp_bwd_plan.h"
 #include "mlp_internal.h"
 #include "mlp_layout.h"
 #include "mlp_pack_src.h"

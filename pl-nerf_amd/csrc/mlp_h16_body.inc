@@ -579,8 +579,8 @@ inline int bwd_launch(const BwdArgs* jobs, int n, hipStream_t st) {
         BwdArgs2 p{};
         p.n[0] = jobs[j];
         p.n[1] = jobs[j + 1 < n ? j + 1 : j];
-        p.tiles0 = (jobs[j].n_rows + BWD_TM - 1) / BWD_TM;
-        const int tiles = p.tiles0 + (j + 1 < n ? (jobs[j + 1].n_rows + BWD_TM - 1) / BWD_TM : 0);
+        p.tiles0 = plnerf::bwdplan::dgrad_tiles(jobs[j].n_rows);
+        const int tiles = p.tiles0 + (j + 1 < n ? plnerf::bwdplan::dgrad_tiles(jobs[j + 1].n_rows) : 0);
         hipLaunchKernelGGL(mlp_bwd_h16_kernel, dim3(tiles), dim3(NTHREADS), lds, st, p);
         PLNERF_CHECK_LAUNCH();
     }

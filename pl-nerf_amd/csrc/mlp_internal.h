@@ -21,31 +21,29 @@ int f32_pack(const float* const* params, int xyz_ch, int dir_ch, void* packed, h
 int f32_fwd(const void* packed, const float* pts, const float* viewdirs, const float* embedded, int xyz_ch,
             int dir_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out, void* saved, hipStream_t st);
 int f32_dgrad(const void* packed, const float* g_raw, int n_rows, const float* saved, float* dz, hipStream_t st);
-// Weight gradients.  h16 = false: fp32 planes on the fp32 MFMA (fp32 mode); h16 = true: half planes on
-// v_mfma_f32_32x32x16_f16, partial sums divided by the dz scale derived from *gmax (16-bit modes).
-// status / status_out: the network's range status word (nullptr in fp32 mode) and where the reduction leaves
-// (float)(word != 0) for the caller's gradient exchange (nullptr = nowhere)
-int wgrad(const float* g_raw, int n_rows, const void* saved, const void* dz, const unsigned* gmax, float* partials,
-          float* const* grads, int xyz_ch, int dir_ch, bool h16, int saved_layout, const unsigned* status,
-          float* status_out, hipStream_t st);
-// The weight-gradient stage of the 16-bit modes for up to MAX_BWD_JOBS networks at once (plnerf_mlp_bwd_multi): the
-// main / thin / head / reduce launches each cover every job -- the one round of 256 (254) workgroups is dealt out over
-// the jobs in proportion to their rows -- instead of running once per network.  One job = what wgrad() takes.
+// One network's weight-gradient stage.  dz, gmax, partials, head_part and gred are the sections of the network's
+// backward workspace (bwdplan::workspace, mlp_bwd_plan.h; mlp_api.hip carves them).
 constexpr int MAX_BWD_JOBS = 2;
 struct WgradJob {
     const float* g_raw;
     int n_rows;
     const void* saved;
-    const void* dz;
-    const unsigned* gmax;
+    const void* dz;           // fp32 planes (fp32 mode) or half planes (16-bit modes)
+    const unsigned* gmax;     // 16-bit modes: the partial sums are divided by the dz scale derived from *gmax; fp32 mode: nullptr
     float* partials;
+    float* head_part;
     float* const* grads;
     int xyz_ch, dir_ch, saved_layout;
-    const unsigned* status;
-    float* status_out;
-    const float* cb;          // the compose block of the job's packed weights (mlp_layout.h: CB_*): the factors W_vf, W_f, b_f
-    float* gred;              // lay::GRED_FLOATS floats of workspace: the reduced G and s on their way to the factors' gradients
+    const unsigned* status;   // the network's range status word (nullptr in fp32 mode) and where the reduction leaves
+    float* status_out;        //   (float)(word != 0) for the caller's gradient exchange (nullptr = nowhere)
+    const float* cb;          // 16-bit modes: the compose block of the job's packed weights (mlp_layout.h: CB_*): the factors W_vf, W_f, b_f
+    float* gred;              // 16-bit modes: the reduced G and s on their way to the factors' gradients
 };
+// fp32 mode: fp32 planes on the fp32 MFMA, one network per launch sequence
+int wgrad_f32(const WgradJob& job, hipStream_t st);
+// 16-bit modes: half planes on v_mfma_f32_32x32x16_f16, up to MAX_BWD_JOBS networks at once (plnerf_mlp_bwd_multi): the
+// main / thin / head / reduce launches each cover every job -- the one round of 256 (254) workgroups is dealt out over
+// the jobs in proportion to their rows (bwdplan::deal) -- instead of running once per network.
 int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st);
 // one network's share of the dgrad grid (mlp_bwd_h16_kernel, two networks per grid)
 struct DgradJob {
@@ -79,13 +77,6 @@ int input_grad(const float* const* params, int n_rows, const void* dz, const uns
 int absmax_act(const float* g_raw, const float* raw_out, float beta, int n_rows, float* g_eff, unsigned* out, hipStream_t st);
 // max |x| over n floats as fp32 bits (non-negative floats order like unsigned integers) -> *out
 int absmax(const float* x, size_t n, unsigned* out, hipStream_t st);
-// bytes of the half dz planes of n_rows rows, rounded up to 16
-#ifndef PLNERF_BWD_TM
-#define PLNERF_BWD_TM 192
-#endif
-inline size_t h16_dz_bytes(int n_rows) {      // (lay::dz_rows)
-    return (size_t)4352 * (((size_t)n_rows + PLNERF_BWD_TM - 1) / PLNERF_BWD_TM * PLNERF_BWD_TM);
-}
 
 // 16-bit-operand MFMA modes, both element types (mlp_h16.hip).  ns = 1: plain operands; ns = 2: 3-term split (hi/lo
 // planes).  f16 = 0: bf16 elements; f16 = 1: IEEE half elements (the dgrad chain runs on half operands in every mode).

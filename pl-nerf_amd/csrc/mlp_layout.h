@@ -1,5 +1,7 @@
 // Static geometry of the PL-NeRF MLP (run_nerf_helpers.py:76-128 at the reference's default
-// flags) and of the buffers the fp32 MFMA kernels exchange.  Host and device code share this.
+// flags) and of the buffers the fp32 MFMA kernels exchange.  Host and device code share this, and so does a plain
+// host compiler (mlp_bwd_plan.h and its CPU test): no HIP include, and the functions are bare `constexpr`, which
+// hip-clang compiles for both sides.
 //
 // Layers as GEMMs (y = x W^T + b; weight tensors are [out][in]):
 //   L0  63->256 | L1..L4 256->256 | L5 (63+256)->256, encoding channels first | L6,L7 256->256
@@ -155,22 +157,22 @@ constexpr int DZ_PER_ROW = DZ_V_OFF + HV;    // 2432
 // bands.  Direction (27 + 5 pad), t in 0..15: t < 12: band 2 g + t / 6; then x, y, z, channel 27 | channels 28..31.  Both
 // are bijections onto 0..63 / 0..31.  Its saved encoding planes are TILED planes whose column 16 s + 8 (e >> 2) + 4 g +
 // (e & 3) holds that channel (sv_enc_channel below): what the weight-gradient reduction un-permutes.
-__host__ __device__ constexpr int rr_pe_channel(int g, int t) {
+constexpr int rr_pe_channel(int g, int t) {
     return t < 30 ? 3 + 6 * (5 * g + t / 6) + t % 6 : (t == 30 ? (g ? 2 : 0) : (g ? PE_K - 1 : 1));
 }
-__host__ __device__ constexpr int rr_dpe_channel(int g, int t) {
+constexpr int rr_dpe_channel(int g, int t) {
     return t < 12 ? 3 + 6 * (2 * g + t / 6) + t % 6 : (g ? 28 + (t - 12) : (t < 15 ? t - 12 : 27));
 }
 // channel held by column c of a tiled encoding plane (xyz: 64 columns, direction: 32)
-__host__ __device__ constexpr int sv_enc_channel(int c, bool dir) {
+constexpr int sv_enc_channel(int c, bool dir) {
     const int s = c >> 4, g = (c >> 2) & 1, e = ((c >> 3) & 1) * 4 + (c & 3);
     return dir ? rr_dpe_channel(g, 8 * s + e) : rr_pe_channel(g, 8 * s + e);
 }
 constexpr int SV_ROW_PAD = 256;     // = the register-resident forward's largest workgroup tile: its plane stores are unconditional
 constexpr int SV_LAYOUT_ROWS = 0, SV_LAYOUT_TILED = 1;
-__host__ __device__ constexpr size_t sv_rows(size_t n_rows) { return (n_rows + SV_ROW_PAD - 1) / SV_ROW_PAD * SV_ROW_PAD; }
+constexpr size_t sv_rows(size_t n_rows) { return (n_rows + SV_ROW_PAD - 1) / SV_ROW_PAD * SV_ROW_PAD; }
 // position (in halves) of element (row, col) of a `width`-wide plane in the tiled layout
-__host__ __device__ constexpr size_t sv_tiled_index(size_t row, int col, int width) {
+constexpr size_t sv_tiled_index(size_t row, int col, int width) {
     return (row >> 5) * (size_t)(32 * width) +
            ((size_t)((((col >> 5) * 2 + ((col >> 4) & 1)) * 2 + ((col >> 2) & 1)) * 32) + (row & 31)) * 8 +
            (size_t)(((col >> 3) & 1) * 4 + (col & 3));
@@ -182,7 +184,7 @@ __host__ __device__ constexpr size_t sv_tiled_index(size_t row, int col, int wid
 #define PLNERF_BWD_TM 192     // rows per workgroup tile of the half dgrad kernel (mlp_h16_body.inc)
 #endif
 constexpr int DZ_ROW_PAD = PLNERF_BWD_TM;
-__host__ __device__ constexpr size_t dz_rows(size_t n_rows) { return (n_rows + DZ_ROW_PAD - 1) / DZ_ROW_PAD * DZ_ROW_PAD; }
+constexpr size_t dz_rows(size_t n_rows) { return (n_rows + DZ_ROW_PAD - 1) / DZ_ROW_PAD * DZ_ROW_PAD; }
 // planes of the half state (the composed network has no feature plane and no dz_feature plane): h0..h7, then hv [128], pe [64],
 // dpe [32]; dz0..dz7, then dz_view [128]
 constexpr int SVC_HV_OFF = 8 * W;
@@ -192,7 +194,7 @@ constexpr int SVC_FLOATS = SVC_DPE_OFF + DPE_K;                    // 2272 halve
 constexpr int DZC_V_OFF = 8 * W;
 constexpr int DZC_PER_ROW = DZC_V_OFF + HV;                        // 2176 halves per row
 constexpr int SVH_BYTES_PER_ROW = SVC_FLOATS * 2 + SV_MASK_BYTES;  // 4816
-constexpr int DZH_BYTES_PER_ROW = DZC_PER_ROW * 2;                 // 4352
+constexpr int DZH_BYTES_PER_ROW = DZC_PER_ROW * 2;                 // 4,352
 constexpr int WSH_SCALARS_BYTES = 16;                              // max |g_raw| (fp32 bits) + pad
 #ifndef PLNERF_DZH_TARGET_EXP
 #define PLNERF_DZH_TARGET_EXP 4
@@ -210,7 +212,7 @@ constexpr int PART_VDIR = PART_PE5 + W * PE_K;                 // view layer dir
 constexpr int PART_BIAS = PART_VDIR + HV * DPE_K;              // b0..b7, bf: 9 x 256, bv: 128
 constexpr int PART_SIGMA = PART_BIAS + 9 * W + HV;             // alpha_linear.weight [256] (tiled half planes: the view job's idle waves sum it, mlp_wgrad.hip)
 constexpr int PART_PER_SPLIT = PART_SIGMA + W;
-constexpr int MAX_SPLITS = 128;
+constexpr int MAX_SPLITS = 128;             // (every round of mlp_bwd_plan.h is asserted to fit)
 constexpr int HEAD_PART = 648;               // per-workgroup partial of the sigma/rgb heads
 #ifndef PLNERF_MAX_HEAD_WGS
 #define PLNERF_MAX_HEAD_WGS 512

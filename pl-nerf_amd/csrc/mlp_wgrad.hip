@@ -14,7 +14,12 @@
 // Reference: what autograd derives for run_nerf_helpers.py:105-128 at loss.backward() (run_plnerf.py:1300):
 // dW_l = dz_l^T a_{l-1}, db_l = column sums of dz_l.  (Round 4: moved out of mlp_f32.hip, where the 16-bit modes' dominant
 // backward kernel lived in a file named for another mode.)
+//
+// The host side at the end of the file only turns a plan into kernel arguments and grids: how many row ranges a network
+// launches and how long they are, how a round is dealt over two networks, the head launch and where the workspace's
+// sections lie are decided in mlp_bwd_plan.h (plain C++, swept by tests/test_mlp_bwd_plan.py).
 #include "common.h"
+#include "mlp_bwd_plan.h"
 #include "mlp_frag.h"
 #include "mlp_internal.h"
 #include "mlp_layout.h"
@@ -22,18 +27,6 @@
 
 using namespace plnerf;
 using namespace plnerf::lay;
-
-// row ranges of the 256-wide weight-gradient jobs.  Half planes: 8 tiles (L1..L7 and the composed view layer, mlp_layout.h;
-// 9 tiles x 28 = 252 until round 5, when feature_linear had a job of its own) x 32 = 256 workgroups, ONE round on the
-// 256 CUs (each keeps its 256 x 256 partial in registers for twice as many rows as with 56, and the partial sums
-// written and re-read by the reduction halve: 134 -> 67 MB per network; step -1.5 %).  The fp32 kernel (17 tiles of
-// 256 threads, several workgroups per CU) wants the 56 it was tuned with (28: +8 % step).
-#ifndef PLNERF_WG_SPLITS
-#define PLNERF_WG_SPLITS 32
-#endif
-#ifndef PLNERF_WG_SPLITS_F32
-#define PLNERF_WG_SPLITS_F32 56
-#endif
 
 namespace {
 
@@ -744,7 +737,6 @@ __global__ __launch_bounds__(256) void input_grad_kernel(InGradArgs a) {
     }
 }
 
-constexpr int WG_SPLITS = PLNERF_WG_SPLITS;
 constexpr int HEAD_OUT = 644;   // dW_alpha 256, dW_rgb 384, b_alpha 1, b_rgb 3
 struct ReduceArgs {
     const float* part;
@@ -907,20 +899,6 @@ __global__ __launch_bounds__(256) void absmax_act_kernel(const float4* __restric
     }
 }
 
-inline int splits_for(int n_rows, bool h16) {
-    const int cap = h16 ? WG_SPLITS : PLNERF_WG_SPLITS_F32;
-    int s = (n_rows + 1023) / 1024;
-    if (s < 1) s = 1;
-    if (s > cap) s = cap;
-    return s;
-}
-inline int head_wgs_for(int n_rows) {
-    int s = (n_rows + 255) / 256;
-    if (s < 1) s = 1;
-    if (s > MAX_HEAD_WGS) s = MAX_HEAD_WGS;
-    return s;
-}
-
 }  // namespace
 
 namespace plnerf {
@@ -951,38 +929,23 @@ int absmax_act(const float* g_raw, const float* raw_out, float beta, int n_rows,
 }
 
 namespace {
-// Everything the stage's launches need for ONE network, with the number of row ranges it may use in the main / thin
-// launches (`cap_main`, `cap_thin`: the whole round for a single network, its share of it when two networks share a grid).
+// Everything the stage's launches need for ONE network: the kernel arguments of a job whose row ranges in the main / thin
+// launches and head launch mlp_bwd_plan.h has decided.
 struct WgradPlan {
     WgradArgs main_args, thin_args;
     int nt;                           // tiles (jobs) of the main launch
-    int splits, splits_thin, n_head, rows_per_head_wg;
-    float* head_part;
+    int splits, splits_thin;
+    bwdplan::Head head;
     ReduceArgs red;
 };
 
-int plan_job(const plnerf::impl::WgradJob& jb, bool h16, int cap_main, int cap_thin, WgradPlan& P) {
+int plan_job(const plnerf::impl::WgradJob& jb, bool h16, bwdplan::Ranges main, bwdplan::Ranges thin, WgradPlan& P) {
     const int n_rows = jb.n_rows;
     const size_t N = (size_t)n_rows;
     const size_t NS_ = h16 ? sv_rows(N) : N;       // row stride of the saved half state (padded, mlp_layout.h)
     const int tiled = h16 && jb.saved_layout == SV_LAYOUT_TILED;
     const size_t es = h16 ? sizeof(_Float16) : sizeof(float);        // plane element size
     float* part = jb.partials;
-    P.head_part = part + (size_t)MAX_SPLITS * PART_PER_SPLIT;
-    int splits = (n_rows + 1023) / 1024;
-    splits = splits < 1 ? 1 : (splits > cap_main ? cap_main : splits);
-    int rps = (n_rows + splits - 1) / splits;
-    rps = h16 ? (rps + 63) & ~63 : (rps + 15) & ~15;      // half kernels: whole 64-row stages (two tiles of the tiled layout)
-    // Rounding the range length up can leave the LAST ranges without a row (131,072 rows over 85 ranges of 1,600: ranges
-    // 82..84 start past the end).  A workgroup without rows writes no partial, and the reduction would add whatever the
-    // workspace held there (round 4: found by comparing two schedules of the same step bit for bit) -- so only ranges
-    // that hold a row are launched and summed.
-    splits = (n_rows + rps - 1) / rps;
-    int splits_thin = splits;
-    if (h16) { splits_thin = (n_rows + 1023) / 1024; splits_thin = splits_thin < 1 ? 1 : (splits_thin > cap_thin ? cap_thin : splits_thin); }
-    int rps_thin = (n_rows + splits_thin - 1) / splits_thin;
-    rps_thin = h16 ? (rps_thin + 63) & ~63 : (rps_thin + 15) & ~15;      // (half: whole tiles of the tiled dz planes)
-    splits_thin = (n_rows + rps_thin - 1) / rps_thin;
     const unsigned char* sv = (const unsigned char*)jb.saved;
     const unsigned char* dz = (const unsigned char*)jb.dz;
     auto splane = [&](int p) { return (const void*)(sv + (size_t)p * W * NS_ * es); };
@@ -1021,7 +984,7 @@ int plan_job(const plnerf::impl::WgradJob& jb, bool h16, int cap_main, int cap_t
         jv.part_off = PART_VMAIN; jv.bias_off = PART_BIAS + 9 * W; jv.b_tiled = tiled;
         if (tiled) { jv.B2 = dpe_plane; jv.part2_off = PART_VDIR; jv.g_raw = jb.g_raw; jv.gmax = jb.gmax; }      // (the direction columns and the sigma head on the job's idle waves)
         a.tile_job[nt] = 8; a.tile_o0[nt++] = 0;
-        a.n_rows = n_rows; a.rows_per_split = rps; a.part = part;
+        a.n_rows = n_rows; a.rows_per_split = main.rows_per_split; a.part = part;
         P.main_args = a; P.nt = nt;
     }
     {
@@ -1033,18 +996,17 @@ int plan_job(const plnerf::impl::WgradJob& jb, bool h16, int cap_main, int cap_t
         a.jobs[2] = WJob{dzv_plane, dpe_plane, HV, DPE_K, HV, DPE_K, PART_VDIR, -1, tiled};
         for (int t = 0; t < 3; ++t) { a.tile_job[t] = t; a.tile_o0[t] = 0; }
         if (tiled) a.tile_job[2] = -1;      // (dz_view^T dpe: the view job of the main launch)
-        // half: three (tiled: two) tiles only, so more row ranges than the main launch to cover the 256 CUs (3 x 85 = 255, 2 x 127).
+        // half: three (tiled: two) tiles only, so more row ranges than the main launch (bwdplan::thin_round).
         // (Equal ROW counts per workgroup, not equal bytes: a stage costs its latency whatever its width, so
         // giving the 128 x 32 job half as many, twice as long ranges measured 0.27 ms slower per step.)
-        a.n_rows = n_rows; a.rows_per_split = h16 ? rps_thin : rps; a.part = part;
+        a.n_rows = n_rows; a.rows_per_split = thin.rows_per_split; a.part = part;
         P.thin_args = a;
     }
-    P.splits = splits; P.splits_thin = splits_thin;
-    P.n_head = head_wgs_for(n_rows);
-    P.rows_per_head_wg = h16 ? ((((n_rows + P.n_head - 1) / P.n_head) + 31) & ~31) : (n_rows + P.n_head - 1) / P.n_head;
+    P.splits = main.splits; P.splits_thin = thin.splits;
+    P.head = bwdplan::head_launch(n_rows, h16);
     {
         ReduceArgs a{};
-        a.part = part; a.head_part = P.head_part; a.splits = splits; a.splits_thin = splits_thin; a.n_head = P.n_head;
+        a.part = part; a.head_part = jb.head_part; a.splits = main.splits; a.splits_thin = thin.splits; a.n_head = P.head.n_head;
         a.gmax = h16 ? jb.gmax : nullptr;
         a.status = jb.status; a.status_out = jb.status_out;
         a.enc_tiled = tiled;
@@ -1071,14 +1033,12 @@ int launch_reduce(const WgradPlan* P, int n, hipStream_t st) {
 }
 }  // namespace
 
-// fp32 mode (and the single-network entry of the 16-bit modes)
-int wgrad(const float* g_raw, int n_rows, const void* saved, const void* dzv, const unsigned* gmax, float* part,
-          float* const* grads, int xyz_ch, int dir_ch, bool h16, int saved_layout, const unsigned* status,
-          float* status_out, hipStream_t st) {
-    const WgradJob jb{g_raw, n_rows, saved, dzv, gmax, part, grads, xyz_ch, dir_ch, saved_layout, status, status_out};
-    if (h16) return wgrad_h16_multi(1, &jb, st);
+// fp32 mode: the main and the thin launches walk the same row ranges
+int wgrad_f32(const WgradJob& jb, hipStream_t st) {
+    const int n_rows = jb.n_rows;
+    const bwdplan::Ranges ranges = bwdplan::row_ranges(n_rows, false, bwdplan::F32_SPLITS);
     WgradPlan P;
-    const int rc = plan_job(jb, false, PLNERF_WG_SPLITS_F32, PLNERF_WG_SPLITS_F32, P);
+    const int rc = plan_job(jb, false, ranges, ranges, P);
     if (rc) return rc;
     hipLaunchKernelGGL((wgrad_f32_kernel<2, 2, 2, 4, 4>), dim3(P.nt, P.splits), dim3(256), 0, st, P.main_args);
     PLNERF_CHECK_LAUNCH();
@@ -1087,39 +1047,30 @@ int wgrad(const float* g_raw, int n_rows, const void* saved, const void* dzv, co
     WgradArgs v{};
     v.jobs[0] = P.thin_args.jobs[2];
     v.tile_job[0] = 0; v.tile_o0[0] = 0;
-    v.n_rows = n_rows; v.rows_per_split = P.thin_args.rows_per_split; v.part = part;
+    v.n_rows = n_rows; v.rows_per_split = P.thin_args.rows_per_split; v.part = jb.partials;
     hipLaunchKernelGGL((wgrad_f32_kernel<4, 1, 1, 1, 8>), dim3(1, P.splits), dim3(256), 0, st, v);
     PLNERF_CHECK_LAUNCH();
     HeadArgs2<float> h{};
-    h.n[0] = h.n[1] = HeadArgs<float>{g_raw, (const float*)P.main_args.jobs[7].B, (const float*)((const unsigned char*)saved + (size_t)SV_HV_OFF * (size_t)n_rows * sizeof(float)),
-                                      n_rows, P.rows_per_head_wg, P.head_part, 0, 0};
-    h.wgs0 = P.n_head;
-    hipLaunchKernelGGL(wgrad_head_kernel<float>, dim3(P.n_head), dim3(256), 0, st, h);
+    h.n[0] = h.n[1] = HeadArgs<float>{jb.g_raw, (const float*)P.main_args.jobs[7].B, (const float*)((const unsigned char*)jb.saved + (size_t)SV_HV_OFF * (size_t)n_rows * sizeof(float)),
+                                      n_rows, P.head.rows_per_head_wg, jb.head_part, 0, 0};
+    h.wgs0 = P.head.n_head;
+    hipLaunchKernelGGL(wgrad_head_kernel<float>, dim3(P.head.n_head), dim3(256), 0, st, h);
     PLNERF_CHECK_LAUNCH();
     return launch_reduce(&P, 1, st);
 }
 
 int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st) {
     if (n < 1 || n > MAX_BWD_JOBS) return PLNERF_EINVAL;
-    // the one round of workgroups, dealt out in proportion to the networks' rows (a single network: all of it, as before)
+    // the one round of workgroups of each launch, dealt out in proportion to the networks' rows (a single network: all of it)
     bool all_tiled = true;
     for (int j = 0; j < n; ++j) all_tiled = all_tiled && jobs[j].saved_layout == SV_LAYOUT_TILED;
-    const int thin_tiles = all_tiled ? 2 : 3;               // (tiled: the direction columns ride on the main launch's view job)
-    const int thin_round = all_tiled ? 127 : 85;            // row ranges of a thin job: 2 x 127 = 254 / 3 x 85 = 255 workgroups
-    int cap_main[MAX_BWD_JOBS] = {WG_SPLITS, 0}, cap_thin[MAX_BWD_JOBS] = {thin_round, 0};
-    if (n == 2) {
-        const double f = (double)jobs[0].n_rows / ((double)jobs[0].n_rows + (double)jobs[1].n_rows);
-        auto deal = [&](int total, int* cap) {
-            int s0 = (int)(total * f + 0.5);
-            s0 = s0 < 1 ? 1 : (s0 > total - 1 ? total - 1 : s0);
-            cap[0] = s0; cap[1] = total - s0;
-        };
-        deal(WG_SPLITS, cap_main);
-        deal(thin_round, cap_thin);
-    }
+    const int n_rows1 = n == 2 ? jobs[1].n_rows : 0;
+    const bwdplan::Deal cap_main = bwdplan::deal(bwdplan::MAIN_ROUND, jobs[0].n_rows, n_rows1);
+    const bwdplan::Deal cap_thin = bwdplan::deal(bwdplan::thin_round(all_tiled), jobs[0].n_rows, n_rows1);
     WgradPlan P[MAX_BWD_JOBS];
     for (int j = 0; j < n; ++j) {
-        const int rc = plan_job(jobs[j], true, cap_main[j], cap_thin[j], P[j]);
+        const int rc = plan_job(jobs[j], true, bwdplan::row_ranges(jobs[j].n_rows, true, cap_main.cap[j]),
+                                bwdplan::row_ranges(jobs[j].n_rows, true, cap_thin.cap[j]), P[j]);
         if (rc) return rc;
     }
     const size_t lds = (size_t)2 * 2 * TR_STEPS * TR_PLANE * sizeof(_Float16);
@@ -1141,7 +1092,7 @@ int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st) {
         a.splits0 = P[0].splits_thin;
         const int splits = P[0].splits_thin + (n == 2 ? P[1].splits_thin : 0);
         (void)hipFuncSetAttribute((const void*)wgrad_thin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(wgrad_thin_kernel, dim3(thin_tiles, splits), dim3(512), lds, st, a);
+        hipLaunchKernelGGL(wgrad_thin_kernel, dim3(bwdplan::thin_tiles(all_tiled), splits), dim3(512), lds, st, a);
         PLNERF_CHECK_LAUNCH();
     }
     {
@@ -1151,11 +1102,11 @@ int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st) {
             const size_t NS_ = sv_rows((size_t)jobs[q].n_rows);
             h.n[j] = HeadArgs<_Float16>{jobs[q].g_raw, (const _Float16*)P[q].main_args.jobs[8].B,      // (h7: the composed view job's B plane)
                                         (const _Float16*)((const unsigned char*)jobs[q].saved + (size_t)SVC_HV_OFF * NS_ * sizeof(_Float16)),
-                                        jobs[q].n_rows, P[q].rows_per_head_wg, P[q].head_part,
+                                        jobs[q].n_rows, P[q].head.rows_per_head_wg, jobs[q].head_part,
                                         jobs[q].saved_layout == SV_LAYOUT_TILED, jobs[q].saved_layout == SV_LAYOUT_TILED};
         }
-        h.wgs0 = P[0].n_head;
-        hipLaunchKernelGGL(wgrad_head_kernel<_Float16>, dim3(P[0].n_head + (n == 2 ? P[1].n_head : 0)), dim3(256), 0, st, h);
+        h.wgs0 = P[0].head.n_head;
+        hipLaunchKernelGGL(wgrad_head_kernel<_Float16>, dim3(P[0].head.n_head + (n == 2 ? P[1].head.n_head : 0)), dim3(256), 0, st, h);
         PLNERF_CHECK_LAUNCH();
     }
     const int rc = launch_reduce(P, n, st);

@@ -777,7 +777,10 @@ def test_merged_backward_equals_two_backwards(P):
             worst = 0.0
             for k, job in enumerate(jobs):
                 # the dz planes (the workspace's first section): the gradient chain is the same arithmetic in either grid
-                n_dz = 4352 * ((job["n_rows"] + 191) // 192 * 192) // 4
+                # (its size through the ABI: what the workspace grows by with the rows, less the 16 bytes per row of its last section,
+                # the effective gradient; tests/test_mlp_bwd_plan.py pins the layout)
+                ws_bytes = L.lib().plnerf_mlp_bwd_workspace_bytes
+                n_dz = (ws_bytes(job["n_rows"], prec) - ws_bytes(0, prec) - 16 * job["n_rows"]) // 4
                 assert torch.equal(single[k][0][:n_dz].view(torch.int32), both[k][0][:n_dz].view(torch.int32)), (sizes, k, "dz planes")
                 for name, a, b in zip(names, single[k][1], both[k][1]):
                     assert torch.isfinite(b).all(), (sizes, k, name)
