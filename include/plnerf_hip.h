@@ -69,7 +69,14 @@ extern "C" {
 /* Backward of modes 1-4: the saved activations and the pre-activation gradients are IEEE-half
  * planes, the latter under one power-of-two scale per launch (max |g_raw| -> [8,16), saturating
  * conversion); dgrad chain and weight gradients are single half MFMAs with fp32 accumulation.
- * Weight-gradient entries agree with fp32 autograd to ~1e-3 of max |g| (cosine > 0.999999). */
+ * Weight-gradient entries agree with fp32 autograd to ~1e-3 of max |g| (cosine > 0.999999).
+ * The scale is 2^s with s = 4 - e for max |g_raw| = m 2^e (0.5 <= m < 1), an exact power of two that every result is divided
+ * by again, so a backward is homogeneous in g_raw bit for bit: g_raw 2^k gives every gradient times 2^k while nothing leaves
+ * fp32's normal range.  Below max |g_raw| = 2^-124 (subnormals included) s stays at 127, the largest finite scale: the scaled
+ * maximum then lies below 8 -- at 2^-126 it is 2, two of the half's bits unused -- and the results, themselves fp32 subnormals
+ * there, are the gradient to within one smallest normal (2^-126).  For max |g_raw| = 0, +inf or NaN s = 0: the planes hold
+ * g_raw's own values through the saturating conversion (+-65,504 at most, a NaN among them saturated too); a call with a
+ * non-finite g_raw has no meaningful gradient and sets no status bit. */
 
 #define PLNERF_MAX_SAMPLES 1022 /* S+2 knots must fit the per-wave LDS row */
 

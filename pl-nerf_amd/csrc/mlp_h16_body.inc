@@ -399,7 +399,7 @@ __global__ __launch_bounds__(NTHREADS, BWD_TM <= 96 ? 4 : 2) void mlp_bwd_h16_ke
 #define DTILES(p) (DPLANE(p) + (size_t)row0 * W)      // the workgroup's two 32-row tiles of plane p (row0 % 64 == 0)
 #define MASKP(p) (reinterpret_cast<const unsigned char*>(a.saved) + (size_t)SVC_FLOATS * 2 * NSV + (size_t)(p) * (W / 8) * NSV)
 #define WBK(g_, KS) wblock<NS>(a.packed, false, bwdc_off(g_), KS, wave, 0, a.fwd_ns)
-    float dz_scale = 1.0f;
+    float dz_scale;
     {
         unsigned gbits;
         if (a.n_cand > 0) {      // (uniform) the producer left per-workgroup maxima instead of one word: no absmax pass, no memset
@@ -417,12 +417,7 @@ __global__ __launch_bounds__(NTHREADS, BWD_TM <= 96 ? 4 : 2) void mlp_bwd_h16_ke
         } else {
             gbits = *a.gmax;
         }
-        const float gm = __uint_as_float(gbits);
-        if (gm > 0.0f && gm < __builtin_inff()) {
-            int e;
-            (void)frexpf(gm, &e);
-            dz_scale = ldexpf(1.0f, (int)DZH_TARGET_EXP - e);
-        }
+        dz_scale = __uint_as_float(dzh_scale_bits(gbits));      // (mlp_layout.h: the one derivation of the launch scale)
     }
     static_assert(TM <= NTHREADS, "one upstream-gradient row per thread");
     float4 g_up = make_float4(0.f, 0.f, 0.f, 0.f);      // (the prologue's first request: see the masks below)

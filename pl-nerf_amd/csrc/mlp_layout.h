@@ -199,8 +199,29 @@ constexpr int WSH_SCALARS_BYTES = 16;                              // max |g_raw
 #ifndef PLNERF_DZH_TARGET_EXP
 #define PLNERF_DZH_TARGET_EXP 4
 #endif
-constexpr float DZH_TARGET_EXP = (float)(PLNERF_DZH_TARGET_EXP);   // scaled max |g_raw| in [2^3, 2^4)
+constexpr int DZH_TARGET_EXP = PLNERF_DZH_TARGET_EXP;   // scaled max |g_raw| in [2^3, 2^4)
+static_assert(DZH_TARGET_EXP >= 1 && DZH_TARGET_EXP <= 15, "the scaled maximum is a finite half, and the shift below stays in fp32's exponent range");
 constexpr float H16_MAX = 65504.0f;
+// The launch scale of the half dz planes, derived in this ONE place from the workspace's max |g_raw| word (fp32 bits; a
+// maximum of absolute values, so the sign bit is clear): the shift s -- the planes hold g 2^s, every reader multiplies its
+// sums by 2^-s.  On the bit pattern, so that a host compiler runs the same text (tests/test_mlp_bwd_plan.py sweeps it):
+//   exponent field E >= T - 1 (T = 4: 2^-124 and up), finite  s = T + 126 - E: the maximum lands in [2^(T-1), 2^T), T = DZH_TARGET_EXP
+//   below that, subnormals included, but not zero              s = 127, the largest finite scale: the scaled maximum stays
+//                                                              below 2^(T-1) (fewer of the half's bits are used, nothing else)
+//   zero, infinity, NaN                                        s = 0: the planes hold g as it is
+constexpr int dzh_shift(unsigned gmax_bits) {
+    const int e = (int)((gmax_bits >> 23) & 0xffu);
+    if ((gmax_bits & 0x7fffffffu) == 0u || e == 255) return 0;
+    const int s = DZH_TARGET_EXP + 126 - e;
+    return s > 127 ? 127 : s;
+}
+// 2^p as fp32 bits, -149 <= p <= 127 (2^-127 = the un-scale of s = 127 is a subnormal: one mantissa bit, still exact)
+constexpr unsigned pow2_bits(int p) { return p >= -126 ? (unsigned)(p + 127) << 23 : 1u << (p + 149); }
+constexpr unsigned dzh_scale_bits(unsigned gmax_bits) { return pow2_bits(dzh_shift(gmax_bits)); }
+constexpr unsigned dzh_unscale_bits(unsigned gmax_bits) { return pow2_bits(-dzh_shift(gmax_bits)); }
+static_assert(dzh_shift(0x3f800000u) == DZH_TARGET_EXP - 1 && dzh_shift(0x7f7fffffu) == DZH_TARGET_EXP - 128 && dzh_shift(1u) == 127 &&
+                  dzh_shift(0u) == 0 && dzh_shift(0x7f800000u) == 0 && dzh_scale_bits(1u) == 0x7f000000u && dzh_unscale_bits(1u) == 0x00400000u,
+              "launch scale");
 
 // split-K partial sums of the weight gradients (per split)
 constexpr int WG_MAIN_JOBS = 8;              // L1..L4, L5 (hidden part), L6, L7, feature

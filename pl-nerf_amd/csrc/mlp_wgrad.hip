@@ -229,13 +229,8 @@ __device__ __forceinline__ void wgrad_half_body(const WgradArgs& a, const WJob& 
     _Float16* lds3 = lds2 + (size_t)2 * 4 * B2_BLOCK;
     float g_scale = 1.0f;
     if constexpr (X2) {
-        const float gm = __uint_as_float(*job.gmax);       // (written by the gradient chain's launch, or the absmax pass, before this one)
-        if (gm > 0.0f && gm < __builtin_inff()) {
-            int e;
-            (void)frexpf(gm, &e);
-            g_scale = ldexpf(1.0f, (int)DZH_TARGET_EXP - e);
-        }
-        g_scale = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(g_scale)));      // (uniform: a scalar register)
+        // (the word: written by the gradient chain's launch, or the absmax pass, before this one; the scale: mlp_layout.h.  Uniform: a scalar register)
+        g_scale = __uint_as_float(__builtin_amdgcn_readfirstlane(dzh_scale_bits(*job.gmax)));
     }
     const _Float16* B2g = (const _Float16*)job.B2;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -663,14 +658,7 @@ __global__ __launch_bounds__(256) void input_grad_kernel(InGradArgs a) {
     }
     __syncthreads();
     float unscale = 1.0f;
-    if (H16 && a.gmax) {
-        const float gm = __uint_as_float(*a.gmax);
-        if (gm > 0.0f && gm < __builtin_inff()) {
-            int e;
-            (void)frexpf(gm, &e);
-            unscale = ldexpf(1.0f, e - (int)DZH_TARGET_EXP);
-        }
-    }
+    if (H16 && a.gmax) unscale = __uint_as_float(dzh_unscale_bits(*a.gmax));      // (mlp_layout.h)
     const int r = tid & 31, cg = tid >> 5;
     const int n_tiles = (a.n_rows + 31) / 32;
     const int out_ch = a.xyz_ch + a.dir_ch;
@@ -742,7 +730,7 @@ struct ReduceArgs {
     const float* part;
     const float* head_part;
     int splits, splits_thin, n_head;   // row ranges of the 256-wide jobs / of the three thin jobs
-    const unsigned* gmax;   // 16-bit modes: the dz planes were scaled by 2^(DZH_TARGET_EXP - exponent(max |g_raw|))
+    const unsigned* gmax;   // 16-bit modes: the dz planes were scaled by 2^dzh_shift(*gmax) (mlp_layout.h)
     const unsigned* status; // the network's range status word (16-bit modes), or nullptr
     float* status_out;      // nullptr, or where this launch leaves (float)(*status != 0): the tail of the caller's flat gradient
     int enc_tiled;          // the encoding planes were tiled (mlp_layout.h): column c of the thin jobs' results = channel sv_enc_channel(c);
@@ -800,14 +788,7 @@ __global__ void wgrad_reduce_kernel(ReduceArgs2 p) {
         }
         for (; sp < ns; ++sp) s += a.part[(size_t)sp * PART_PER_SPLIT + idx];
     }
-    if (a.gmax) {   // undo the power-of-two scale of the half dz planes (exact)
-        const float gm = __uint_as_float(*a.gmax);
-        if (gm > 0.0f && gm < __builtin_inff()) {
-            int e;
-            (void)frexpf(gm, &e);
-            s = ldexpf(s, e - (int)DZH_TARGET_EXP);
-        }
-    }
+    if (a.gmax) s *= __uint_as_float(dzh_unscale_bits(*a.gmax));   // undo the power-of-two scale of the half dz planes (exact; mlp_layout.h)
     if (idx < PART_VMAIN) {
         const int job = idx >> 16, r = idx & 65535, o = r >> 8, i = r & 255;
         // jobs: L1, L2, L3, L4, L5 (hidden part), L6, L7, feature

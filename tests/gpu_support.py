@@ -66,6 +66,27 @@ def make_net(P, sd, precision="fp32"):
     return net.to(dev())
 
 
+def ambiguous_rows(sd, pts, vd, eps):
+    """Samples with some ReLU pre-activation within eps of zero (fp64 evaluation of the oracle net)."""
+    sd64 = {k: v.double() for k, v in sd.items()}
+    R, S = pts.shape[:2]
+    emb = torch.cat([orc.positional_encoding(pts.reshape(-1, 3).double(), 10),
+                     orc.positional_encoding(vd.double()[:, None].expand(R, S, 3).reshape(-1, 3), 4)], -1)
+    enc_xyz, enc_dir = emb[:, :63], emb[:, 63:]
+    h, bad = enc_xyz, torch.zeros(R * S, dtype=torch.bool)
+    for i in range(8):
+        pre = torch.nn.functional.linear(h, sd64[f"pts_linears.{i}.weight"], sd64[f"pts_linears.{i}.bias"])
+        bad |= (pre.abs() < eps).any(-1)
+        h = torch.relu(pre)
+        if i == 4:
+            h = torch.cat([enc_xyz, h], -1)
+    feat = torch.nn.functional.linear(h, sd64["feature_linear.weight"], sd64["feature_linear.bias"])
+    pre = torch.nn.functional.linear(torch.cat([feat, enc_dir], -1), sd64["views_linears.0.weight"],
+                                     sd64["views_linears.0.bias"])
+    bad |= (pre.abs() < eps).any(-1)
+    return bad
+
+
 def quad_case(R, S, seed):
     gen = torch.Generator().manual_seed(seed)
     raw = torch.randn(R, S, 4, generator=gen)

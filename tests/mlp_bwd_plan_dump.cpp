@@ -6,6 +6,8 @@
 //   head N HALF                head workgroups, rows per head workgroup
 //   tiles N                    dgrad workgroup tiles
 //   ws N HALF                  byte offsets dz gmax partials head_part gred g_eff total
+//   shift BITS                 mlp_layout.h's launch scale of the half dz planes for max |g_raw| = the fp32 with these bits
+//                              (decimal): the shift s, then 2^s and 2^-s as fp32 bits
 // With the argument `sweep` it checks the plan's invariants over every row count up to 3,000,000 and prints, per
 // property, how many cases it checked and how many broke it (with the first few of those).
 #include <cstdio>
@@ -105,6 +107,8 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(line, "ws %ld %ld", &a, &b) == 2) {
             const Workspace w = workspace((size_t)a, b != 0);
             std::printf("%zu %zu %zu %zu %zu %zu %zu\n", w.dz, w.gmax, w.partials, w.head_part, w.gred, w.g_eff, w.total);
+        } else if (std::sscanf(line, "shift %ld", &a) == 1) {
+            std::printf("%d %u %u\n", lay::dzh_shift((unsigned)a), lay::dzh_scale_bits((unsigned)a), lay::dzh_unscale_bits((unsigned)a));
         } else {
             std::printf("? %s", line);
             return 1;

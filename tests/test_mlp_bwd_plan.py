@@ -7,7 +7,9 @@
     whole 64- / 16-row stages, two dealt caps are >= 1 each and sum to the round, the head workgroups cover all rows
     within MAX_HEAD_WGS (empty head workgroups are fine: the head kernel writes zeros for them; 131,073 rows has 56);
   * literal tables of row ranges, deals, head launches and dgrad tiles;
-  * the workspace layout: sections in order, back to back, 16-byte aligned, and the total size.
+  * the workspace layout: sections in order, back to back, 16-byte aligned, and the total size;
+  * the launch scale of the half dz planes (mlp_layout.h: dzh_shift, which the four kernel sites call) over fp32's whole
+    exponent range, zero, subnormals, infinity and NaNs.
 
 The tables and sizes were NOT taken from the header: they were written down from the arithmetic of plan_job, wgrad_h16_multi's
 deal, head_wgs_for and bwd_launch as they stood in the commit before the header existed (f19716f; a line-for-line port
@@ -119,6 +121,61 @@ def test_literal_tables(dump):
         (got,) = ask(dump, [f"deal {rnd} {n0} {n1}"])
         assert got == caps, (n0, n1, rnd, got)
         assert ask(dump, [f"ranges {n0} 1 {got[0]}", f"ranges {n1} 1 {got[1]}"]) == [r0, r1], (n0, n1, rnd)
+
+
+def launch_scale_patterns():
+    """fp32 bit patterns of max |g_raw| for the launch-scale sweep: every exponent field at mantissa 0, 1 and all-ones (zero,
+    the smallest and the largest subnormal, 2^-124 = 0x01800000 with both neighbours, the largest finite value, infinity and
+    two NaN patterns are among them), and a third NaN pattern with the quiet bit."""
+    bits = [(e << 23) | m for e in range(256) for m in (0, 1, 0x7fffff)]
+    for named in (0, 1, 0x007fffff, 0x017fffff, 0x01800000, 0x01800001, 0x7f7fffff, 0x7f800000, 0x7f800001, 0x7fffffff):
+        assert named in bits, hex(named)
+    return bits + [0x7fc00000]
+
+
+def test_launch_scale_of_the_half_dz_planes(dump):
+    """mlp_layout.h: dzh_shift, the one derivation of the 16-bit backward's launch scale 2^s (include/plnerf_hip.h, "Backward
+    of modes 1-4"), against the contract written out in exact integer arithmetic (fractions, no float rounding):
+      finite, max |g_raw| >= 2^-124      s = 4 - e, max |g_raw| = m 2^e with 0.5 <= m < 1 (what frexpf / ldexpf gave before the
+                                         derivation was written once), so max |g_raw| 2^s lies in [8, 16);
+      0 < max |g_raw| < 2^-124           s = 127, the largest finite scale (the scaled maximum stays below 8);
+      0, infinity, any NaN               s = 0;
+    and 2^s, 2^-s come back as the fp32 bit patterns of exactly those powers: finite and non-zero for every input."""
+    import math
+    from fractions import Fraction
+    bits = launch_scale_patterns()
+    answers = ask(dump, [f"shift {b}" for b in bits])
+
+    def value(b):      # a non-negative finite fp32 bit pattern, exactly
+        e, m = b >> 23, b & 0x7fffff
+        return Fraction(m, 1 << 23) * Fraction(2) ** -126 if e == 0 else (1 + Fraction(m, 1 << 23)) * Fraction(2) ** (e - 127)
+
+    checked = {"in range": 0, "below": 0, "unscaled": 0}
+    for b, (s, up, down) in zip(bits, answers):
+        e = b >> 23
+        if b == 0 or e == 255:
+            want, kind = 0, "unscaled"
+        else:
+            gm = value(b)
+            if gm >= Fraction(2) ** -124:
+                want, kind = 4 - math.frexp(float(gm))[1], "in range"      # (every fp32 is a double: frexp is exact)
+                assert 8 <= gm * Fraction(2) ** s < 16, (hex(b), s)
+            else:
+                want, kind = 127, "below"
+                assert gm * Fraction(2) ** s < 8, (hex(b), s)
+        checked[kind] += 1
+        assert s == want, (hex(b), s, want)
+        assert -127 <= s <= 127, (hex(b), s)
+        # 2^s is a normal number; 2^-s too, but for s = 127: the subnormal 2^-127, one mantissa bit
+        assert 0 < up < 0x7f800000 and value(up) == Fraction(2) ** s, (hex(b), s, hex(up))
+        assert 0 < down < 0x7f800000 and value(down) == Fraction(2) ** -s, (hex(b), s, hex(down))
+    # 253 exponent fields from 3 up at three mantissas | fields 0..2 less zero | zero, infinity and three NaN patterns
+    assert checked == {"in range": 252 * 3, "below": 3 * 3 - 1, "unscaled": 1 + 3 + 1}, checked
+    # the literal corners: 1.0 -> 3; 2^-124 -> 127 and its neighbour below -> 127 as well; the largest finite -> -124
+    assert dict(zip(bits, (a[0] for a in answers)))[0x3f800000] == 3
+    by_bits = dict(zip(bits, answers))
+    assert by_bits[0x01800000] == (127, 0x7f000000, 0x00400000) and by_bits[0x017fffff][0] == 127 and by_bits[0x02000000][0] == 126
+    assert by_bits[0x7f7fffff] == (-124, 0x01800000, 0x7d800000)
 
 
 ROWS = (0, 1, 191, 192, 193, 961, 1152, 1153, 1000)

@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import torch
 import plnerf_amd as P
 from oracle import plnerf_oracle as orc
-from test_gpu_parity import ambiguous_rows
+from gpu_support import ambiguous_rows
 dev = torch.device("cuda:0")
 prec = sys.argv[1] if len(sys.argv) > 1 else "bf16x3"
 R, S = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (5, 64)
