@@ -2,6 +2,8 @@
 // the precision mode.  Kernels live in mlp_f32.hip (exact fp32 MFMA), mlp_wgrad.hip (the weight-gradient stage of every
 // mode), mlp_h16.hip (the 16-bit-operand MFMA modes, bf16 and IEEE-half elements, plain and 3-term split: ping-pong
 // forward and dgrad chain) and mlp_rr.hip (their register-resident forward).
+#include <cstdlib>
+
 #include "common.h"
 #include "mlp_bwd_plan.h"
 #include "mlp_fwd_route.h"
@@ -23,7 +25,8 @@ inline bool geometry_ok(int input_ch, int input_ch_views) {
     return input_ch >= 1 && input_ch <= lay::PE_K && input_ch_views >= 1 && input_ch_views <= lay::DPE_K;
 }
 // Forward kernel of the 16-bit modes: `fwd_kernel` is an ABI argument (PLNERF_FWD_KERNEL_AUTO / _RR / _PP; the library
-// itself reads no environment); which kernel a call runs on is route::fwd_uses_rr (mlp_fwd_route.h) and nothing else.
+// reads no environment for it); which kernel a call runs on is route::fwd_uses_rr (mlp_fwd_route.h) and nothing else.
+// (The one variable the library does read: PLNERF_BWD_COMPACT, impl::bwd_compact at the end of this file.)
 inline bool kernel_arg_ok(int k) { return k == PLNERF_FWD_KERNEL_AUTO || k == PLNERF_FWD_KERNEL_RR || k == PLNERF_FWD_KERNEL_PP; }
 static_assert(route::FWD_AUTO == PLNERF_FWD_KERNEL_AUTO && route::FWD_RR == PLNERF_FWD_KERNEL_RR && route::FWD_PP == PLNERF_FWD_KERNEL_PP, "");
 inline bool use_rr(int precision, bool training, bool embedded, int forced) {      // (16-bit modes)
@@ -151,6 +154,10 @@ extern "C" int plnerf_mlp_bwd_multi(int n_jobs, const void* const* packed, int p
     const bool half = ns_of(precision) != 0;
     impl::DgradJob dj[PLNERF_MAX_BWD_JOBS];
     impl::WgradJob wj[PLNERF_MAX_BWD_JOBS];
+    impl::LiveJob lj[PLNERF_MAX_BWD_JOBS];      // 16-bit modes: the networks whose backward runs over the live rows only (mlp_bwd_plan.h)
+    int n_live_jobs = 0;
+    bool compact = half;      // (every network of the call, or none: they share the weight-gradient launches)
+    for (int j = 0; j < n_jobs; ++j) compact = compact && impl::bwd_compact(n_rows[j]);
     for (int j = 0; j < n_jobs; ++j) {
         const bwdplan::Workspace lo = bwdplan::workspace((size_t)n_rows[j], half);
         unsigned char* ws = (unsigned char*)workspace[j];
@@ -175,9 +182,12 @@ extern "C" int plnerf_mlp_bwd_multi(int n_jobs, const void* const* packed, int p
         wj[j] = impl::WgradJob{g, n_rows[j], saved[j], ws + lo.dz, gmax, (float*)(ws + lo.partials), (float*)(ws + lo.head_part),
                                grads + j * PLNERF_N_PARAM_TENSORS, input_ch, input_ch_views, saved_layout[j],
                                status_word(const_cast<void*>(packed[j]), precision), status_out ? status_out[j] : nullptr,
-                               half ? compose_block(packed[j], precision) : nullptr, half ? (float*)(ws + lo.gred) : nullptr};
+                               half ? compose_block(packed[j], precision) : nullptr, half ? (float*)(ws + lo.gred) : nullptr,
+                               compact ? 1 : 0};
         if (half) {
-            dj[j] = impl::DgradJob{packed[j], ns_of(precision), g, n_rows[j], saved[j], ws + lo.dz, gmax, cand, n_cand};
+            dj[j] = impl::DgradJob{packed[j], ns_of(precision), g, n_rows[j], saved[j], ws + lo.dz, gmax, cand, n_cand,
+                                   compact ? (const unsigned*)(ws + lo.partials) : nullptr};
+            if (compact) lj[n_live_jobs++] = impl::LiveJob{g, n_rows[j], (float*)(ws + lo.partials)};
         } else {
             rc = impl::f32_dgrad(packed[j], g, n_rows[j], (const float*)saved[j], (float*)(ws + lo.dz), st);
             if (!rc) rc = impl::wgrad_f32(wj[j], st);
@@ -185,7 +195,9 @@ extern "C" int plnerf_mlp_bwd_multi(int n_jobs, const void* const* packed, int p
         }
     }
     if (!half) return PLNERF_OK;
-    const int rc = impl::h16_dgrad(n_jobs, dj, st);
+    int rc = n_live_jobs ? impl::live_list(n_live_jobs, lj, st) : PLNERF_OK;      // (on this stream, ahead of dgrad; the host reads nothing back)
+    if (rc) return rc;
+    rc = impl::h16_dgrad(n_jobs, dj, st);
     if (rc) return rc;
     return impl::wgrad_h16_multi(n_jobs, wj, st);
 }
@@ -206,9 +218,20 @@ extern "C" int plnerf_mlp_input_grad(const float* const* params, int precision, 
     for (int i = 0; i < PLNERF_N_PARAM_TENSORS; ++i)
         if (!params[i]) return PLNERF_EINVAL;
     if (precision == PLNERF_PREC_FP32)
-        return impl::input_grad(params, n_rows, workspace, nullptr, false, input_ch, input_ch_views, g_embedded, (hipStream_t)stream);
+        return impl::input_grad(params, n_rows, workspace, nullptr, false, input_ch, input_ch_views, g_embedded, nullptr, (hipStream_t)stream);
     const unsigned char* ws = (const unsigned char*)workspace;      // the dz planes and the launch scale's word, where plnerf_mlp_bwd left them
     const bwdplan::Workspace lo = bwdplan::workspace((size_t)n_rows, true);
+    // (a backward over the live rows left compact planes and the list: the same decision as plnerf_mlp_bwd_multi's, on the same n_rows
+    // -- of a one-network call, or of a merged one whose every network had room for its list, i.e. any that fits the device)
+    const unsigned* live = impl::bwd_compact(n_rows) ? (const unsigned*)(ws + lo.partials) : nullptr;
     return impl::input_grad(params, n_rows, ws + lo.dz, (const unsigned*)(ws + lo.gmax), true, input_ch, input_ch_views, g_embedded,
-                            (hipStream_t)stream);
+                            live, (hipStream_t)stream);
+}
+
+// PLNERF_BWD_COMPACT=0: the dense backward (A/B measurements, the tests' dense leg).  Read at every call, so a process may
+// switch between two backwards -- not between a backward and the plnerf_mlp_input_grad that reads its workspace.
+bool plnerf::impl::bwd_compact(int n_rows) {
+    if (n_rows < 1 || !bwdplan::live_list_fits((size_t)n_rows)) return false;
+    const char* e = getenv("PLNERF_BWD_COMPACT");
+    return !(e && e[0] == '0' && e[1] == '\0');
 }

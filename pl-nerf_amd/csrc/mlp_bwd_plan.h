@@ -113,5 +113,57 @@ constexpr Head head_launch(int n_rows, bool half) {
 // ---- dgrad grid of the 16-bit modes: workgroup tiles of one network (two networks share a grid) -------------------
 constexpr int dgrad_tiles(int n_rows) { return (n_rows + lay::DZ_ROW_PAD - 1) / lay::DZ_ROW_PAD; }
 
+// ---- live rows (16-bit modes) --------------------------------------------------------------------------------------
+// A row whose upstream gradient is (0, 0, 0, 0) has dz = 0 in every layer and adds nothing to any gradient: the backward
+// runs over the LIVE rows only.  Ahead of dgrad a two-level scan (per-block counts, one workgroup's scan of them, an
+// ordered scatter: mlp_live.hip) leaves the ascending indices of the rows whose four gradient floats are not all == 0.0f
+// (a NaN row is live) and their number n_live in the workspace; dgrad writes dz of live row k at COMPACT row k of the
+// unchanged planes, and every later reader takes its source rows (saved planes, upstream gradient) from the list.  The
+// host never reads n_live: grids stay sized from n_rows, the row ranges below are taken again on the device from n_live.
+//
+// Where the list lives -- no section of its own, the workspace's size and sections are as they were: the partials
+// section holds MAX_SPLITS slots, of which a 16-bit main launch writes only [0, MAIN_ROUND) (a network's share of the
+// round is at most the round), and the thin launch, which may use every slot, writes nothing below PART_PE0 of a slot
+// (its encoding and direction partials and L0's bias partial).  So floats [PART_MAIN, PART_PE0) of the slots
+// [MAIN_ROUND, MAX_SPLITS) are written by no launch and read by none (the reduction reads a main-launch element of at
+// most MAIN_ROUND slots): the list is chunked over their PART_MAIN areas, LIVE_CHUNK entries per slot, and the scan's
+// words (n_live, the per-block counts) sit in the PART_VMAIN area of the first such slot.  Each network has a
+// workspace of its own, so the two networks of a merged call cannot meet.  Where there is no room -- a build whose
+// main round takes every slot, or more rows than the chunks hold -- live_list_fits() says so and the backward is dense.
+constexpr int LIVE_SLOT0 = MAIN_ROUND;                              // first slot no main launch writes
+constexpr int LIVE_SLOTS = lay::MAX_SPLITS - LIVE_SLOT0;
+constexpr int LIVE_CHUNK_LOG2 = 19;
+constexpr size_t LIVE_CHUNK = (size_t)1 << LIVE_CHUNK_LOG2;         // list entries (uint32) per slot: its PART_MAIN area
+constexpr int LIVE_BLOCK_ROWS = 1024;                               // rows per workgroup of the count and scatter launches
+constexpr int LIVE_N = 0;                                           // scan words: [LIVE_N] = n_live, [LIVE_COUNTS + b] = block b's count, then its offset
+constexpr int LIVE_COUNTS = 16;
+constexpr int LIVE_MAX_BLOCKS = lay::PART_PE0 - lay::PART_VMAIN - LIVE_COUNTS;
+static_assert(LIVE_CHUNK <= (size_t)(lay::PART_VMAIN - lay::PART_MAIN) && LIVE_SLOT0 >= MAIN_ROUND && LIVE_SLOT0 + LIVE_SLOTS <= lay::MAX_SPLITS &&
+              lay::PART_MAIN < lay::PART_VMAIN && lay::PART_VMAIN + LIVE_COUNTS + LIVE_MAX_BLOCKS <= lay::PART_PE0,
+              "the live-row list and its scan words stay inside [PART_MAIN, PART_PE0) of slots no main launch writes");
+static_assert(THIN_ROUND_ROWS <= lay::MAX_SPLITS && THIN_ROUND_TILED <= lay::MAX_SPLITS && lay::PART_PE0 < lay::PART_PE5 &&
+              lay::PART_PE5 < lay::PART_VDIR && lay::PART_VDIR < lay::PART_BIAS,
+              "everything a thin launch writes lies at or above PART_PE0 of its slot");
+constexpr int live_blocks(size_t n_rows) { return (int)((n_rows + LIVE_BLOCK_ROWS - 1) / LIVE_BLOCK_ROWS); }
+// the most rows the chunks and the count words hold (0: no slot is free)
+constexpr size_t LIVE_MAX_ROWS = LIVE_SLOTS < 1 ? 0
+                                 : ((size_t)LIVE_SLOTS * LIVE_CHUNK < (size_t)LIVE_MAX_BLOCKS * LIVE_BLOCK_ROWS ? (size_t)LIVE_SLOTS * LIVE_CHUNK
+                                                                                                                 : (size_t)LIVE_MAX_BLOCKS * LIVE_BLOCK_ROWS);
+constexpr bool live_list_fits(size_t n_rows) { return n_rows <= LIVE_MAX_ROWS && LIVE_MAX_ROWS > 0; }
+// word offsets (4-byte units) from the start of the partials section
+constexpr size_t live_entry_word(size_t i) {
+    return (size_t)(LIVE_SLOT0 + (int)(i >> LIVE_CHUNK_LOG2)) * lay::PART_PER_SPLIT + lay::PART_MAIN + (i & (LIVE_CHUNK - 1));
+}
+constexpr size_t live_scan_word(int k) { return (size_t)LIVE_SLOT0 * lay::PART_PER_SPLIT + lay::PART_VMAIN + (size_t)k; }
+// The row ranges and the head launch over the live rows: the same rules as above on n_live, evaluated by every workgroup
+// and by the reduction alike (one text, compiled for both sides).  `launched`: the ranges the host launched for the
+// network, row_ranges(n_rows, true, cap).splits -- NOT the dealt cap: rounding the length up can leave the host fewer
+// ranges than its cap (262,144 rows at a cap of 73: 72 ranges), and fewer rows could then ask for more ranges than the
+// grid has workgroups (73,729 live rows at a cap of 73: 73).  Without a live row there is no range: no workgroup
+// writes a partial and the reduction adds none.  An empty head workgroup writes zeros, as above, and head_launch grows
+// with its rows, so all of the host's n_head partials (sized from n_rows >= n_live) are written.
+constexpr Ranges live_ranges(int n_live, int launched) { return n_live < 1 ? Ranges{0, 64} : row_ranges(n_live, true, launched); }
+constexpr Head live_head(int n_live) { return head_launch(n_live < 0 ? 0 : n_live, true); }
+
 }  // namespace bwdplan
 }  // namespace plnerf

@@ -253,6 +253,8 @@ struct BwdArgs {
     int fwd_ns;             // plane count of the packed forward section (locates the dgrad section)
     const unsigned* cand;   // n_cand > 0: candidates whose maximum IS that word (plnerf_quad_bwd's per-workgroup maxima);
     int n_cand;             //   every workgroup takes the maximum itself, the network's first one stores it for the later kernels
+    const unsigned* live;   // the live-row list's home (mlp_bwd_plan.h: "live rows"), or nullptr: tile t then handles COMPACT rows
+                            //   [TM t, TM t + TM) -- upstream gradient and masks come from the listed rows, dz goes to the compact ones
 };
 // Up to two networks' chains in ONE grid (plnerf_mlp_bwd_multi; round 5): tiles [0, tiles0) belong to n[0], the rest to
 // n[1].  A training step's coarse and fine backward launched separately end on partial rounds (262,144 rows = 1,366
@@ -279,12 +281,9 @@ constexpr int BWD_WPF = PLNERF_BWD_WPF;      // the dgrad kernel's weight prefet
 constexpr int MASK_ROW_WORDS = 9;
 constexpr int MASK_TILE_BYTES = BWD_TM * 4 * MASK_ROW_WORDS;   // one layer's mask rows of a tile in LDS
 constexpr int MASK_WORDS = (BWD_TM * 8 + NTHREADS - 1) / NTHREADS;   // mask words per thread and layer (the last may be partial)
-__device__ __forceinline__ unsigned mask_fetch(const unsigned char* __restrict__ mask_plane, const int row0,
-                                               const int rows_valid, const int tid, const int k = 0) {
-    static_assert(BWD_TM % 32 == 0 && MASK_WORDS >= 1, "whole 32-row tiles");
-    const unsigned* src = reinterpret_cast<const unsigned*>(mask_plane + (size_t)row0 * 32);
-    const int q = tid + NTHREADS * k;      // word q of the tile: row q / 8, word q % 8 of its 32 bytes
-    return (q < BWD_TM * 8 && (q >> 3) < rows_valid) ? src[q] : 0u;
+static_assert(BWD_TM % 32 == 0 && MASK_WORDS >= 1, "whole 32-row tiles");
+__device__ __forceinline__ unsigned mask_word(const unsigned char* __restrict__ mask_plane, const int row, const int w) {
+    return reinterpret_cast<const unsigned*>(mask_plane + (size_t)row * 32)[w];      // word w of the row's 32 mask bytes
 }
 __device__ __forceinline__ void mask_commit(unsigned char* maskb, const unsigned word, const int tid, const int k = 0) {
     const int q = tid + NTHREADS * k;
@@ -384,10 +383,10 @@ __global__ __launch_bounds__(NTHREADS, BWD_TM <= 96 ? 4 : 2) void mlp_bwd_h16_ke
     float* gr = reinterpret_cast<float*>(g + G_PLANE);
     unsigned char* maskb = reinterpret_cast<unsigned char*>(gr + TM * 4);
     unsigned* tbl = reinterpret_cast<unsigned*>(maskb + 8 * MASK_TILE_BYTES);
+    int* rowl = reinterpret_cast<int*>(tbl + 32);      // live rows: the tile's TM list entries
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform
     const int row0 = bid * TM;
-    const int rows_valid = min(TM, a.n_rows - row0);
     const size_t N = (size_t)a.n_rows;
     const float* hd = head(a.packed);
     const int rot = bid >> 3;   // consecutive blocks of one XCD (b, b+8, ...) get consecutive rotations (the network's own tile index: a row's arithmetic does not depend on what else shares the grid)
@@ -420,8 +419,22 @@ __global__ __launch_bounds__(NTHREADS, BWD_TM <= 96 ? 4 : 2) void mlp_bwd_h16_ke
         dz_scale = __uint_as_float(dzh_scale_bits(gbits));      // (mlp_layout.h: the one derivation of the launch scale)
     }
     static_assert(TM <= NTHREADS, "one upstream-gradient row per thread");
+    // Live rows (mlp_bwd_plan.h): the tile's rows are COMPACT rows [row0, row0 + TM) -- row k of the tile reads its upstream
+    // gradient and its masks from source row list[row0 + k] and writes dz at compact row row0 + k, where the weight-gradient
+    // stage looks for it.  A tile past n_live has nothing to do (the grid is sized from n_rows on the host, which never reads
+    // n_live); rows of the last live tile past n_live get dz = 0, as rows past n_rows do without a list.  (After the scale block:
+    // the network's first workgroup has stored the launch scale's word, live rows or none.)
+    const bool listed = a.live != nullptr;      // (uniform)
+    const int n_eff = listed ? (int)a.live[plnerf::bwdplan::live_scan_word(plnerf::bwdplan::LIVE_N)] : a.n_rows;
+    if (row0 >= n_eff) return;
+    const int rows_valid = min(TM, n_eff - row0);
+    if (listed) {      // (entries past n_live: the last live row's -- nothing is fetched from a row that is not live; their dz is zero)
+        if (tid < TM) rowl[tid] = (int)a.live[plnerf::bwdplan::live_entry_word((size_t)min(row0 + tid, n_eff - 1))];
+        __syncthreads();
+    }
+#define SRC_ROW(r) (listed ? rowl[r] : row0 + (r))      // source row of the tile's row r
     float4 g_up = make_float4(0.f, 0.f, 0.f, 0.f);      // (the prologue's first request: see the masks below)
-    if (tid < rows_valid) g_up = reinterpret_cast<const float4*>(a.g_raw)[row0 + tid];
+    if (tid < rows_valid) g_up = reinterpret_cast<const float4*>(a.g_raw)[SRC_ROW(tid)];
     // dz_view's own inputs, requested with the upstream gradient and the masks so that they share that one latency: a thread's items
     // idx = tid + NTHREADS k all have the same feature octet c = tid & 15 (its 24 rgb-head weights: registers) and
     // consecutive bytes of the view layer's mask plane.  (Loaded inside the loop below -- a predicated byte load and 24
@@ -432,11 +445,11 @@ __global__ __launch_bounds__(NTHREADS, BWD_TM <= 96 ? 4 : 2) void mlp_bwd_h16_ke
     const int vc = tid & 15;
     unsigned hvm[VIEW_ITEMS];
     {
-        const unsigned char* hv_mask = MASKP(8) + (size_t)row0 * (HV / 8);
+        const unsigned char* hv_mask = MASKP(8);
 #pragma unroll
         for (int k = 0; k < VIEW_ITEMS; ++k) {
             const int idx = tid + NTHREADS * k;
-            hvm[k] = (idx < TM * (HV / 8) && (idx >> 4) < rows_valid) ? hv_mask[idx] : 0u;
+            hvm[k] = (idx < TM * (HV / 8) && (idx >> 4) < rows_valid) ? hv_mask[(size_t)SRC_ROW(idx >> 4) * (HV / 8) + (idx & 15)] : 0u;
         }
     }
     float wr8[3][8];
@@ -459,7 +472,10 @@ __global__ __launch_bounds__(NTHREADS, BWD_TM <= 96 ? 4 : 2) void mlp_bwd_h16_ke
 #pragma unroll
     for (int p = 0; p < 8; ++p)
 #pragma unroll
-        for (int k = 0; k < MASK_WORDS; ++k) mw[p][k] = mask_fetch(MASKP(p), row0, rows_valid, tid, k);
+        for (int k = 0; k < MASK_WORDS; ++k) {
+            const int q = tid + NTHREADS * k;      // word q of the tile: row q / 8, word q % 8 of its 32 bytes
+            mw[p][k] = (q < TM * 8 && (q >> 3) < rows_valid) ? mask_word(MASKP(p), SRC_ROW(q >> 3), q & 7) : 0u;
+        }
     if (tid < TM) {
         float4 v = g_up;
         v.x *= dz_scale; v.y *= dz_scale; v.z *= dz_scale; v.w *= dz_scale;
@@ -537,6 +553,7 @@ __global__ __launch_bounds__(NTHREADS, BWD_TM <= 96 ? 4 : 2) void mlp_bwd_h16_ke
         TR(6 + 5 * (7 - l));
     }
     TR(42);
+#undef SRC_ROW
 #undef DPLANE
 #undef DTILES
 #undef MASKP
@@ -567,7 +584,7 @@ int fwd_launch(const FwdArgs& a, hipStream_t st) {
 
 #ifdef H16_HAS_BWD
 inline int bwd_launch(const BwdArgs* jobs, int n, hipStream_t st) {
-    const size_t lds = (size_t)BWD_TM * BLDA * 2 + (size_t)BWD_TM * 16 + (size_t)8 * MASK_TILE_BYTES + 128;      // (+ 32 B static)
+    const size_t lds = (size_t)BWD_TM * BLDA * 2 + (size_t)BWD_TM * 16 + (size_t)8 * MASK_TILE_BYTES + 128 + (size_t)BWD_TM * 4;      // (+ 32 B static)
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void*)mlp_bwd_h16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     for (int j = 0; j < n; j += 2) {      // two networks per grid
@@ -620,7 +637,7 @@ inline int h16_dgrad(int n, const plnerf::impl::DgradJob* jobs, hipStream_t st) 
     BwdArgs a[plnerf::impl::MAX_BWD_JOBS];
     for (int j = 0; j < n; ++j)
         a[j] = BwdArgs{jobs[j].packed, jobs[j].g_raw, jobs[j].n_rows, jobs[j].saved, jobs[j].dz, jobs[j].gmax, jobs[j].fwd_ns,
-                       jobs[j].cand, jobs[j].n_cand};
+                       jobs[j].cand, jobs[j].n_cand, jobs[j].live};
     return bwd_launch(a, n, st);
 }
 #endif

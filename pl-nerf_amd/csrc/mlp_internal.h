@@ -38,6 +38,8 @@ struct WgradJob {
     float* status_out;        //   (float)(word != 0) for the caller's gradient exchange (nullptr = nowhere)
     const float* cb;          // 16-bit modes: the compose block of the job's packed weights (mlp_layout.h: CB_*): the factors W_vf, W_f, b_f
     float* gred;              // 16-bit modes: the reduced G and s on their way to the factors' gradients
+    int compact;              // 16-bit modes: the dz planes hold the LIVE rows only, compacted (mlp_bwd_plan.h: "live rows"; the list and
+                              //   n_live are in `partials`): source rows come from the list, row ranges from n_live on the device
 };
 // fp32 mode: fp32 planes on the fp32 MFMA, one network per launch sequence
 int wgrad_f32(const WgradJob& job, hipStream_t st);
@@ -56,7 +58,20 @@ struct DgradJob {
     unsigned* gmax;           // the workspace's max |g_raw| word: holds it already, or (n_cand > 0) is written by the launch
     const unsigned* cand;     // n_cand candidates whose maximum is that word, or nullptr / 0
     int n_cand;
+    const unsigned* live;     // the workspace's partials section as words when it holds the live-row list (live_list below): the
+                              //   chain runs over the listed rows and writes dz at their compact positions; nullptr: every row
 };
+// The live-row list of a network's upstream gradient, into its workspace's partials section (mlp_live.hip; where and
+// what: mlp_bwd_plan.h, "live rows").  Only for row counts bwdplan::live_list_fits() accepts.
+struct LiveJob {
+    const float* g_raw;
+    int n_rows;
+    float* partials;
+};
+int live_list(int n, const LiveJob* jobs, hipStream_t st);
+// Does the 16-bit backward run over the live rows only?  PLNERF_BWD_COMPACT=0 in the environment (read at every call: A/B
+// measurements and the tests' dense leg) selects the dense path; so does a row count the list has no room for.
+bool bwd_compact(int n_rows);
 // The composed view layer of the 16-bit modes (mlp_layout.h; mlp_compose.hip).
 //   compose_pack: cb <- W_c = W_vf W_f, b_c = W_vf b_f + b_v (fp64 accumulation, rounded once) and copies of W_vf, W_f, b_f
 //   compose_grads (per job, after the split-K reduction left G and s in `gred`): grads[P_WF] = W_vf^T G, grads[P_BF] = W_vf^T s,
@@ -70,8 +85,9 @@ struct ComposeGradJob {
 };
 int compose_grads(int n, const ComposeGradJob* jobs, hipStream_t st);
 // gradient with respect to the embedded input rows, from the dz planes a finished plnerf_mlp_bwd left in its workspace
+// (live: the workspace's partials section as words when that backward ran over the live rows only, else nullptr)
 int input_grad(const float* const* params, int n_rows, const void* dz, const unsigned* gmax, bool h16, int xyz_ch,
-               int dir_ch, float* g_emb, hipStream_t st);
+               int dir_ch, float* g_emb, const unsigned* live, hipStream_t st);
 // g_eff [n_rows, 4] = g_raw with the sigma column times the density activation's derivative (from raw_out, the forward's
 // activated output); out (nullable): max |g_eff| as fp32 bits, like absmax
 int absmax_act(const float* g_raw, const float* raw_out, float beta, int n_rows, float* g_eff, unsigned* out, hipStream_t st);

@@ -10,6 +10,8 @@
 //                         planes divided back out, + the range status for a data-parallel exchange)
 //   absmax_kernel, absmax_act_kernel   max |g_raw| = the half dz planes' launch scale (and the density activation's
 //                         derivative on the backward's entry)
+// The 16-bit modes run over the LIVE rows only (mlp_bwd_plan.h: "live rows"; the list is built by mlp_live.hip): the half
+// kernels, the head kernel, the reduction and input_grad_kernel then take rows and row ranges through the list (LISTED / `live`).
 //
 // Reference: what autograd derives for run_nerf_helpers.py:105-128 at loss.backward() (run_plnerf.py:1300):
 // dW_l = dz_l^T a_{l-1}, db_l = column sums of dz_l.  (Round 4: moved out of mlp_f32.hip, where the 16-bit modes' dominant
@@ -52,6 +54,12 @@ struct WgradArgs {
     int tile_o0[MAX_WTILES];
     int n_rows, rows_per_split;
     float* part;      // [splits][PART_PER_SPLIT]
+    // Live rows (half kernels; mlp_bwd_plan.h): `part` as words when it holds the network's live-row list, else nullptr.  The A
+    // operand (dz) is then addressed by COMPACT row, the B operands and g_raw by the listed source row, and the row ranges are
+    // bwdplan::live_ranges(n_live, cap) -- taken here, on the device, from the workspace's n_live (the host's rows_per_split
+    // and n_rows describe the dense launch and only size the grid).
+    const unsigned* live;
+    int cap;          // the row ranges the launch's grid holds for this network
 };
 // The half kernels take up to two networks per grid (round 5: plnerf_mlp_bwd_multi): row ranges [0, splits0) of the
 // grid's y extent belong to n[0], the rest to n[1] -- the ONE round of workgroups is dealt out over the networks in
@@ -199,7 +207,15 @@ __device__ __forceinline__ wh8 tr_frag_tiled(const _Float16* stage, int srows, i
 // vmcnt(0) and the younger stage's latency is back on the critical path (a first attempt inside the generic
 // kernel measured +-0 for exactly that reason).  O and I are therefore template parameters (slot counts static),
 // rows past the range are loaded from the clamped last row and zeroed by a select.
-template <int O, int I, int NI, bool DEEP, bool TILED = false, bool X2 = false>
+//
+// LISTED (live rows, mlp_bwd_plan.h): rows m of the range are COMPACT rows -- the A operand is read as before, a B chunk
+// (and the view job's second B operand and g_raw) from source row list[m + its row of the stage].  A thread's B chunks lie in
+// at most NL rows of the stage (tiled: rows tid & 31 and 32 + (tid & 31), which also are the rows of its B2 chunk and its
+// g_raw element); their list entries are requested one stage AHEAD of the loads that use them, behind that stage's own plane
+// loads, so the dependent address never waits.  Entries past the range are clamped to the last live row (those rows are
+// zeroed in stash): nothing is fetched from a row that is not live.  A template parameter, not a run-time test: the dense
+// instantiation is the code it was, and the number of outstanding loads stays countable in both.
+template <int O, int I, int NI, bool DEEP, bool TILED = false, bool X2 = false, bool LISTED = false>
 __device__ __forceinline__ void wgrad_half_body(const WgradArgs& a, const WJob& job, const int split, unsigned char* smem_raw) {
     // (TILED B: the 256-wide activation planes, and since round 5 the 64- / 32-wide encoding planes of the register-resident
     // forward, whose columns are in ITS order -- the reduction kernel un-permutes them, sv_enc_channel)
@@ -241,8 +257,12 @@ __device__ __forceinline__ void wgrad_half_body(const WgradArgs& a, const WJob& 
     const int wo = wave / WI, wi = wave % WI;
     const int o_base = wo * NO * 32, i_base = wi * NI * 32;
     const bool live = o_base < O && i_base < I;
-    const int m_begin = split * a.rows_per_split;
-    const int m_end = min(a.n_rows, m_begin + a.rows_per_split);
+    // (LISTED: n_live from the workspace and the range rule on it -- uniform, scalar registers; a range past the live rows
+    // starts at or past n_live and returns below, and the reduction counts the ranges by the same rule)
+    const int n_eff = LISTED ? (int)a.live[bwdplan::live_scan_word(bwdplan::LIVE_N)] : a.n_rows;
+    const int rps = LISTED ? bwdplan::live_ranges(n_eff, a.cap).rows_per_split : a.rows_per_split;
+    const int m_begin = split * rps;
+    const int m_end = min(n_eff, m_begin + rps);
     int a_row[SA], a_col[SA];        // ATILED: row of the stage | piece block of the chunk (as b_row / b_col below)
 #pragma unroll
     for (int j = 0; j < SA; ++j) {
@@ -260,8 +280,22 @@ __device__ __forceinline__ void wgrad_half_body(const WgradArgs& a, const WJob& 
             b_row[j] = q / B_C8; b_col[j] = (q % B_C8) * 8;
         }
     }
-    const int last_tile = (a.n_rows + 31) / 32 - 1;      // the last tile that holds a real row
+    const int last_tile = (n_eff + 31) / 32 - 1;      // the last tile that holds a real row
     const bool b_owner = tid < B_THREADS;
+    // LISTED: the distinct stage rows of the thread's B chunks (tiled, SB = 4: chunks 0, 1 | 2, 3 share a row) and the list
+    // entries of the stage the next fetch loads
+    constexpr int NL = LISTED ? ((TILED && SB >= 2) ? 2 : SB) : 1;
+    constexpr int B_PER_L = SB / NL;
+    static_assert(SB % NL == 0 && (!TILED || SB == 1 || SB == 4), "a thread's B chunks share rows in runs of SB / NL");
+    static_assert(!(LISTED && X2) || (NL == 2 && B2_CHUNKS == 256 && B2_CT == 128 && SROWS == 64), "B2 and g_raw use the B rows' entries");
+    unsigned le[NL];
+    auto list_fetch = [&](const int m) {
+        if constexpr (LISTED) {
+#pragma unroll
+            for (int e = 0; e < NL; ++e)
+                le[e] = a.live[bwdplan::live_entry_word((size_t)min(m + b_row[e * B_PER_L], n_eff - 1))];
+        }
+    };
     struct Set { wh8 a[SA]; wh8 b[SB]; wh8 b2; float g; };
     Set s0, s1;      // (s1 only in the DEEP variant)
     // bias partial = column sums of the dz stage.  Row-major A: a thread's chunks share one chunk column.  Tiled A: its
@@ -289,17 +323,28 @@ __device__ __forceinline__ void wgrad_half_body(const WgradArgs& a, const WJob& 
         }
 #pragma unroll
         for (int j = 0; j < SB; ++j) {
-            if (TILED)      // (m is a multiple of 64: a stage is two whole tiles; a tile past the plane re-reads the last one)
+            if constexpr (LISTED) {      // (le: the entries of THIS stage, requested by the previous fetch)
+                const size_t r = le[j / B_PER_L];
+                if (TILED) s.b[j] = WG_LD(reinterpret_cast<const wh8*>(Bg + ((r >> 5) * B_CT + b_col[j] * 32 + (r & 31)) * 8));
+                else s.b[j] = WG_LD(reinterpret_cast<const wh8*>(Bg + r * I + b_col[j]));
+            } else if (TILED)      // (m is a multiple of 64: a stage is two whole tiles; a tile past the plane re-reads the last one)
                 s.b[j] = WG_LD(reinterpret_cast<const wh8*>(
                     Bg + ((size_t)min((m >> 5) + (b_row[j] >> 5), last_tile) * B_CT + b_col[j] * 32 + (b_row[j] & 31)) * 8));
             else
                 s.b[j] = WG_LD(reinterpret_cast<const wh8*>(Bg + (size_t)min(m + b_row[j], last) * I + b_col[j]));
         }
         if constexpr (X2) {    // (every thread, like B: threads past the chunk count reload a neighbour's -- static load counts)
-            s.b2 = WG_LD(reinterpret_cast<const wh8*>(
-                B2g + ((size_t)min((m >> 5) + (b2_row >> 5), last_tile) * B2_CT + b2_col * 32 + (b2_row & 31)) * 8));
-            s.g = job.g_raw[4 * (size_t)min(m + (tid & (SROWS - 1)), last) + 3];
+            if constexpr (LISTED) {
+                const size_t r2 = le[(tid >> 7) & 1], rg = le[(tid >> 5) & 1];      // rows b2_row and tid & 63 of the stage
+                s.b2 = WG_LD(reinterpret_cast<const wh8*>(B2g + ((r2 >> 5) * B2_CT + b2_col * 32 + (r2 & 31)) * 8));
+                s.g = job.g_raw[4 * rg + 3];
+            } else {
+                s.b2 = WG_LD(reinterpret_cast<const wh8*>(
+                    B2g + ((size_t)min((m >> 5) + (b2_row >> 5), last_tile) * B2_CT + b2_col * 32 + (b2_row & 31)) * 8));
+                s.g = job.g_raw[4 * (size_t)min(m + (tid & (SROWS - 1)), last) + 3];
+            }
         }
+        list_fetch(m + SROWS);      // (fetches walk the stages in order, one call per stage: the next call's entries)
     };
     auto stash = [&](const Set& s, const int buf, const int m) {
         _Float16* A0 = lds + (size_t)buf * 2 * SPLANE;
@@ -387,7 +432,8 @@ __device__ __forceinline__ void wgrad_half_body(const WgradArgs& a, const WJob& 
     // and stage i+2 is requested into the other set; two iterations per trip keep the sets static
     // Fetches are UNCONDITIONAL (a stage past the range re-reads the clamped last row and is never stashed): a
     // branch around a fetch would again leave the number of outstanding loads unknown at the next wait.
-    if (m_begin >= m_end) return;     // (uniform; only when there are more row ranges than rows)
+    if (m_begin >= m_end) return;     // (uniform; only when there are more row ranges than rows -- or than LIVE rows)
+    list_fetch(m_begin);
     fetch(s0, m_begin);
     if constexpr (DEEP) {
         fetch(s1, m_begin + SROWS);
@@ -468,6 +514,9 @@ __device__ __forceinline__ void wgrad_half_body(const WgradArgs& a, const WJob& 
     }
 }
 
+// (LISTED: the launch over the live rows, mlp_bwd_plan.h -- a kernel of its own, so that the dense kernel is the code it was,
+// registers included.  A call's networks take the same one: wgrad_h16_multi.)
+template <bool LISTED>
 __global__ __launch_bounds__(512) void wgrad_thin_kernel(WgradArgs2 p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const bool second = (int)blockIdx.y >= p.splits0;      // (uniform)
@@ -477,14 +526,15 @@ __global__ __launch_bounds__(512) void wgrad_thin_kernel(WgradArgs2 p) {
     if (j < 0) return;      // (this network's direction columns ride on its view job: X2)
     const WJob job = a.jobs[j];
     if (job.b_tiled) {      // (uniform per workgroup: the register-resident forward's encoding planes; O = W only -- X2 above)
-        wgrad_half_body<W, PE_K, 1, true, true>(a, job, split, smem_raw);
+        wgrad_half_body<W, PE_K, 1, true, true, false, LISTED>(a, job, split, smem_raw);
     } else {
-        if (job.O == W) wgrad_half_body<W, PE_K, 1, true>(a, job, split, smem_raw);      // encoding columns of L0 / L5
-        else wgrad_half_body<HV, DPE_K, 1, true>(a, job, split, smem_raw);               // direction columns of the view layer
+        if (job.O == W) wgrad_half_body<W, PE_K, 1, true, false, false, LISTED>(a, job, split, smem_raw);      // encoding columns of L0 / L5
+        else wgrad_half_body<HV, DPE_K, 1, true, false, false, LISTED>(a, job, split, smem_raw);               // direction columns of the view layer
     }
 }
 
 // the 256-wide jobs on the same body (256 x 256 layers, 128 x 256 feature columns of the view layer)
+template <bool LISTED>
 __global__ __launch_bounds__(512) void wgrad_main_kernel(WgradArgs2 p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const bool second = (int)blockIdx.y >= p.splits0;      // (uniform)
@@ -492,11 +542,11 @@ __global__ __launch_bounds__(512) void wgrad_main_kernel(WgradArgs2 p) {
     const int split = (int)blockIdx.y - (second ? p.splits0 : 0);
     const WJob job = a.jobs[a.tile_job[blockIdx.x]];
     if (job.b_tiled) {      // (uniform per workgroup)
-        if (job.O == W) wgrad_half_body<W, W, 4, false, true>(a, job, split, smem_raw);
-        else wgrad_half_body<HV, W, 4, false, true, true>(a, job, split, smem_raw);      // (+ the direction columns: X2)
+        if (job.O == W) wgrad_half_body<W, W, 4, false, true, false, LISTED>(a, job, split, smem_raw);
+        else wgrad_half_body<HV, W, 4, false, true, true, LISTED>(a, job, split, smem_raw);      // (+ the direction columns: X2)
     } else {
-        if (job.O == W) wgrad_half_body<W, W, 4, false>(a, job, split, smem_raw);
-        else wgrad_half_body<HV, W, 4, false>(a, job, split, smem_raw);
+        if (job.O == W) wgrad_half_body<W, W, 4, false, false, false, LISTED>(a, job, split, smem_raw);
+        else wgrad_half_body<HV, W, 4, false, false, false, LISTED>(a, job, split, smem_raw);
     }
 }
 
@@ -510,6 +560,8 @@ struct HeadArgs {
     float* part;  // [n_wg][HEAD_PART]
     int tiled;    // half planes in SV_LAYOUT_TILED (rows_per_wg is then a multiple of 32)
     int skip_alpha;   // dW_alpha comes from the main launch's view job (PART_SIGMA): h7 is not read here
+    const unsigned* live;   // the network's live-row list (mlp_bwd_plan.h), or nullptr: the workgroup's rows are bwdplan::live_head(n_live)'s
+                            //   share of the list and g_raw / h7 / hv are read at the listed rows
 };
 
 template <typename PT>
@@ -533,8 +585,12 @@ __global__ __launch_bounds__(256) void wgrad_head_kernel(HeadArgs2<PT> p) {
     __shared__ float accv[RV][3][HV];
     __shared__ float red[4][4];
     const int tid = threadIdx.x;
-    const int m_begin = wg * a.rows_per_wg;
-    const int m_end = min(a.n_rows, m_begin + a.rows_per_wg);
+    const bool listed = a.live != nullptr;      // (uniform)
+    const int n_eff = listed ? (int)a.live[bwdplan::live_scan_word(bwdplan::LIVE_N)] : a.n_rows;
+    const int rows_per_wg = listed ? bwdplan::live_head(n_eff).rows_per_head_wg : a.rows_per_wg;
+    const int m_begin = wg * rows_per_wg;
+    const int m_end = min(n_eff, m_begin + rows_per_wg);
+    const auto src_row = [&](const int m) -> size_t { return listed ? (size_t)a.live[bwdplan::live_entry_word((size_t)m)] : (size_t)m; };
     const float4* g4 = reinterpret_cast<const float4*>(a.g_raw);
     // Tiled half planes (mlp_layout.h): a 16-byte piece = 8 features {4 g + 0..3, 8 + 4 g + 0..3} + 32 j + 16 f of one row,
     // 32 rows of a piece block contiguous.  Thread = (piece block, row class): eight lanes read one 128-byte line.
@@ -547,10 +603,11 @@ __global__ __launch_bounds__(256) void wgrad_head_kernel(HeadArgs2<PT> p) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) w[e] = 0.0f;
 #pragma unroll 4
-        for (int m = m_begin + r; m < m_end; m += R7) {
-            const float gs = a.g_raw[4 * (size_t)m + 3];
-            const PT* src = tiled ? a.h7 + (size_t)(m >> 5) * (32 * W) + ((size_t)c * 32 + (m & 31)) * 8
-                                  : a.h7 + (size_t)m * W + c * VEC;
+        for (int mc = m_begin + r; mc < m_end; mc += R7) {
+            const size_t m = src_row(mc);
+            const float gs = a.g_raw[4 * m + 3];
+            const PT* src = tiled ? a.h7 + (m >> 5) * (32 * W) + ((size_t)c * 32 + (m & 31)) * 8
+                                  : a.h7 + m * W + c * VEC;
             const vec_t h = *reinterpret_cast<const vec_t*>(src);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) w[e] = fmaf(gs, (float)h[e], w[e]);
@@ -568,10 +625,11 @@ __global__ __launch_bounds__(256) void wgrad_head_kernel(HeadArgs2<PT> p) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) { w0[e] = 0.0f; w1[e] = 0.0f; w2[e] = 0.0f; }
 #pragma unroll 4
-        for (int m = m_begin + r; m < m_end; m += RV) {
+        for (int mc = m_begin + r; mc < m_end; mc += RV) {
+            const size_t m = src_row(mc);
             const float4 g = g4[m];
-            const PT* src = tiled ? a.hv + (size_t)(m >> 5) * (32 * HV) + ((size_t)c * 32 + (m & 31)) * 8
-                                  : a.hv + (size_t)m * HV + c * VEC;
+            const PT* src = tiled ? a.hv + (m >> 5) * (32 * HV) + ((size_t)c * 32 + (m & 31)) * 8
+                                  : a.hv + m * HV + c * VEC;
             const vec_t h = *reinterpret_cast<const vec_t*>(src);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
@@ -591,7 +649,7 @@ __global__ __launch_bounds__(256) void wgrad_head_kernel(HeadArgs2<PT> p) {
     }
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     for (int m = m_begin + tid; m < m_end; m += 256) {
-        const float4 g = g4[m];
+        const float4 g = g4[src_row(m)];
         s0 += g.x; s1 += g.y; s2 += g.z; s3 += g.w;
     }
     s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
@@ -638,6 +696,8 @@ struct InGradArgs {
     const unsigned* gmax;   // half planes: the launch scale's maximum (nullptr: fp32 planes)
     int xyz_ch, dir_ch, n_rows;
     float* g_emb;           // [n_rows][xyz_ch + dir_ch]
+    const unsigned* live;   // half planes left by a backward over the live rows (mlp_bwd_plan.h): the planes' rows are compact rows,
+                            //   compact row k's result goes to row list[k] of g_emb (zeroed by the host beforehand); else nullptr
 };
 
 template <bool H16>
@@ -660,7 +720,8 @@ __global__ __launch_bounds__(256) void input_grad_kernel(InGradArgs a) {
     float unscale = 1.0f;
     if (H16 && a.gmax) unscale = __uint_as_float(dzh_unscale_bits(*a.gmax));      // (mlp_layout.h)
     const int r = tid & 31, cg = tid >> 5;
-    const int n_tiles = (a.n_rows + 31) / 32;
+    const int n_eff = a.live ? (int)a.live[bwdplan::live_scan_word(bwdplan::LIVE_N)] : a.n_rows;      // (uniform)
+    const int n_tiles = (n_eff + 31) / 32;
     const int out_ch = a.xyz_ch + a.dir_ch;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int row = tile * 32 + r;
@@ -669,7 +730,7 @@ __global__ __launch_bounds__(256) void input_grad_kernel(InGradArgs a) {
         for (int j = 0; j < 8; ++j) ax[j] = 0.0f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) ad[j] = 0.0f;
-        if (row < a.n_rows) {
+        if (row < n_eff) {
             for (int pb = 0; pb < 32; ++pb) {
                 float v0[8], v5[8];
                 int f[8];
@@ -714,7 +775,8 @@ __global__ __launch_bounds__(256) void input_grad_kernel(InGradArgs a) {
                     for (int j = 0; j < 4; ++j) ad[j] = fmaf(vv[e], wr[j], ad[j]);
                 }
             }
-            float* dst = a.g_emb + (size_t)row * out_ch;
+            const size_t out_row = a.live ? (size_t)a.live[bwdplan::live_entry_word((size_t)row)] : (size_t)row;
+            float* dst = a.g_emb + out_row * out_ch;
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if (cg * 8 + j < a.xyz_ch) dst[cg * 8 + j] = ax[j] * unscale;
@@ -739,6 +801,8 @@ struct ReduceArgs {
     float* gred;            // 16-bit modes (composed view layer, mlp_layout.h): the view job's 128 x 256 result is G = dz_view^T h7 and goes
                             // here with s = the job's bias sums behind it (compose_grads turns them into the factors' gradients);
                             // nullptr: fp32 mode, the reference's two layers
+    const unsigned* live;   // live rows (mlp_bwd_plan.h): the ranges that hold a row -- the only ones whose workgroups wrote a partial --
+    int cap_main, cap_thin; //   are bwdplan::live_ranges(n_live, cap) of either launch, counted here as the launches' workgroups count them
     GradPtrs G;
 };
 
@@ -773,7 +837,9 @@ __global__ void wgrad_reduce_kernel(ReduceArgs2 p) {
     // composed view layer: the feature layer's job and bias slots are not used
     if (a.gred && ((idx >= PART_MAIN + 7 * W * W && idx < PART_VMAIN) || (idx >= PART_BIAS + 8 * W && idx < PART_BIAS + 9 * W))) return;
     if (idx >= PART_SIGMA && !a.sig_main) return;
-    const int ns = thin ? a.splits_thin : a.splits;
+    int ns = thin ? a.splits_thin : a.splits;
+    if (a.live)      // (uniform; no live row: no range, the sum is an exact zero)
+        ns = bwdplan::live_ranges((int)a.live[bwdplan::live_scan_word(bwdplan::LIVE_N)], thin ? a.cap_thin : a.cap_main).splits;
     float s = 0.0f;
     {   // a batch's loads all in flight before its first add (one dependent load per add held the kernel at 33 us;
         // 22 us this way); the additions keep their left-to-right order, so the sums are the same bits
@@ -921,6 +987,10 @@ struct WgradPlan {
 };
 
 int plan_job(const plnerf::impl::WgradJob& jb, bool h16, bwdplan::Ranges main, bwdplan::Ranges thin, WgradPlan& P) {
+    // (live rows: the ranges a launch holds for this network -- counted from n_rows -- cap the ranges taken from n_live on the device,
+    // which can therefore never be more than the grid has workgroups for: bwdplan::live_ranges)
+    const int cap_main = main.splits, cap_thin = thin.splits;
+    const unsigned* live = (h16 && jb.compact) ? reinterpret_cast<const unsigned*>(jb.partials) : nullptr;
     const int n_rows = jb.n_rows;
     const size_t N = (size_t)n_rows;
     const size_t NS_ = h16 ? sv_rows(N) : N;       // row stride of the saved half state (padded, mlp_layout.h)
@@ -966,6 +1036,7 @@ int plan_job(const plnerf::impl::WgradJob& jb, bool h16, bwdplan::Ranges main, b
         if (tiled) { jv.B2 = dpe_plane; jv.part2_off = PART_VDIR; jv.g_raw = jb.g_raw; jv.gmax = jb.gmax; }      // (the direction columns and the sigma head on the job's idle waves)
         a.tile_job[nt] = 8; a.tile_o0[nt++] = 0;
         a.n_rows = n_rows; a.rows_per_split = main.rows_per_split; a.part = part;
+        a.live = live; a.cap = cap_main;
         P.main_args = a; P.nt = nt;
     }
     {
@@ -981,6 +1052,7 @@ int plan_job(const plnerf::impl::WgradJob& jb, bool h16, bwdplan::Ranges main, b
         // (Equal ROW counts per workgroup, not equal bytes: a stage costs its latency whatever its width, so
         // giving the 128 x 32 job half as many, twice as long ranges measured 0.27 ms slower per step.)
         a.n_rows = n_rows; a.rows_per_split = thin.rows_per_split; a.part = part;
+        a.live = live; a.cap = cap_thin;
         P.thin_args = a;
     }
     P.splits = main.splits; P.splits_thin = thin.splits;
@@ -993,6 +1065,7 @@ int plan_job(const plnerf::impl::WgradJob& jb, bool h16, bwdplan::Ranges main, b
         a.enc_tiled = tiled;
         a.sig_main = tiled;
         a.gred = h16 ? jb.gred : nullptr;
+        a.live = live; a.cap_main = cap_main; a.cap_thin = cap_thin;
         if (h16 && (!jb.gred || !jb.cb)) return PLNERF_EINVAL;
         a.G.xyz_ch = jb.xyz_ch; a.G.dir_ch = jb.dir_ch;
         for (int i = 0; i < PLNERF_N_PARAM_TENSORS; ++i) {
@@ -1045,6 +1118,9 @@ int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st) {
     // the one round of workgroups of each launch, dealt out in proportion to the networks' rows (a single network: all of it)
     bool all_tiled = true;
     for (int j = 0; j < n; ++j) all_tiled = all_tiled && jobs[j].saved_layout == SV_LAYOUT_TILED;
+    const bool listed = jobs[0].compact != 0;      // (over the live rows: every network of the call, or none)
+    for (int j = 1; j < n; ++j)
+        if ((jobs[j].compact != 0) != listed) return PLNERF_EINVAL;
     const int n_rows1 = n == 2 ? jobs[1].n_rows : 0;
     const bwdplan::Deal cap_main = bwdplan::deal(bwdplan::MAIN_ROUND, jobs[0].n_rows, n_rows1);
     const bwdplan::Deal cap_thin = bwdplan::deal(bwdplan::thin_round(all_tiled), jobs[0].n_rows, n_rows1);
@@ -1063,8 +1139,9 @@ int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st) {
         for (int j = 0; j < 2; ++j) a.n[j] = P[j < n ? j : 0].main_args;
         a.splits0 = P[0].splits;
         const int splits = P[0].splits + (n == 2 ? P[1].splits : 0);
-        (void)hipFuncSetAttribute((const void*)wgrad_main_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_main);
-        hipLaunchKernelGGL(wgrad_main_kernel, dim3(P[0].nt, splits), dim3(512), lds_main, st, a);
+        const auto kernel = listed ? wgrad_main_kernel<true> : wgrad_main_kernel<false>;
+        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_main);
+        hipLaunchKernelGGL(kernel, dim3(P[0].nt, splits), dim3(512), lds_main, st, a);
         PLNERF_CHECK_LAUNCH();
     }
     {
@@ -1072,8 +1149,9 @@ int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st) {
         for (int j = 0; j < 2; ++j) a.n[j] = P[j < n ? j : 0].thin_args;
         a.splits0 = P[0].splits_thin;
         const int splits = P[0].splits_thin + (n == 2 ? P[1].splits_thin : 0);
-        (void)hipFuncSetAttribute((const void*)wgrad_thin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(wgrad_thin_kernel, dim3(bwdplan::thin_tiles(all_tiled), splits), dim3(512), lds, st, a);
+        const auto kernel = listed ? wgrad_thin_kernel<true> : wgrad_thin_kernel<false>;
+        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3(bwdplan::thin_tiles(all_tiled), splits), dim3(512), lds, st, a);
         PLNERF_CHECK_LAUNCH();
     }
     {
@@ -1084,7 +1162,8 @@ int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st) {
             h.n[j] = HeadArgs<_Float16>{jobs[q].g_raw, (const _Float16*)P[q].main_args.jobs[8].B,      // (h7: the composed view job's B plane)
                                         (const _Float16*)((const unsigned char*)jobs[q].saved + (size_t)SVC_HV_OFF * NS_ * sizeof(_Float16)),
                                         jobs[q].n_rows, P[q].head.rows_per_head_wg, jobs[q].head_part,
-                                        jobs[q].saved_layout == SV_LAYOUT_TILED, jobs[q].saved_layout == SV_LAYOUT_TILED};
+                                        jobs[q].saved_layout == SV_LAYOUT_TILED, jobs[q].saved_layout == SV_LAYOUT_TILED,
+                                        P[q].main_args.live};
         }
         h.wgs0 = P[0].head.n_head;
         hipLaunchKernelGGL(wgrad_head_kernel<_Float16>, dim3(P[0].head.n_head + (n == 2 ? P[1].head.n_head : 0)), dim3(256), 0, st, h);
@@ -1099,8 +1178,10 @@ int wgrad_h16_multi(int n, const WgradJob* jobs, hipStream_t st) {
 }
 
 int input_grad(const float* const* params, int n_rows, const void* dzv, const unsigned* gmax, bool h16, int xyz_ch,
-               int dir_ch, float* g_emb, hipStream_t st) {
+               int dir_ch, float* g_emb, const unsigned* live, hipStream_t st) {
     const size_t N = (size_t)n_rows;
+    // (live rows: the kernel writes the listed rows only; a row without gradient has an input gradient of exactly zero)
+    if (live && hipMemsetAsync(g_emb, 0, N * (size_t)(xyz_ch + dir_ch) * sizeof(float), st) != hipSuccess) return PLNERF_ELAUNCH;
     const size_t es = h16 ? sizeof(_Float16) : sizeof(float);
     const size_t ND = h16 ? dz_rows(N) : N;
     const unsigned char* dz = (const unsigned char*)dzv;
@@ -1109,6 +1190,7 @@ int input_grad(const float* const* params, int n_rows, const void* dzv, const un
     a.dz0 = dz; a.dz5 = dz + (size_t)5 * W * ND * es; a.dzv = dz + (size_t)(h16 ? DZC_V_OFF : DZ_V_OFF) * ND * es;
     a.gmax = h16 ? gmax : nullptr;
     a.xyz_ch = xyz_ch; a.dir_ch = dir_ch; a.n_rows = n_rows; a.g_emb = g_emb;
+    a.live = h16 ? live : nullptr;
     const size_t lds = ((size_t)2 * W * PE_K + (size_t)HV * DPE_K) * sizeof(float);
     const int n_tiles = (n_rows + 31) / 32;
     const int grid = n_tiles < 256 ? n_tiles : 256;
