@@ -414,6 +414,21 @@ _disjoint(DPSTEP_TABLE_SIGNATURES, ALL_SIGNATURES)
 _disjoint(DPSTEP_TABLE_SIGNATURES, EXPERIMENTAL_SIGNATURES)
 _disjoint(DPSTEP_TABLE_SIGNATURES, CAMCODE_TABLE_SIGNATURES)
 
+# ---- a fifth table, for include/experimental/plnerf_hip_gemm16.h: one layer of the layer-by-layer route (generic.py) in the
+# 16-bit modes' arithmetic.  Experimental, and apart from the four tables above for the reason the third is apart from the
+# first two.
+GEMM16_SIGNATURES = {
+    "plnerf_gemm_h16": (c_i, [c_f, ctypes.c_int64, c_f, ctypes.c_int64, c_f] + [c_i] * 5 + [c_f, ctypes.c_int64, c_f, c_s]),
+}
+GEMM16_HEADERS = (
+    ("experimental/plnerf_hip_gemm16.h", GEMM16_SIGNATURES, {}),
+)
+GEMM16_TABLE_SIGNATURES = _merge(GEMM16_HEADERS)
+_disjoint(GEMM16_TABLE_SIGNATURES, ALL_SIGNATURES)
+_disjoint(GEMM16_TABLE_SIGNATURES, EXPERIMENTAL_SIGNATURES)
+_disjoint(GEMM16_TABLE_SIGNATURES, CAMCODE_TABLE_SIGNATURES)
+_disjoint(GEMM16_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES)
+
 _lib = None
 
 
@@ -429,7 +444,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES,
-                                  **DPSTEP_TABLE_SIGNATURES}.items():
+                                  **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -1,0 +1,318 @@
+// One nn.Linear of the generic route on the 16-bit MFMAs: C[M, N] = relu?(A[M, K] . W[N, K]^T + bias[N]), operands and
+// result fp32 in memory (include/experimental/plnerf_hip_gemm16.h).
+//
+// Reference: run_nerf_helpers.py:76-128 builds ANY netdepth / netwidth / skip list / encoding width; what the fused kernels
+// are not compiled for runs layer by layer (pl-nerf_amd/generic.py).  linear.hip serves that route on the exact-fp32 MFMA
+// whatever `precision` says; this file is the forward of the four 16-bit modes, in the arithmetic the fused kernels use
+// (DESIGN section 5): both operands are split ON THE FLY, in the loader, into x = hi + lo of IEEE half or bf16 (hi = the
+// value rounded to nearest even, lo = the fp32 residual x - hi, exact, rounded to nearest even), and every 16-deep k-step of
+// a 32 x 32 block is, in this order, hi.hi, lo.hi (A's lo with W's hi), hi.lo on v_mfma_f32_32x32x16_f16 / _bf16 with fp32
+// accumulation; the plain modes issue the one hi.hi product.  k ascends in steps of 16 from 0 whatever the tile: a row's
+// result does not depend on the tile or the launch it sits in.
+//
+// Structure: 256 threads = four waves, a 128 x 128 tile as 2 x 2 waves of 2 x 2 blocks (N <= 32: a 128 x 32 tile, four waves
+// of one block each -- the one- and three-column head layers would otherwise spend 127 / 128 of a tile on padding).  A stage
+// is 32 k deep.  Both operands are k-contiguous in memory: a thread loads four consecutive k of a row (one 16-byte load when
+// the base and the row stride allow it, dwords otherwise: the first layer reads K = lda = 63), splits them and writes the
+// halves k-fastest into the stage's planes (A hi | A lo | W hi | W lo; row stride 80 bytes = 5 sixteen-byte slots: odd, so the
+// sixteen rows of a ds_read_b128 lane group lie on sixteen different slots of the 256-byte bank row), where a lane's eight
+// k-elements of an MFMA operand are one 16-byte read.  Two stages in LDS (81,920 bytes in the split modes, no static LDS beside them: exactly two workgroups per CU):
+// the next stage's global loads are issued before the current stage's MFMAs and land in the other buffer behind them, one
+// barrier per stage.
+//
+// Edges: rows past M, columns past N and k past K contribute exact zeros and are never loaded; neither is anything between K
+// and the row stride.  Range (PLNERF_RANGE_* of plnerf_hip.h), IEEE-half modes only: an element of A beyond +-65,504 or not
+// finite is clamped there and raises PLNERF_RANGE_ACTIVATION, such an element of W PLNERF_RANGE_WEIGHT -- one atomic OR per
+// workgroup at most, none when `status` is NULL.  bf16 elements carry fp32's exponent range and set nothing.
+#include <atomic>
+
+#include "common.h"
+#include "mlp_frag.h"
+#include "../../include/experimental/plnerf_hip_gemm16.h"
+
+namespace {
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+struct Gemm16Args {
+    const float* a; long long lda;
+    const float* w; long long ldw;
+    const float* bias;      // [N] or nullptr
+    int M, N, K;
+    int relu;
+    float* c; long long ldc;
+    unsigned* status;       // or nullptr
+    int tiles_n;            // column tiles: workgroup b owns tile (b / tiles_n, b % tiles_n) -- the tiles that share rows of A
+                            // run side by side
+    int a_vec, w_vec;       // the operand's rows may be read 16 bytes at a time
+};
+
+constexpr float H16_MAX = 65504.0f;
+constexpr int KS = 32;                  // k per stage
+constexpr int RS = KS * 2 + 16;         // row stride of a plane, bytes
+constexpr int THREADS = 256;
+
+template <bool BF> struct Elem;
+template <> struct Elem<false> {
+    typedef f16x8 v8;
+    typedef f16x2 v2;
+    static __device__ __forceinline__ f32x16 mfma(const v8 a, const v8 b, const f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ f32x2 widen(const unsigned h) {
+        return __builtin_convertvector(__builtin_bit_cast(v2, h), f32x2);
+    }
+};
+template <> struct Elem<true> {
+    typedef bf16x8 v8;
+    typedef bf16x2 v2;
+    static __device__ __forceinline__ f32x16 mfma(const v8 a, const v8 b, const f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ f32x2 widen(const unsigned h) {
+        const f32x2 r = {__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};
+        return r;
+    }
+};
+
+// two fp32 values -> one dword of the hi plane (both rounded to nearest even) and one of the lo plane (the residuals, exact in
+// fp32, rounded once)
+template <bool BF, int NS>
+__device__ __forceinline__ void split2(const float v0, const float v1, unsigned& hi, unsigned& lo) {
+    typedef typename Elem<BF>::v2 v2;
+    const f32x2 v = {v0, v1};
+    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, v2));
+    if constexpr (NS == 2) {
+        // (x - hi is exact in fp32; written as fma(hi, -1, x), the same value, which for IEEE half is one mixed-precision
+        // instruction per element: widen, subtract, round)
+        const f32x2 h = Elem<BF>::widen(hi);
+        const f32x2 r = {__builtin_fmaf(h[0], -1.0f, v0), __builtin_fmaf(h[1], -1.0f, v1)};
+        lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, v2));
+    }
+}
+
+// four consecutive k of one row (zeros outside [0, rows) x [0, K)): one 16-byte load where the whole chunk lies inside K and
+// `vec` says the address is aligned, dwords otherwise.  (A loader that keeps each chunk's address through the k loop and
+// takes the stages inside K without a branch was measured against this one in the same run, 512 x 512 x 262,144: slower in
+// every mode, f16x3 0.96 against 0.76 ms -- LABNOTES.)
+__device__ __forceinline__ f32x4 load4(const float* base, const long long ld, const int row, const int rows, const int k,
+                                       const int K, const int vec) {
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (row < rows && k < K) {
+        const float* src = base + (long long)row * ld + k;
+        if (vec && k + 4 <= K) {
+            v = *reinterpret_cast<const f32x4*>(src);
+        } else {
+            v[0] = src[0];
+            if (k + 1 < K) v[1] = src[1];
+            if (k + 2 < K) v[2] = src[2];
+            if (k + 3 < K) v[3] = src[3];
+        }
+    }
+    return v;
+}
+
+// IEEE-half elements: a value beyond the half range (or not finite) is clamped to it (a NaN leaves as a finite value); `top`
+// keeps the largest magnitude met, as its bit pattern -- an infinity's or a NaN's compares above every finite one's
+__device__ __forceinline__ void clamp4(f32x4& v, unsigned& top) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const unsigned mag = __float_as_uint(v[e]) & 0x7fffffffu;
+        top = mag > top ? mag : top;
+        v[e] = fminf(fmaxf(v[e], -H16_MAX), H16_MAX);
+    }
+}
+
+template <bool BF, int NS>
+__device__ __forceinline__ void store4(unsigned char* plane_hi, const int plane_bytes, const int row, const int kc, const f32x4 v) {
+    unsigned h0, h1, l0 = 0u, l1 = 0u;
+    split2<BF, NS>(v[0], v[1], h0, l0);
+    split2<BF, NS>(v[2], v[3], h1, l1);
+    unsigned char* dst = plane_hi + row * RS + kc * 8;
+    const u32x2 hi = {h0, h1}, lo = {l0, l1};
+    *reinterpret_cast<u32x2*>(dst) = hi;
+    if constexpr (NS == 2) *reinterpret_cast<u32x2*>(dst + plane_bytes) = lo;
+}
+
+// WM x WN waves, each BM x BN blocks of 32 x 32
+template <bool BF, int NS, int WM, int WN, int BM, int BN>
+__global__ __launch_bounds__(THREADS) void gemm_h16_kernel(const Gemm16Args p) {
+    static_assert(WM * WN == 4, "four waves");
+    typedef typename Elem<BF>::v8 v8;
+    constexpr int TM = WM * BM * 32, TN = WN * BN * 32;
+    constexpr int A_PLANE = TM * RS, W_PLANE = TN * RS;
+    constexpr int W_OFF = NS * A_PLANE, STAGE = NS * (A_PLANE + W_PLANE);
+    constexpr int CA = TM * (KS / 4) / THREADS, CW = TN * (KS / 4) / THREADS;      // four-k chunks per thread and stage
+    static_assert(TM * (KS / 4) % THREADS == 0 && TN * (KS / 4) % THREADS == 0, "whole chunks per thread");
+    // two stages, and nothing else: the split variants' 81,920 bytes fit a CU's 163,840 exactly twice, so the range flags
+    // are gathered in the first dword of the stages once the k loop is done with them, not in a word of their own
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile_m = (int)(blockIdx.x / (unsigned)p.tiles_n), tile_n = (int)(blockIdx.x % (unsigned)p.tiles_n);
+    const int i0 = tile_m * TM, j0 = tile_n * TN;
+    const int wi = (wave % WM) * BM * 32, wj = (wave / WM) * BN * 32;
+
+    f32x16 acc[BM][BN];
+    plnerf::zero_acc(acc);
+    f32x4 ra[CA], rw[CW];
+    unsigned top_a = 0u, top_w = 0u;      // IEEE-half elements: the largest magnitudes split so far (bit patterns)
+    const int n_stages = (p.K + KS - 1) / KS;
+
+    // (chunk q of a thread: row (tid + 256 q) >> 3 of the tile, k-elements 4 ((tid + 256 q) & 7) .. + 3 of the stage)
+    auto fetch = [&](const int s) {      // stage s of both operands, global memory -> registers
+        const int k0 = s * KS;
+#pragma unroll
+        for (int q = 0; q < CA; ++q) {
+            const int ch = tid + THREADS * q;
+            ra[q] = load4(p.a, p.lda, i0 + (ch >> 3), p.M, k0 + 4 * (ch & 7), p.K, p.a_vec);
+        }
+#pragma unroll
+        for (int q = 0; q < CW; ++q) {
+            const int ch = tid + THREADS * q;
+            rw[q] = load4(p.w, p.ldw, j0 + (ch >> 3), p.N, k0 + 4 * (ch & 7), p.K, p.w_vec);
+        }
+    };
+    auto stash = [&](unsigned char* stage) {      // registers -> the stage's planes, split
+#pragma unroll
+        for (int q = 0; q < CA; ++q) {
+            const int ch = tid + THREADS * q;
+            if constexpr (!BF) clamp4(ra[q], top_a);
+            store4<BF, NS>(stage, A_PLANE, ch >> 3, ch & 7, ra[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < CW; ++q) {
+            const int ch = tid + THREADS * q;
+            if constexpr (!BF) clamp4(rw[q], top_w);
+            store4<BF, NS>(stage + W_OFF, W_PLANE, ch >> 3, ch & 7, rw[q]);
+        }
+    };
+
+    if (n_stages > 0) {
+        fetch(0);
+        stash(smem);
+    }
+    __syncthreads();
+    // this lane's operand rows: row (lane & 31) of a block, k-elements 8 (lane >> 5) .. + 7 of a k-step
+    const int frag = (lane & 31) * RS + (lane >> 5) * 16;
+    for (int s = 0; s < n_stages; ++s) {
+        const unsigned char* cur = smem + (s & 1) * STAGE;
+        if (s + 1 < n_stages) fetch(s + 1);
+#pragma unroll
+        for (int ks = 0; ks < KS / 16; ++ks) {
+            v8 fa[BM][NS], fw[BN][NS];
+#pragma unroll
+            for (int b = 0; b < BM; ++b)
+#pragma unroll
+                for (int h = 0; h < NS; ++h)
+                    fa[b][h] = *reinterpret_cast<const v8*>(cur + h * A_PLANE + (wi + 32 * b) * RS + frag + ks * 32);
+#pragma unroll
+            for (int b = 0; b < BN; ++b)
+#pragma unroll
+                for (int h = 0; h < NS; ++h)
+                    fw[b][h] = *reinterpret_cast<const v8*>(cur + W_OFF + h * W_PLANE + (wj + 32 * b) * RS + frag + ks * 32);
+#pragma unroll
+            for (int bi = 0; bi < BM; ++bi)
+#pragma unroll
+                for (int bj = 0; bj < BN; ++bj) {
+                    acc[bi][bj] = Elem<BF>::mfma(fa[bi][0], fw[bj][0], acc[bi][bj]);                          // hi . hi
+                    if constexpr (NS == 2) {
+                        acc[bi][bj] = Elem<BF>::mfma(fa[bi][1], fw[bj][0], acc[bi][bj]);                      // lo . hi
+                        acc[bi][bj] = Elem<BF>::mfma(fa[bi][0], fw[bj][1], acc[bi][bj]);                      // hi . lo
+                    }
+                }
+        }
+        // (the other buffer's last readers were the previous stage's MFMAs, behind the barrier that ended it)
+        if (s + 1 < n_stages) stash(smem + ((s + 1) & 1) * STAGE);
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int bj = 0; bj < BN; ++bj) {
+        const int j = j0 + wj + 32 * bj + (lane & 31);
+        if (j >= p.N) continue;
+        const float bias = p.bias ? p.bias[j] : 0.0f;
+#pragma unroll
+        for (int bi = 0; bi < BM; ++bi)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int i = i0 + wi + 32 * bi + plnerf::frag_row(r, lane);
+                if (i >= p.M) continue;
+                float v = acc[bi][bj][r] + bias;
+                if (p.relu) v = v > 0.0f ? v : 0.0f;
+                p.c[(long long)i * p.ldc + j] = v;
+            }
+    }
+
+    if constexpr (!BF) {      // (uniform: every thread arrives at the barrier)
+        if (p.status) {
+            // (the stages' last readers are behind the barrier that ended the k loop -- or, with K == 0, the one before it)
+            unsigned* wg_range = reinterpret_cast<unsigned*>(smem);
+            const unsigned limit = __float_as_uint(H16_MAX);
+            const unsigned range = (top_a > limit ? PLNERF_RANGE_ACTIVATION : 0u) | (top_w > limit ? PLNERF_RANGE_WEIGHT : 0u);
+            if (tid == 0) *wg_range = 0u;
+            __syncthreads();
+            if (range) atomicOr(wg_range, range);
+            __syncthreads();
+            if (tid == 0 && *wg_range) atomicOr(p.status, *wg_range);
+        }
+    }
+}
+
+template <bool BF, int NS, int WM, int WN, int BM, int BN>
+int launch(Gemm16Args p, hipStream_t st) {
+    constexpr int TM = WM * BM * 32, TN = WN * BN * 32;
+    constexpr size_t lds = 2 * (size_t)NS * (TM + TN) * RS;
+    const long long tiles_m = ((long long)p.M + TM - 1) / TM, tiles_n = ((long long)p.N + TN - 1) / TN;
+    if (tiles_m * tiles_n > 0x7fffffffLL) return PLNERF_ERANGE;
+    p.tiles_n = (int)tiles_n;
+    auto kernel = gemm_h16_kernel<BF, NS, WM, WN, BM, BN>;
+    if (lds > 64 * 1024) {      // once per instantiation and device, not per layer and chunk
+        static std::atomic<unsigned long long> raised{0ull};
+        int device = 0;
+        if (hipGetDevice(&device) != hipSuccess) return PLNERF_ELAUNCH;
+        const unsigned long long bit = 1ull << (device & 63);
+        if (!(raised.load(std::memory_order_relaxed) & bit)) {
+            if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                return PLNERF_ELAUNCH;
+            raised.fetch_or(bit, std::memory_order_relaxed);
+        }
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(THREADS), lds, st, p);
+    PLNERF_CHECK_LAUNCH();
+    return PLNERF_OK;
+}
+
+template <bool BF, int NS>
+int launch_shape(const Gemm16Args& p, hipStream_t st) {
+    return p.N <= 32 ? launch<BF, NS, 4, 1, 1, 1>(p, st) : launch<BF, NS, 2, 2, 2, 2>(p, st);
+}
+
+// (an operand whose rows a thread may read 16 bytes at a time: the chunks start at multiples of four k)
+inline int vec_rows(const float* base, const int64_t ld) { return plnerf::aligned16(base) && ld % 4 == 0 ? 1 : 0; }
+
+}  // namespace
+
+extern "C" int plnerf_gemm_h16(const float* a, int64_t lda, const float* w, int64_t ldw, const float* bias, int M, int N, int K,
+                               int relu, int precision, float* c, int64_t ldc, int* status, plnerf_stream_t stream) {
+    if (M < 0 || N < 0 || K < 0 || ldc < N || lda < K || ldw < K || !c) return PLNERF_EINVAL;
+    if (precision != PLNERF_PREC_BF16X3 && precision != PLNERF_PREC_BF16 && precision != PLNERF_PREC_F16X3 &&
+        precision != PLNERF_PREC_F16)
+        return PLNERF_EINVAL;
+    if (M == 0 || N == 0) return PLNERF_OK;
+    if (K > 0 && (!a || !w)) return PLNERF_EINVAL;
+    const Gemm16Args p{a, lda, w, ldw, bias, M, N, K, relu ? 1 : 0, c, ldc, reinterpret_cast<unsigned*>(status), 1,
+                       vec_rows(a, lda), vec_rows(w, ldw)};
+    const hipStream_t st = (hipStream_t)stream;
+    switch (precision) {
+        case PLNERF_PREC_BF16X3: return launch_shape<true, 2>(p, st);
+        case PLNERF_PREC_BF16: return launch_shape<true, 1>(p, st);
+        case PLNERF_PREC_F16X3: return launch_shape<false, 2>(p, st);
+        default: return launch_shape<false, 1>(p, st);
+    }
+}

@@ -13,6 +13,21 @@ import torch
 
 from . import _lib as L
 
+# Opt-in: a generic network whose `precision` is one of the 16-bit modes runs its FORWARD products in that arithmetic
+# (plnerf_gemm_h16: operands split on the fly, hi.hi + lo.hi + hi.lo per k-step; the plain modes the one rounded product) and
+# owns a range status word (nerf.NeRF.status_word).  The backward stays on plnerf_gemm_f32 over the fp32 activations the
+# forward wrote.  Off (the default): every product is plnerf_gemm_f32 whatever `precision` says, bit for bit as before.
+# Set it BEFORE create_nerf: that is where the optimizers are handed the networks that guard their steps (render.create_nerf's
+# guard()), and a network outside the trunk is among them only if the switch is on then.  Switched on later, a clamped
+# forward still sets the word and check_range() still raises, but the Adam step is not withheld.
+# (A module switch like render.FUSE_CONST_EPILOGUE; tests set and restore it.)
+HONOUR_PRECISION = False
+
+
+def honours(net):
+    """True when `net`'s forward through this route runs in its own 16-bit precision (and has a range status word)."""
+    return HONOUR_PRECISION and net.precision in L.GUARDED_PRECISIONS
+
 
 def _gemm(a, a_rs, a_cs, b, b_rs, b_cs, M, N, K, bias=None, gate=None, relu=False, ones_col=False, out=None):
     c = torch.empty(M, N, device=a.device, dtype=torch.float32) if out is None else out
@@ -29,19 +44,54 @@ def _gemm(a, a_rs, a_cs, b, b_rs, b_cs, M, N, K, bias=None, gate=None, relu=Fals
     return c
 
 
+def _rows(t, name):
+    """Device pointer and row stride of a 2-D fp32 tensor whose rows are contiguous (a column slice of wider rows included:
+    plnerf_gemm_h16 takes the row stride, so no copy is made)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"plnerf_amd: `{name}` is on {t.device}; the HIP path needs a GPU tensor (there is no CPU fallback)")
+    return L.ctypes.c_void_p(t.data_ptr()), t.stride(0)
+
+
+def _gemm_h16(x, w, bias, relu, precision, status):
+    """relu?(x W^T + bias) in a 16-bit mode's arithmetic (plnerf_gemm_h16); x and w may be column slices of wider rows."""
+    M, K = x.shape
+    N = w.shape[0]
+    y = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    if M == 0 or N == 0:
+        return y
+    if M > 1 and x.stride(0) < K or N > 1 and w.stride(0) < K:      # (an expanded view: rows that overlap)
+        raise RuntimeError("plnerf_amd: plnerf_gemm_h16 needs rows at least K apart")
+    (a_ptr, lda), (w_ptr, ldw) = _rows(x, "x"), _rows(w, "weight")
+    L.check(L.lib().plnerf_gemm_h16(a_ptr, max(lda, K), w_ptr, max(ldw, K), L.dptr(bias, "bias"), M, N, K, int(relu),
+                                    L.PRECISION[precision], L.dptr(y, "y"), y.stride(0), L.dptr(status, "status", torch.int32),
+                                    L.stream()), "plnerf_gemm_h16")
+    return y
+
+
 class LinearFn(torch.autograd.Function):
-    """y = relu?(x W^T + b) as one plnerf_gemm_f32; backward: dx = (g * [y > 0]) W, [dW | db] = (g * [y > 0])^T [x | 1]."""
+    """y = relu?(x W^T + b) as one plnerf_gemm_f32 (with HONOUR_PRECISION and a 16-bit `precision`: one plnerf_gemm_h16, which
+    ORs into `status`); backward: dx = (g * [y > 0]) W, [dW | db] = (g * [y > 0])^T [x | 1], on plnerf_gemm_f32 either way."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu):
-        x = x.detach().to(torch.float32).contiguous()
-        w = weight.detach().to(torch.float32).contiguous()
+    def forward(ctx, x, weight, bias, relu, precision="fp32", status=None):
+        h16 = HONOUR_PRECISION and precision != "fp32"
+        x = x.detach().to(torch.float32)
+        w = weight.detach().to(torch.float32)
+        if not (h16 and x.dim() == 2 and x.stride(1) == 1):      # (the 16-bit entry reads a column slice in place)
+            x = x.contiguous()
+        if not (h16 and w.dim() == 2 and w.stride(1) == 1):
+            w = w.contiguous()
         M, K = x.shape
         N = w.shape[0]
         if w.shape[1] != K:      # (as F.linear: e.g. a skip after the LAST trunk layer, whose concatenation no head layer takes)
             raise RuntimeError(f"plnerf_amd: a layer with {w.shape[1]} input features got rows of {K}")
-        # B(k, j) = W[j, k]: row stride 1, column stride K
-        y = _gemm(x, K, 1, w, 1, K, M, N, K, bias=bias.detach().to(torch.float32).contiguous(), relu=relu)
+        b = bias.detach().to(torch.float32).contiguous()
+        if h16:
+            y = _gemm_h16(x, w, b, relu, precision, status)
+            x, w = x.contiguous(), w.contiguous()      # (what the backward's products index; a no-op but for a column slice)
+        else:
+            # B(k, j) = W[j, k]: row stride 1, column stride K
+            y = _gemm(x, K, 1, w, 1, K, M, N, K, bias=b, relu=relu)
         ctx.relu = bool(relu)
         ctx.save_for_backward(x, w, y if relu else None)
         return y
@@ -61,14 +111,14 @@ class LinearFn(torch.autograd.Function):
             gwb = _gemm(g, 1, N, x, K, 1, N, K + 1, M, gate=y, ones_col=True)
         gw = gwb[:, :K].contiguous() if gwb is not None and ctx.needs_input_grad[1] else None
         gb = gwb[:, K].contiguous() if gwb is not None and ctx.needs_input_grad[2] else None
-        return gx, gw, gb, None
+        return gx, gw, gb, None, None, None
 
 
-def linear(x, layer, relu):
+def linear(x, layer, relu, precision="fp32", status=None):
     if not x.is_cuda:
         raise RuntimeError(f"plnerf_amd: the generic NeRF route got a tensor on {x.device}; the HIP path needs a GPU tensor "
                            "(there is no CPU fallback)")
-    return LinearFn.apply(x, layer.weight, layer.bias, relu)
+    return LinearFn.apply(x, layer.weight, layer.bias, relu, precision, status)
 
 
 def _softplus_density(cols, at):
@@ -80,19 +130,25 @@ def forward(net, rows):
     """The module's layers applied to embedded rows [N, input_ch + view_ch], whatever its shape: what NeRF.forward computes
     (run_nerf_helpers.py:105-128; with the camera columns and the softplus density of the depth-supervised variant,
     depth_supervised_exps/model/run_nerf_helpers.py:164-205), every nn.Linear through LinearFn."""
+    # (with HONOUR_PRECISION: the network's 16-bit mode and its range status word, through every layer)
+    mode = net.precision if honours(net) else "fp32"
+    word = net.status_word() if mode != "fp32" else None
+
+    def layer(x, fc, relu):
+        return linear(x, fc, relu, mode, word)
     xyz = rows[:, :net.input_ch]
     act = xyz
     for depth, fc in enumerate(net.pts_linears):
-        act = linear(act, fc, relu=True)
+        act = layer(act, fc, relu=True)
         if depth in net.skips:      # the encoding re-enters BEHIND this layer, its channels first (:111-112)
             act = torch.cat((xyz, act), 1)
     if not net.use_viewdirs:
-        out = linear(act, net.output_linear, relu=False)
+        out = layer(act, net.output_linear, relu=False)
         return _softplus_density(out, 3) if net.density_activation == "softplus" else out
-    sigma = linear(act, net.alpha_linear, relu=False)
+    sigma = layer(act, net.alpha_linear, relu=False)
     side = rows[:, net.input_ch:net.input_ch + net.view_ch]      # direction encoding (+ camera code)
-    head = torch.cat((linear(act, net.feature_linear, relu=False), side), 1)
+    head = torch.cat((layer(act, net.feature_linear, relu=False), side), 1)
     for fc in net.views_linears:
-        head = linear(head, fc, relu=True)
-    out = torch.cat((linear(head, net.rgb_linear, relu=False), sigma), 1)
+        head = layer(head, fc, relu=True)
+    out = torch.cat((layer(head, net.rgb_linear, relu=False), sigma), 1)
     return _softplus_density(out, 3) if net.density_activation == "softplus" else out

@@ -292,7 +292,19 @@ class NeRF(nn.Module):
 
     def status_word(self):
         """The packed buffer's range status word as a 1-element int32 tensor (a view: the kernels OR into it).  Half-
-        element modes only set it (include/plnerf_hip.h: PLNERF_RANGE_*); optim.FlatAdam takes it as its guard."""
+        element modes only set it (include/plnerf_hip.h: PLNERF_RANGE_*); optim.FlatAdam takes it as its guard.
+        A network outside the compiled trunk has no packed buffer: with generic.HONOUR_PRECISION and a 16-bit precision it
+        owns a one-element tensor that plnerf_gemm_h16 ORs into; otherwise the call raises as before."""
+        if not self.is_supported():
+            from . import generic
+            if generic.honours(self):
+                dev = next(self.parameters()).device
+                if dev.type != "cuda":
+                    raise RuntimeError("plnerf_amd: the range status word lives on the GPU (there is no CPU fallback)")
+                word = self.__dict__.get("_generic_status")
+                if word is None or word.device != dev:
+                    word = self.__dict__["_generic_status"] = torch.zeros(1, device=dev, dtype=torch.int32)
+                return word
         self._require_supported()
         prec = L.PRECISION[self.precision]
         dev = next(self.parameters()).device

@@ -390,9 +390,16 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
             rgbs.append(rgb.cpu().numpy())
             disps.append(disp.cpu().numpy())
             for net in (render_kwargs.get('network_fn'), render_kwargs.get('network_fine')):
-                if isinstance(net, NeRF) and net.precision in L.GUARDED_PRECISIONS and net.is_supported():
+                if isinstance(net, NeRF) and net.precision in L.GUARDED_PRECISIONS and _has_status_word(net):
                     net.check_range()       # (the frame was just synchronised) a clamped frame must not pass silently
     return np.stack(rgbs, 0), np.stack(disps, 0)
+
+
+def _has_status_word(net):
+    """A network whose forward can set a range status word: the compiled trunk, and -- with generic.HONOUR_PRECISION -- a
+    layer-by-layer network in a 16-bit mode."""
+    from . import generic
+    return net.is_supported() or generic.honours(net)
 
 
 def _refuse_unsupported(*nets):
@@ -402,12 +409,19 @@ def _refuse_unsupported(*nets):
     kernels and fp32 whatever `precision` says, which the caller is told once, here, before any data is loaded.  What still
     raises: a shape the reference's own forward cannot run either (a skip after the last trunk layer)."""
     import warnings
+    from . import generic
     for net in nets:
         if net is None or net.is_supported():
             continue
         if any(k == net.D - 1 for k in net.skips):
             raise NotImplementedError(f"skips={net.skips} concatenates after the last trunk layer (netdepth {net.D}): the "
                                       "reference's head layers cannot consume that either (run_nerf_helpers.py:109-116)")
+        if generic.honours(net):      # (the switch is on: say what runs)
+            warnings.warn(f"plnerf_amd: D={net.D}, W={net.W}, skips={net.skips}, input_ch={net.input_ch}, input_ch_views="
+                          f"{net.input_ch_views} is outside the fused kernels' trunk: it runs layer by layer (generic.py), "
+                          f"unfused -- the forward in precision={net.precision!r} (plnerf_gemm_h16), the backward in fp32",
+                          RuntimeWarning, stacklevel=3)
+            continue
         warnings.warn(f"plnerf_amd: D={net.D}, W={net.W}, skips={net.skips}, input_ch={net.input_ch}, input_ch_views="
                       f"{net.input_ch_views} is outside the fused kernels' trunk: it runs layer by layer on exact-fp32 "
                       "products (generic.py), unfused and fp32 in every precision mode", RuntimeWarning, stacklevel=3)
@@ -449,7 +463,7 @@ def create_nerf(args, device=None):
     half_range = on_gpu and precision in L.GUARDED_PRECISIONS
 
     def guard(*nets):
-        nets = [n for n in nets if n is not None and n.is_supported()]
+        nets = [n for n in nets if n is not None and _has_status_word(n)]
         return {"guards": nets} if (half_range and nets) else {}
     adam = FlatAdam if on_gpu else torch.optim.Adam
     # (the fine network's step is guarded by BOTH networks: its samples and z_vals come from the coarse pass, and a

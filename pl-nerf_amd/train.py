@@ -580,7 +580,7 @@ class TrainStep:
             if hasattr(opt, "withheld_steps"):
                 withheld += opt.withheld_steps()
         for net in self.nets:
-            if getattr(net, "precision", None) in L.GUARDED_PRECISIONS and net.is_supported() and \
+            if getattr(net, "precision", None) in L.GUARDED_PRECISIONS and Rn._has_status_word(net) and \
                     next(net.parameters()).is_cuda:
                 net.check_range()
         if withheld and self.bucket is not None:
