@@ -429,6 +429,20 @@ _disjoint(GEMM16_TABLE_SIGNATURES, EXPERIMENTAL_SIGNATURES)
 _disjoint(GEMM16_TABLE_SIGNATURES, CAMCODE_TABLE_SIGNATURES)
 _disjoint(GEMM16_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES)
 
+# ---- a sixth table, for include/experimental/plnerf_hip_gemm16_bwd.h: the two backward products of such a layer (dgrad,
+# wgrad) in the same arithmetic.  Experimental, and a table of its own because the fifth is pinned to its one entry.
+_c_i64 = ctypes.c_int64
+GEMM16_BWD_SIGNATURES = {
+    "plnerf_gemm_h16_dgrad": (c_i, [c_f, _c_i64, c_f, _c_i64, c_f, _c_i64] + [c_i] * 4 + [c_f, c_f, _c_i64, c_f, c_s]),
+    "plnerf_gemm_h16_wgrad": (c_i, [c_f, _c_i64, c_f, _c_i64, c_f, _c_i64] + [c_i] * 4 + [c_f, c_f, _c_i64, c_i, c_f, c_f, c_s]),
+}
+GEMM16_BWD_HEADERS = (
+    ("experimental/plnerf_hip_gemm16_bwd.h", GEMM16_BWD_SIGNATURES, {}),
+)
+GEMM16_BWD_TABLE_SIGNATURES = _merge(GEMM16_BWD_HEADERS)
+for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES, GEMM16_TABLE_SIGNATURES):
+    _disjoint(GEMM16_BWD_TABLE_SIGNATURES, _table)
+
 _lib = None
 
 
@@ -444,7 +458,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES,
-                                  **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES}.items():
+                                  **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES, **GEMM16_BWD_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -23,10 +23,25 @@ from . import _lib as L
 # (A module switch like render.FUSE_CONST_EPILOGUE; tests set and restore it.)
 HONOUR_PRECISION = False
 
+# Opt-in, on top of HONOUR_PRECISION: where a layer's forward ran on plnerf_gemm_h16 (HONOUR_PRECISION on, a 16-bit
+# `precision`), its two BACKWARD products run in the same arithmetic (plnerf_gemm_h16_dgrad / _wgrad: the gated gradient and
+# the other operand split on the fly, hi.hi + lo.hi + hi.lo per 16-deep step in the x3 modes) and OR into the same status
+# word, so the guarded Adam withholds a step a backward product clamped like one a forward did.  In the IEEE-half modes the
+# gradient is scaled into the half range by a power of two taken from max |g| (one device scalar per layer and backward
+# call, no host sync).  Off (the default), or without HONOUR_PRECISION, or in an fp32 network: no effect -- the backward is
+# plnerf_gemm_f32, bit for bit as before.  Read when a layer's forward runs, so it may be switched between steps.
+HONOUR_PRECISION_BACKWARD = False
+_HALF = ("f16x3", "f16")      # IEEE-half elements: the backward entries are handed max |g|
+
 
 def honours(net):
     """True when `net`'s forward through this route runs in its own 16-bit precision (and has a range status word)."""
     return HONOUR_PRECISION and net.precision in L.GUARDED_PRECISIONS
+
+
+def _splits(M, N, K):
+    tiles = -(-M // 64) * -(-N // 64)
+    return max(1, min(1024 // tiles, K // 512)) if tiles < 256 else 1
 
 
 def _gemm(a, a_rs, a_cs, b, b_rs, b_cs, M, N, K, bias=None, gate=None, relu=False, ones_col=False, out=None):
@@ -35,8 +50,7 @@ def _gemm(a, a_rs, a_cs, b, b_rs, b_cs, M, N, K, bias=None, gate=None, relu=Fals
         return c
     # a product with few 64 x 64 output tiles and a long k (a weight gradient: k = the rows): deal k out so that ~1000
     # workgroups share it (64 of them walking 262,144 rows each measured 430 ms per backward at 8 x 512)
-    tiles = -(-M // 64) * -(-N // 64)
-    splits = max(1, min(1024 // tiles, K // 512)) if tiles < 256 else 1
+    splits = _splits(M, N, K)
     partials = torch.empty(splits * M * N, device=a.device, dtype=torch.float32) if splits > 1 else None
     L.check(L.lib().plnerf_gemm_f32(L.dptr(a, "a"), a_rs, a_cs, L.dptr(b, "b"), b_rs, b_cs, L.dptr(bias, "bias"), L.dptr(gate, "gate"),
                                     M, N, K, int(relu), 0, int(ones_col), L.dptr(c, "c"), c.stride(0), splits,
@@ -68,9 +82,44 @@ def _gemm_h16(x, w, bias, relu, precision, status):
     return y
 
 
+def _rows_h16(t, width, name):
+    """`t` as the 16-bit entries read it: fp32, rows contiguous and at least `width` apart (a column slice stays in place)."""
+    t = t.to(torch.float32)
+    if not (t.dim() == 2 and t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= width)):
+        t = t.contiguous()
+    ptr, ld = _rows(t, name)
+    return t, ptr, max(ld, width)
+
+
+def _backward_h16(g, y, x, w, precision, status, need_x, need_w):
+    """(dx, [dW | db]) of one layer in a 16-bit mode's arithmetic: plnerf_gemm_h16_dgrad / _wgrad.  The ReLU gate (y, or
+    None) is applied in the kernels' loaders; max |g| -- IEEE-half modes only -- is one device scalar shared by both."""
+    M, K = x.shape
+    N = w.shape[0]
+    g, g_ptr, ldg = _rows_h16(g, N, "grad")
+    (y_ptr, ldy) = _rows(y, "y") if y is not None else (None, 0)
+    absmax = torch.linalg.vector_norm(g, ord=float("inf")) if precision in _HALF and g.numel() else None
+    code, word, gx, gwb = L.PRECISION[precision], L.dptr(status, "status", torch.int32), None, None
+    if need_x:
+        gx = torch.empty(M, K, device=g.device, dtype=torch.float32)
+        w_ptr, ldw = _rows(w, "weight")
+        L.check(L.lib().plnerf_gemm_h16_dgrad(g_ptr, ldg, y_ptr, ldy, w_ptr, max(ldw, K), M, N, K, code, L.dptr(absmax, "absmax"),
+                                              L.dptr(gx, "gx"), max(K, 1), word, L.stream()), "plnerf_gemm_h16_dgrad")
+    if need_w:
+        gwb = torch.empty(N, K + 1, device=g.device, dtype=torch.float32)
+        splits = _splits(N, K + 1, M)
+        partials = torch.empty(splits * N * (K + 1), device=g.device, dtype=torch.float32) if splits > 1 else None
+        x_ptr, ldx = _rows(x, "x")
+        L.check(L.lib().plnerf_gemm_h16_wgrad(g_ptr, ldg, y_ptr, ldy, x_ptr, max(ldx, K), M, N, K, code, L.dptr(absmax, "absmax"),
+                                              L.dptr(gwb, "gwb"), K + 1, splits, L.dptr(partials, "partials"), word,
+                                              L.stream()), "plnerf_gemm_h16_wgrad")
+    return gx, gwb
+
+
 class LinearFn(torch.autograd.Function):
     """y = relu?(x W^T + b) as one plnerf_gemm_f32 (with HONOUR_PRECISION and a 16-bit `precision`: one plnerf_gemm_h16, which
-    ORs into `status`); backward: dx = (g * [y > 0]) W, [dW | db] = (g * [y > 0])^T [x | 1], on plnerf_gemm_f32 either way."""
+    ORs into `status`); backward: dx = (g * [y > 0]) W, [dW | db] = (g * [y > 0])^T [x | 1], on plnerf_gemm_f32 -- or, where
+    the forward ran on plnerf_gemm_h16 and HONOUR_PRECISION_BACKWARD is on, on plnerf_gemm_h16_dgrad / _wgrad."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu, precision="fp32", status=None):
@@ -86,9 +135,12 @@ class LinearFn(torch.autograd.Function):
         if w.shape[1] != K:      # (as F.linear: e.g. a skip after the LAST trunk layer, whose concatenation no head layer takes)
             raise RuntimeError(f"plnerf_amd: a layer with {w.shape[1]} input features got rows of {K}")
         b = bias.detach().to(torch.float32).contiguous()
+        ctx.h16_backward = bool(h16 and HONOUR_PRECISION_BACKWARD)
+        ctx.precision, ctx.status = precision, status
         if h16:
             y = _gemm_h16(x, w, b, relu, precision, status)
-            x, w = x.contiguous(), w.contiguous()      # (what the backward's products index; a no-op but for a column slice)
+            if not ctx.h16_backward:      # (the 16-bit backward entries take row strides: a column slice is read in place)
+                x, w = x.contiguous(), w.contiguous()      # (what the fp32 products index; a no-op but for a column slice)
         else:
             # B(k, j) = W[j, k]: row stride 1, column stride K
             y = _gemm(x, K, 1, w, 1, K, M, N, K, bias=b, relu=relu)
@@ -99,9 +151,15 @@ class LinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w, y = ctx.saved_tensors
-        g = g.to(torch.float32).contiguous()
         M, K = x.shape
         N = w.shape[0]
+        if ctx.h16_backward:
+            gx, gwb = _backward_h16(g, y, x, w, ctx.precision, ctx.status, ctx.needs_input_grad[0],
+                                    ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+            gw = gwb[:, :K].contiguous() if gwb is not None and ctx.needs_input_grad[1] else None
+            gb = gwb[:, K].contiguous() if gwb is not None and ctx.needs_input_grad[2] else None
+            return gx, gw, gb, None, None, None
+        g = g.to(torch.float32).contiguous()
         gx = gwb = None
         if ctx.needs_input_grad[0]:
             # dx[M, K] = gate(g)[M, N] . W[N, K]

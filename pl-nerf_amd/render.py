@@ -417,9 +417,11 @@ def _refuse_unsupported(*nets):
             raise NotImplementedError(f"skips={net.skips} concatenates after the last trunk layer (netdepth {net.D}): the "
                                       "reference's head layers cannot consume that either (run_nerf_helpers.py:109-116)")
         if generic.honours(net):      # (the switch is on: say what runs)
+            backward = (f"precision={net.precision!r} (plnerf_gemm_h16_dgrad / _wgrad)" if generic.HONOUR_PRECISION_BACKWARD
+                        else "fp32")
             warnings.warn(f"plnerf_amd: D={net.D}, W={net.W}, skips={net.skips}, input_ch={net.input_ch}, input_ch_views="
                           f"{net.input_ch_views} is outside the fused kernels' trunk: it runs layer by layer (generic.py), "
-                          f"unfused -- the forward in precision={net.precision!r} (plnerf_gemm_h16), the backward in fp32",
+                          f"unfused -- the forward in precision={net.precision!r} (plnerf_gemm_h16), the backward in {backward}",
                           RuntimeWarning, stacklevel=3)
             continue
         warnings.warn(f"plnerf_amd: D={net.D}, W={net.W}, skips={net.skips}, input_ch={net.input_ch}, input_ch_views="
