@@ -443,6 +443,39 @@ GEMM16_BWD_TABLE_SIGNATURES = _merge(GEMM16_BWD_HEADERS)
 for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES, GEMM16_TABLE_SIGNATURES):
     _disjoint(GEMM16_BWD_TABLE_SIGNATURES, _table)
 
+# ---- a seventh table, for include/experimental/plnerf_hip_generic.h: the layer-by-layer route's whole no-grad forward in one
+# call, on 16-bit activation planes (generic.CHAIN_INFERENCE), and the pack of fp32 rows into such planes.  Experimental, and a
+# table of its own because the fifth and sixth are pinned to their entries.
+GENERIC_MAX_SKIPS = 16                     # PLNERF_GENERIC_MAX_SKIPS
+GENERIC_WORKSPACE_ALIGN = 16               # PLNERF_GENERIC_WORKSPACE_ALIGN
+
+
+class GenericShape(ctypes.Structure):
+    """plnerf_generic_shape."""
+    _fields_ = [("D", c_i), ("W", c_i), ("input_ch", c_i), ("view_ch", c_i), ("use_viewdirs", c_i), ("output_ch", c_i),
+                ("n_view_layers", c_i), ("n_skips", c_i), ("skips", c_i * GENERIC_MAX_SKIPS)]
+
+
+def pack_ld(K):
+    """PLNERF_PACK_LD(K): elements per row of a packed plane."""
+    return -(-K // 8) * 8
+
+
+GENERIC_FWD_STRUCTS = {"plnerf_generic_shape": GenericShape}
+GENERIC_FWD_SIGNATURES = {
+    "plnerf_pack_h16": (c_i, [c_f, _c_i64, c_i, c_i, c_i, c_f, c_f, c_i, c_s]),
+    "plnerf_generic_fwd_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(GenericShape), c_i, c_i]),
+    "plnerf_generic_fwd": (c_i, [ctypes.POINTER(GenericShape), ctypes.POINTER(ctypes.c_void_p), c_f, _c_i64, c_i, c_i, c_f,
+                                 ctypes.c_size_t, c_f, _c_i64, c_f, c_s]),
+}
+GENERIC_FWD_HEADERS = (
+    ("experimental/plnerf_hip_generic.h", GENERIC_FWD_SIGNATURES, GENERIC_FWD_STRUCTS),
+)
+GENERIC_FWD_TABLE_SIGNATURES = _merge(GENERIC_FWD_HEADERS)
+for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES, GEMM16_TABLE_SIGNATURES,
+               GEMM16_BWD_TABLE_SIGNATURES):
+    _disjoint(GENERIC_FWD_TABLE_SIGNATURES, _table)
+
 _lib = None
 
 
@@ -458,7 +491,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES,
-                                  **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES, **GEMM16_BWD_TABLE_SIGNATURES}.items():
+                                  **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES, **GEMM16_BWD_TABLE_SIGNATURES,
+                                  **GENERIC_FWD_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

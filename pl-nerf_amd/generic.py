@@ -33,6 +33,14 @@ HONOUR_PRECISION = False
 HONOUR_PRECISION_BACKWARD = False
 _HALF = ("f16x3", "f16")      # IEEE-half elements: the backward entries are handed max |g|
 
+# Opt-in, on top of HONOUR_PRECISION: a forward that autograd would not record (grad mode off, or neither the rows nor a
+# parameter requires grad) is ONE plnerf_generic_fwd call per chunk instead of one plnerf_gemm_h16 per layer: the weights are
+# split once per call, the activations stay 16-bit planes in a workspace cached on the network, no torch op sits between the
+# layers.  The results are the layered route's bit for bit (the same clamp and split, applied by the producing layer's
+# epilogue instead of the consuming layer's loader) and the same bits of the status word are raised.  Off (the default), or
+# without HONOUR_PRECISION, or in an fp32 network, or whenever autograd records: no effect.  Read at every forward.
+CHAIN_INFERENCE = False
+
 
 def honours(net):
     """True when `net`'s forward through this route runs in its own 16-bit precision (and has a range status word)."""
@@ -184,10 +192,64 @@ def _softplus_density(cols, at):
     return torch.cat([cols[:, :at], torch.nn.functional.softplus(cols[:, at:at + 1], beta=10), cols[:, at + 1:]], 1)
 
 
+def chains(net, rows):
+    """True when forward(net, rows) takes the one-call entry: CHAIN_INFERENCE on a network that honours its precision, nothing
+    for autograd to record, and a shape the entry describes (its skip list holds PLNERF_GENERIC_MAX_SKIPS entries; a skip
+    behind the last trunk layer is left to the layered route, which names the layer that cannot consume it)."""
+    if not (CHAIN_INFERENCE and honours(net)):
+        return False
+    if torch.is_grad_enabled() and (rows.requires_grad or any(p.requires_grad for p in net.parameters())):
+        return False
+    live = _live_skips(net)
+    return len(live) <= L.GENERIC_MAX_SKIPS and net.D - 1 not in live
+
+
+def _live_skips(net):
+    return sorted(set(k for k in net.skips if 0 <= k < net.D))
+
+
+def _chain_forward(net, rows):
+    """One plnerf_generic_fwd call: raw outputs [N, 4 or output_ch]."""
+    if not rows.is_cuda:
+        raise RuntimeError(f"plnerf_amd: the generic NeRF route got a tensor on {rows.device}; the HIP path needs a GPU tensor "
+                           "(there is no CPU fallback)")
+    width = net.input_ch + net.view_ch
+    rows, rows_ptr, ld_rows = _rows_h16(rows.detach(), width, "rows")
+    n = rows.shape[0]
+    live = _live_skips(net)
+    shape = L.GenericShape(D=net.D, W=net.W, input_ch=net.input_ch, view_ch=net.view_ch, use_viewdirs=int(bool(net.use_viewdirs)),
+                           output_ch=0 if net.use_viewdirs else net.output_linear.out_features,
+                           n_view_layers=len(net.views_linears), n_skips=len(live))
+    for q, k in enumerate(live):
+        shape.skips[q] = k
+    layers = list(net.pts_linears) + list(net.views_linears)
+    layers += [net.feature_linear, net.alpha_linear, net.rgb_linear] if net.use_viewdirs else [net.output_linear]
+    tensors = [t.detach().to(torch.float32).contiguous() for fc in layers for t in (fc.weight, fc.bias)]
+    params = (L.ctypes.c_void_p * len(tensors))(*[L.dptr(t, "parameter").value for t in tensors])
+    out = torch.empty(n, 4 if net.use_viewdirs else shape.output_ch, device=rows.device, dtype=torch.float32)
+    if n == 0:
+        return out
+    code = L.PRECISION[net.precision]
+    nbytes = L.lib().plnerf_generic_fwd_workspace_bytes(L.ctypes.byref(shape), n, code)
+    if nbytes == 0:
+        raise RuntimeError("plnerf_amd: plnerf_generic_fwd_workspace_bytes refused this network")
+    ws = net.__dict__.get("_chain_workspace")      # (cached on the network and re-grown on demand, as _packed is)
+    if ws is None or ws.device != rows.device or ws.numel() < nbytes:
+        ws = net.__dict__["_chain_workspace"] = torch.empty(nbytes, device=rows.device, dtype=torch.uint8)
+    L.check(L.lib().plnerf_generic_fwd(L.ctypes.byref(shape), params, rows_ptr, ld_rows, n, code, L.ctypes.c_void_p(ws.data_ptr()),
+                                       ws.numel(), L.dptr(out, "out"), out.stride(0),
+                                       L.dptr(net.status_word(), "status", torch.int32), L.stream()), "plnerf_generic_fwd")
+    return out
+
+
 def forward(net, rows):
     """The module's layers applied to embedded rows [N, input_ch + view_ch], whatever its shape: what NeRF.forward computes
     (run_nerf_helpers.py:105-128; with the camera columns and the softplus density of the depth-supervised variant,
-    depth_supervised_exps/model/run_nerf_helpers.py:164-205), every nn.Linear through LinearFn."""
+    depth_supervised_exps/model/run_nerf_helpers.py:164-205), every nn.Linear through LinearFn -- or, with CHAIN_INFERENCE and
+    nothing for autograd to record, all of them in one plnerf_generic_fwd call."""
+    if chains(net, rows):
+        out = _chain_forward(net, rows)
+        return _softplus_density(out, 3) if net.density_activation == "softplus" else out
     # (with HONOUR_PRECISION: the network's 16-bit mode and its range status word, through every layer)
     mode = net.precision if honours(net) else "fp32"
     word = net.status_word() if mode != "fp32" else None

@@ -419,10 +419,12 @@ def _refuse_unsupported(*nets):
         if generic.honours(net):      # (the switch is on: say what runs)
             backward = (f"precision={net.precision!r} (plnerf_gemm_h16_dgrad / _wgrad)" if generic.HONOUR_PRECISION_BACKWARD
                         else "fp32")
+            no_grad = ("one plnerf_generic_fwd call per chunk on 16-bit activation planes (generic.CHAIN_INFERENCE), the same bits"
+                       if generic.CHAIN_INFERENCE else "the same layered route (generic.CHAIN_INFERENCE is off)")
             warnings.warn(f"plnerf_amd: D={net.D}, W={net.W}, skips={net.skips}, input_ch={net.input_ch}, input_ch_views="
                           f"{net.input_ch_views} is outside the fused kernels' trunk: it runs layer by layer (generic.py), "
-                          f"unfused -- the forward in precision={net.precision!r} (plnerf_gemm_h16), the backward in {backward}",
-                          RuntimeWarning, stacklevel=3)
+                          f"unfused -- the forward in precision={net.precision!r} (plnerf_gemm_h16), the backward in {backward}; "
+                          f"a no-grad forward takes {no_grad}", RuntimeWarning, stacklevel=3)
             continue
         warnings.warn(f"plnerf_amd: D={net.D}, W={net.W}, skips={net.skips}, input_ch={net.input_ch}, input_ch_views="
                       f"{net.input_ch_views} is outside the fused kernels' trunk: it runs layer by layer on exact-fp32 "
