@@ -7,25 +7,19 @@
 // (DESIGN section 5): both operands are split ON THE FLY, in the loader, into x = hi + lo of IEEE half or bf16 (hi = the
 // value rounded to nearest even, lo = the fp32 residual x - hi, exact, rounded to nearest even), and every 16-deep k-step of
 // a 32 x 32 block is, in this order, hi.hi, lo.hi (A's lo with W's hi), hi.lo on v_mfma_f32_32x32x16_f16 / _bf16 with fp32
-// accumulation; the plain modes issue the one hi.hi product.  k ascends in steps of 16 from 0 whatever the tile: a row's
-// result does not depend on the tile or the launch it sits in.
+// accumulation; the plain modes issue the one hi.hi product.
 //
-// Structure: 256 threads = four waves, a 128 x 128 tile as 2 x 2 waves of 2 x 2 blocks (N <= 32: a 128 x 32 tile, four waves
-// of one block each -- the one- and three-column head layers would otherwise spend 127 / 128 of a tile on padding).  A stage
-// is 32 k deep.  Both operands are k-contiguous in memory: a thread loads four consecutive k of a row (one 16-byte load when
-// the base and the row stride allow it, dwords otherwise: the first layer reads K = lda = 63), splits them and writes the
-// halves k-fastest into the stage's planes (A hi | A lo | W hi | W lo; row stride 80 bytes = 5 sixteen-byte slots: odd, so the
-// sixteen rows of a ds_read_b128 lane group lie on sixteen different slots of the 256-byte bank row), where a lane's eight
-// k-elements of an MFMA operand are one 16-byte read.  Two stages in LDS (81,920 bytes in the split modes, no static LDS beside them: exactly two workgroups per CU):
-// the next stage's global loads are issued before the current stage's MFMAs and land in the other buffer behind them, one
-// barrier per stage.
+// Structure (linear_h16_dev.h: Tile, and run_stages for the pipeline's description -- this kernel carries the loop in its own
+// text, see there): 256 threads = four waves on a 128 x 128 tile, 128 x 32 for N <= 32; a stage is 32 k deep.  Both operands are k-contiguous in memory: a thread loads four consecutive k of a row (one
+// 16-byte load when the base and the row stride allow it, dwords otherwise: the first layer reads K = lda = 63), splits them
+// and writes the halves k-fastest into the stage's planes (row stride 80 bytes = 5 sixteen-byte slots: odd, so the sixteen
+// rows of a ds_read_b128 lane group lie on sixteen different slots of the 256-byte bank row), where a lane's eight
+// k-elements of an MFMA operand are one 16-byte read.
 //
 // Edges: rows past M, columns past N and k past K contribute exact zeros and are never loaded; neither is anything between K
 // and the row stride.  Range (PLNERF_RANGE_* of plnerf_hip.h), IEEE-half modes only: an element of A beyond +-65,504 or not
 // finite is clamped there and raises PLNERF_RANGE_ACTIVATION, such an element of W PLNERF_RANGE_WEIGHT -- one atomic OR per
 // workgroup at most, none when `status` is NULL.  bf16 elements carry fp32's exponent range and set nothing.
-#include <atomic>
-
 #include "linear_h16_dev.h"
 #include "../../include/experimental/plnerf_hip_gemm16.h"
 
@@ -44,14 +38,11 @@ struct Gemm16Args {
     int a_vec, w_vec;       // the operand's rows may be read 16 bytes at a time
 };
 
-// WM x WN waves, each BM x BN blocks of 32 x 32
-template <bool BF, int NS, int WM, int WN, int BM, int BN>
+template <bool BF, class T>
 __global__ __launch_bounds__(THREADS) void gemm_h16_kernel(const Gemm16Args p) {
-    static_assert(WM * WN == 4, "four waves");
+    constexpr int NS = T::NS, WM = T::WM, BM = T::BM, BN = T::BN;
     typedef typename Elem<BF>::v8 v8;
-    constexpr int TM = WM * BM * 32, TN = WN * BN * 32;
-    constexpr int A_PLANE = TM * RS, W_PLANE = TN * RS;
-    constexpr int W_OFF = NS * A_PLANE, STAGE = NS * (A_PLANE + W_PLANE);
+    constexpr int TM = T::TM, TN = T::TN, A_PLANE = T::A_PLANE, W_PLANE = T::B_PLANE, W_OFF = T::B_OFF, STAGE = T::STAGE;
     constexpr int CA = TM * (KS / 4) / THREADS, CW = TN * (KS / 4) / THREADS;      // four-k chunks per thread and stage
     static_assert(TM * (KS / 4) % THREADS == 0 && TN * (KS / 4) % THREADS == 0, "whole chunks per thread");
     // two stages, and nothing else: the split variants' 81,920 bytes fit a CU's 163,840 exactly twice, so the range flags
@@ -98,6 +89,7 @@ __global__ __launch_bounds__(THREADS) void gemm_h16_kernel(const Gemm16Args p) {
         }
     };
 
+    // (run_stages' loop in this kernel's own text: linear_h16_dev.h describes it and says why it is not called here)
     if (n_stages > 0) {
         fetch(0);
         stash(smem);
@@ -154,70 +146,28 @@ __global__ __launch_bounds__(THREADS) void gemm_h16_kernel(const Gemm16Args p) {
             }
     }
 
-    if constexpr (!BF) {      // (uniform: every thread arrives at the barrier)
-        if (p.status) {
-            // (the stages' last readers are behind the barrier that ended the k loop -- or, with K == 0, the one before it)
-            unsigned* wg_range = reinterpret_cast<unsigned*>(smem);
-            const unsigned limit = __float_as_uint(H16_MAX);
-            const unsigned range = (top_a > limit ? PLNERF_RANGE_ACTIVATION : 0u) | (top_w > limit ? PLNERF_RANGE_WEIGHT : 0u);
-            if (tid == 0) *wg_range = 0u;
-            __syncthreads();
-            if (range) atomicOr(wg_range, range);
-            __syncthreads();
-            if (tid == 0 && *wg_range) atomicOr(p.status, *wg_range);
-        }
-    }
+    if constexpr (!BF)
+        raise_range(reinterpret_cast<unsigned*>(smem), p.status,
+                    beyond_half(top_a, PLNERF_RANGE_ACTIVATION) | beyond_half(top_w, PLNERF_RANGE_WEIGHT), tid);
 }
-
-template <bool BF, int NS, int WM, int WN, int BM, int BN>
-int launch(Gemm16Args p, hipStream_t st) {
-    constexpr int TM = WM * BM * 32, TN = WN * BN * 32;
-    constexpr size_t lds = 2 * (size_t)NS * (TM + TN) * RS;
-    const long long tiles_m = ((long long)p.M + TM - 1) / TM, tiles_n = ((long long)p.N + TN - 1) / TN;
-    if (tiles_m * tiles_n > 0x7fffffffLL) return PLNERF_ERANGE;
-    p.tiles_n = (int)tiles_n;
-    auto kernel = gemm_h16_kernel<BF, NS, WM, WN, BM, BN>;
-    if (lds > 64 * 1024) {      // once per instantiation and device, not per layer and chunk
-        static std::atomic<unsigned long long> raised{0ull};
-        int device = 0;
-        if (hipGetDevice(&device) != hipSuccess) return PLNERF_ELAUNCH;
-        const unsigned long long bit = 1ull << (device & 63);
-        if (!(raised.load(std::memory_order_relaxed) & bit)) {
-            if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return PLNERF_ELAUNCH;
-            raised.fetch_or(bit, std::memory_order_relaxed);
-        }
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(THREADS), lds, st, p);
-    PLNERF_CHECK_LAUNCH();
-    return PLNERF_OK;
-}
-
-template <bool BF, int NS>
-int launch_shape(const Gemm16Args& p, hipStream_t st) {
-    return p.N <= 32 ? launch<BF, NS, 4, 1, 1, 1>(p, st) : launch<BF, NS, 2, 2, 2, 2>(p, st);
-}
-
-// (an operand whose rows a thread may read 16 bytes at a time: the chunks start at multiples of four k)
-inline int vec_rows(const float* base, const int64_t ld) { return plnerf::aligned16(base) && ld % 4 == 0 ? 1 : 0; }
 
 }  // namespace
 
 extern "C" int plnerf_gemm_h16(const float* a, int64_t lda, const float* w, int64_t ldw, const float* bias, int M, int N, int K,
                                int relu, int precision, float* c, int64_t ldc, int* status, plnerf_stream_t stream) {
     if (M < 0 || N < 0 || K < 0 || ldc < N || lda < K || ldw < K || !c) return PLNERF_EINVAL;
-    if (precision != PLNERF_PREC_BF16X3 && precision != PLNERF_PREC_BF16 && precision != PLNERF_PREC_F16X3 &&
-        precision != PLNERF_PREC_F16)
-        return PLNERF_EINVAL;
+    if (!is_h16(precision)) return PLNERF_EINVAL;
     if (M == 0 || N == 0) return PLNERF_OK;
     if (K > 0 && (!a || !w)) return PLNERF_EINVAL;
-    const Gemm16Args p{a, lda, w, ldw, bias, M, N, K, relu ? 1 : 0, c, ldc, reinterpret_cast<unsigned*>(status), 1,
-                       vec_rows(a, lda), vec_rows(w, ldw)};
-    const hipStream_t st = (hipStream_t)stream;
-    switch (precision) {
-        case PLNERF_PREC_BF16X3: return launch_shape<true, 2>(p, st);
-        case PLNERF_PREC_BF16: return launch_shape<true, 1>(p, st);
-        case PLNERF_PREC_F16X3: return launch_shape<false, 2>(p, st);
-        default: return launch_shape<false, 1>(p, st);
-    }
+    Gemm16Args p{a, lda, w, ldw, bias, M, N, K, relu ? 1 : 0, c, ldc, reinterpret_cast<unsigned*>(status), 1,
+                 vec_rows(a, lda), vec_rows(w, ldw)};
+    return with_mode(precision, [&](auto bf, auto ns) {
+        return with_tile<decltype(ns)::value, false>(M, N, [&](auto tile) -> int {
+            typedef decltype(tile) T;
+            const long long tiles_m = ((long long)M + T::TM - 1) / T::TM, tiles_n = ((long long)N + T::TN - 1) / T::TN;
+            if (tiles_m * tiles_n > 0x7fffffffLL) return PLNERF_ERANGE;
+            p.tiles_n = (int)tiles_n;
+            return launch_tile<gemm_h16_kernel<decltype(bf)::value, T>, T>(tiles_m * tiles_n, p, (hipStream_t)stream);
+        });
+    });
 }

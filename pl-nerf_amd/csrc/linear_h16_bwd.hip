@@ -7,8 +7,8 @@
 //
 // One kernel serves both: an output tile of rows i and columns j, a contraction index c.  Operand A (rows i) is the gated
 // gradient, operand B (rows j) is W or [X | 1]; both are split on the fly into hi + lo and stored c-fastest into the stage's
-// planes exactly as the forward stores its k (A hi | A lo | B hi | B lo, row stride 80 bytes), so the MFMA loop, its fragment
-// reads and its order hi.hi, lo.hi, hi.lo are the forward's.  What differs is where an operand's contraction lies in memory:
+// planes exactly as the forward stores its k, so tile, pipeline and MFMA order are the forward's (linear_h16_dev.h: Tile,
+// run_stages).  What differs is where an operand's contraction lies in memory:
 //   contiguous (dgrad's gradient: c = n along a row of G): the forward's loader, load4 -- four consecutive c of one row;
 //   strided    (dgrad's W, both of wgrad's): the element (row r of the tile, c) lies at base + c ld + r.  A thread takes ONE
 //              tile row r and four consecutive c: four dword loads, each coalesced across the wave along r (64 lanes = 256
@@ -17,10 +17,8 @@
 // (The alternative -- halves stored row-major and MFMA fragments built with the transposing LDS reads of mlp_wgrad.hip -- was
 // not built; LABNOTES says what was measured.)
 //
-// 256 threads = four waves; a 128 x 128 tile as 2 x 2 waves of 2 x 2 blocks, 128 x 32 when the tile's columns are <= 32 (dgrad
-// with K <= 32; wgrad with K + 1 <= 32) and 32 x 128 when its rows are (wgrad of the head layers: N = 1, 3, 4).  Two 32-deep
-// stages in dynamic LDS (81,920 bytes in the split modes, no static LDS: two workgroups per CU), the next stage's global
-// loads issued ahead of the current stage's MFMAs, one barrier per stage.
+// Tiles (with_tile): 128 x 128, 128 x 32 when the tile's columns are <= 32 (dgrad with K <= 32; wgrad with K + 1 <= 32) and
+// 32 x 128 when wgrad's rows are (the head layers: N = 1, 3, 4).
 //
 // wgrad's long contraction: k_splits workgroups per tile, split z over the stages [z P, min(S, (z + 1) P)), S = ceil(M / 32),
 // P = ceil(S / k_splits); the partial tiles go to `partials` unscaled and reduce_splits adds them in split order.  No
@@ -29,8 +27,6 @@
 // Edges: tile rows and columns outside the output and c outside the contraction contribute exact zeros and are never loaded;
 // the ones column is the value 1 for c < M, never read.  Range, IEEE-half modes: clamp4 on the scaled gated gradient and on x
 // (PLNERF_RANGE_ACTIVATION) and on w (PLNERF_RANGE_WEIGHT), one atomic OR per workgroup at most.
-#include <atomic>
-
 #include "linear_h16_dev.h"
 #include "mlp_layout.h"
 #include "../../include/experimental/plnerf_hip_gemm16_bwd.h"
@@ -108,17 +104,10 @@ __device__ __forceinline__ f32x4 gate4(const f32x4 g, const f32x4 y, const float
     return v;
 }
 
-// WM x WN waves, each BM x BN blocks of 32 x 32.  WGRAD: A strided, B = [X | 1] strided; else A contiguous, B = W strided.
-template <bool BF, int NS, int WM, int WN, int BM, int BN, bool WGRAD>
+// WGRAD: A strided, B = [X | 1] strided; else A contiguous, B = W strided.
+template <bool BF, class T, bool WGRAD>
 __global__ __launch_bounds__(THREADS) void gemm_h16_bwd_kernel(const BwdArgs p) {
-    static_assert(WM * WN == 4, "four waves");
-    typedef typename Elem<BF>::v8 v8;
-    constexpr int TM = WM * BM * 32, TN = WN * BN * 32;
-    constexpr int A_PLANE = TM * RS, B_PLANE = TN * RS;
-    constexpr int B_OFF = NS * A_PLANE, STAGE = NS * (A_PLANE + B_PLANE);
-    constexpr int CA = TM * (KS / 4) / THREADS, CB = TN * (KS / 4) / THREADS;      // four-c chunks per thread and stage
-    static_assert(TM * (KS / 4) % THREADS == 0 && TN * (KS / 4) % THREADS == 0, "whole chunks per thread");
-    // (two stages and nothing else, as the forward: the range flags are gathered in the stages' first dword after the loop)
+    constexpr int NS = T::NS, BM = T::BM, BN = T::BN;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -129,8 +118,8 @@ __global__ __launch_bounds__(THREADS) void gemm_h16_bwd_kernel(const BwdArgs p) 
     const unsigned q = gridDim.x / 8u, r = gridDim.x % 8u, cls = blockIdx.x % 8u;
     const unsigned wg = (cls < r ? cls * (q + 1u) : r * (q + 1u) + (cls - r) * q) + blockIdx.x / 8u;
     const int split = (int)(wg / (unsigned)p.tiles), tile = (int)(wg % (unsigned)p.tiles);
-    const int i0 = (tile / p.tiles_j) * TM, j0 = (tile % p.tiles_j) * TN;
-    const int wi = (wave % WM) * BM * 32, wj = (wave / WM) * BN * 32;
+    const int i0 = (tile / p.tiles_j) * T::TM, j0 = (tile % p.tiles_j) * T::TN;
+    const int wi = (wave % T::WM) * BM * 32, wj = (wave / T::WM) * BN * 32;
 
     // (mlp_layout.h: the one derivation of the launch scale; the word is a maximum of absolute values)
     const unsigned gbits = p.gmax ? *p.gmax & 0x7fffffffu : 0u;
@@ -138,6 +127,9 @@ __global__ __launch_bounds__(THREADS) void gemm_h16_bwd_kernel(const BwdArgs p) 
 
     f32x16 acc[BM][BN];
     plnerf::zero_acc(acc);
+    constexpr int TM = T::TM, TN = T::TN;
+    constexpr int CA = TM * (KS / 4) / THREADS, CB = TN * (KS / 4) / THREADS;      // four-c chunks per thread and stage
+    static_assert(TM * (KS / 4) % THREADS == 0 && TN * (KS / 4) % THREADS == 0, "whole chunks per thread");
     f32x4 ra[CA], ry[CA], rb[CB];
     unsigned top_a = 0u, top_b = 0u;      // IEEE-half elements: the largest magnitudes split so far (bit patterns)
     const int all_stages = p.C / KS + (p.C % KS != 0);
@@ -168,55 +160,17 @@ __global__ __launch_bounds__(THREADS) void gemm_h16_bwd_kernel(const BwdArgs p) 
             const int ch = tid + THREADS * q;
             f32x4 v = gated ? gate4(ra[q], ry[q], scale) : ra[q] * scale;
             if constexpr (!BF) clamp4(v, top_a);
-            if constexpr (WGRAD) store4<BF, NS>(stage, A_PLANE, ch % TM, ch / TM, v);
-            else store4<BF, NS>(stage, A_PLANE, ch >> 3, ch & 7, v);
+            if constexpr (WGRAD) store4<BF, NS>(stage, T::A_PLANE, ch % TM, ch / TM, v);
+            else store4<BF, NS>(stage, T::A_PLANE, ch >> 3, ch & 7, v);
         }
 #pragma unroll
         for (int q = 0; q < CB; ++q) {
             const int ch = tid + THREADS * q;
             if constexpr (!BF) clamp4(rb[q], top_b);
-            store4<BF, NS>(stage + B_OFF, B_PLANE, ch % TN, ch / TN, rb[q]);
+            store4<BF, NS>(stage + T::B_OFF, T::B_PLANE, ch % TN, ch / TN, rb[q]);
         }
     };
-
-    if (s_begin < s_end) {
-        fetch(s_begin);
-        stash(smem);
-    }
-    __syncthreads();
-    // this lane's operand rows: row (lane & 31) of a block, c-elements 8 (lane >> 5) .. + 7 of a 16-deep step
-    const int frag = (lane & 31) * RS + (lane >> 5) * 16;
-    for (int s = s_begin; s < s_end; ++s) {
-        const unsigned char* cur = smem + ((s - s_begin) & 1) * STAGE;
-        if (s + 1 < s_end) fetch(s + 1);
-#pragma unroll
-        for (int ks = 0; ks < KS / 16; ++ks) {
-            v8 fa[BM][NS], fb[BN][NS];
-#pragma unroll
-            for (int b = 0; b < BM; ++b)
-#pragma unroll
-                for (int h = 0; h < NS; ++h)
-                    fa[b][h] = *reinterpret_cast<const v8*>(cur + h * A_PLANE + (wi + 32 * b) * RS + frag + ks * 32);
-#pragma unroll
-            for (int b = 0; b < BN; ++b)
-#pragma unroll
-                for (int h = 0; h < NS; ++h)
-                    fb[b][h] = *reinterpret_cast<const v8*>(cur + B_OFF + h * B_PLANE + (wj + 32 * b) * RS + frag + ks * 32);
-#pragma unroll
-            for (int bi = 0; bi < BM; ++bi)
-#pragma unroll
-                for (int bj = 0; bj < BN; ++bj) {
-                    acc[bi][bj] = Elem<BF>::mfma(fa[bi][0], fb[bj][0], acc[bi][bj]);                          // hi . hi
-                    if constexpr (NS == 2) {
-                        acc[bi][bj] = Elem<BF>::mfma(fa[bi][1], fb[bj][0], acc[bi][bj]);                      // lo . hi
-                        acc[bi][bj] = Elem<BF>::mfma(fa[bi][0], fb[bj][1], acc[bi][bj]);                      // hi . lo
-                    }
-                }
-        }
-        // (the other buffer's last readers were the previous stage's MFMAs, behind the barrier that ended it)
-        if (s + 1 < s_end) stash(smem + ((s + 1 - s_begin) & 1) * STAGE);
-        __syncthreads();
-    }
+    run_stages<BF, T>(acc, smem, s_begin, s_end, wi, wj, lane, fetch, stash);
 
     // one launch: the sums times 2^-s; split: this split's tile as it is (reduce_splits applies 2^-s to the total)
     const float unscale = p.k_splits > 1 ? 1.0f : __uint_as_float(plnerf::lay::dzh_unscale_bits(gbits));
@@ -235,20 +189,10 @@ __global__ __launch_bounds__(THREADS) void gemm_h16_bwd_kernel(const BwdArgs p) 
             }
     }
 
-    if constexpr (!BF) {      // (uniform: every thread arrives at the barriers)
-        if (p.status) {
-            // (the stages' last readers are behind the barrier that ended the loop -- or, with no stage, the one before it)
-            unsigned* wg_range = reinterpret_cast<unsigned*>(smem);
-            const unsigned limit = __float_as_uint(H16_MAX);
-            const unsigned range = (top_a > limit ? PLNERF_RANGE_ACTIVATION : 0u) |
-                                   (top_b > limit ? (WGRAD ? PLNERF_RANGE_ACTIVATION : PLNERF_RANGE_WEIGHT) : 0u);
-            if (tid == 0) *wg_range = 0u;
-            __syncthreads();
-            if (range) atomicOr(wg_range, range);
-            __syncthreads();
-            if (tid == 0 && *wg_range) atomicOr(p.status, *wg_range);
-        }
-    }
+    if constexpr (!BF)
+        raise_range(reinterpret_cast<unsigned*>(smem), p.status,
+                    beyond_half(top_a, PLNERF_RANGE_ACTIVATION) |
+                        beyond_half(top_b, WGRAD ? PLNERF_RANGE_ACTIVATION : PLNERF_RANGE_WEIGHT), tid);
 }
 
 // dwb[i, j] = 2^-s sum_z partials[z][i, j], z ascending
@@ -262,58 +206,22 @@ __global__ __launch_bounds__(THREADS) void reduce_splits(const float* partials, 
     out[e / J * ldo + e % J] = sum * __uint_as_float(plnerf::lay::dzh_unscale_bits(gbits));
 }
 
-template <bool BF, int NS, int WM, int WN, int BM, int BN, bool WGRAD>
-int launch(BwdArgs p, hipStream_t st) {
-    constexpr int TM = WM * BM * 32, TN = WN * BN * 32;
-    constexpr size_t lds = 2 * (size_t)NS * (TM + TN) * RS;
-    static_assert(lds <= 81920, "two workgroups share a CU");
-    const long long tiles_i = ((long long)p.I + TM - 1) / TM, tiles_j = ((long long)p.J + TN - 1) / TN;
-    if (tiles_i * tiles_j > 0x7fffffffLL || tiles_i * tiles_j * p.k_splits > 0x7fffffffLL) return PLNERF_ERANGE;
-    p.tiles_j = (int)tiles_j;
-    p.tiles = (int)(tiles_i * tiles_j);
-    const int all_stages = p.C / KS + (p.C % KS != 0);
-    p.per_split = (all_stages + p.k_splits - 1) / p.k_splits;
-    auto kernel = gemm_h16_bwd_kernel<BF, NS, WM, WN, BM, BN, WGRAD>;
-    if (lds > 64 * 1024) {      // once per instantiation and device, not per layer and chunk
-        static std::atomic<unsigned long long> raised{0ull};
-        int device = 0;
-        if (hipGetDevice(&device) != hipSuccess) return PLNERF_ELAUNCH;
-        const unsigned long long bit = 1ull << (device & 63);
-        if (!(raised.load(std::memory_order_relaxed) & bit)) {
-            if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return PLNERF_ELAUNCH;
-            raised.fetch_or(bit, std::memory_order_relaxed);
-        }
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(p.tiles * (long long)p.k_splits)), dim3(THREADS), lds, st, p);
-    PLNERF_CHECK_LAUNCH();
-    return PLNERF_OK;
-}
-
-template <bool BF, int NS, bool WGRAD>
-int launch_shape(const BwdArgs& p, hipStream_t st) {
-    if (WGRAD && p.I <= 32) return launch<BF, NS, 1, 4, 1, 1, WGRAD>(p, st);
-    if (p.J <= 32) return launch<BF, NS, 4, 1, 1, 1, WGRAD>(p, st);
-    return launch<BF, NS, 2, 2, 2, 2, WGRAD>(p, st);
-}
-
+// the (split, tile) list of one product, and its launch
 template <bool WGRAD>
-int launch_mode(const BwdArgs& p, const int precision, hipStream_t st) {
-    switch (precision) {
-        case PLNERF_PREC_BF16X3: return launch_shape<true, 2, WGRAD>(p, st);
-        case PLNERF_PREC_BF16: return launch_shape<true, 1, WGRAD>(p, st);
-        case PLNERF_PREC_F16X3: return launch_shape<false, 2, WGRAD>(p, st);
-        default: return launch_shape<false, 1, WGRAD>(p, st);
-    }
+int launch(BwdArgs p, const int precision, hipStream_t st) {
+    return with_mode(precision, [&](auto bf, auto ns) {
+        return with_tile<decltype(ns)::value, WGRAD>(p.I, p.J, [&](auto tile) -> int {
+            typedef decltype(tile) T;
+            const long long tiles_i = ((long long)p.I + T::TM - 1) / T::TM, tiles_j = ((long long)p.J + T::TN - 1) / T::TN;
+            if (tiles_i * tiles_j > 0x7fffffffLL || tiles_i * tiles_j * p.k_splits > 0x7fffffffLL) return PLNERF_ERANGE;
+            p.tiles_j = (int)tiles_j;
+            p.tiles = (int)(tiles_i * tiles_j);
+            const int all_stages = p.C / KS + (p.C % KS != 0);
+            p.per_split = (all_stages + p.k_splits - 1) / p.k_splits;
+            return launch_tile<gemm_h16_bwd_kernel<decltype(bf)::value, T, WGRAD>, T>(p.tiles * (long long)p.k_splits, p, st);
+        });
+    });
 }
-
-inline bool h16_mode(const int precision) {
-    return precision == PLNERF_PREC_BF16X3 || precision == PLNERF_PREC_BF16 || precision == PLNERF_PREC_F16X3 ||
-           precision == PLNERF_PREC_F16;
-}
-
-// (an operand whose rows a thread may read 16 bytes at a time: the chunks start at multiples of four)
-inline int vec_rows(const float* base, const int64_t ld) { return plnerf::aligned16(base) && ld % 4 == 0 ? 1 : 0; }
 
 }  // namespace
 
@@ -321,19 +229,19 @@ extern "C" int plnerf_gemm_h16_dgrad(const float* g, int64_t ldg, const float* y
                                      int M, int N, int K, int precision, const float* g_absmax, float* dx, int64_t lddx,
                                      int* status, plnerf_stream_t stream) {
     if (M < 0 || N < 0 || K < 0 || ldg < N || (y && ldy < N) || ldw < K || lddx < K || !dx) return PLNERF_EINVAL;
-    if (!h16_mode(precision)) return PLNERF_EINVAL;
+    if (!is_h16(precision)) return PLNERF_EINVAL;
     if (M == 0 || K == 0) return PLNERF_OK;
     if (N > 0 && (!g || !w)) return PLNERF_EINVAL;
     const BwdArgs p{g, ldg, y, ldy, w, ldw, M, K, N, reinterpret_cast<const unsigned*>(g_absmax), dx, lddx,
                     reinterpret_cast<unsigned*>(status), 1, 1, 1, 0, vec_rows(g, ldg), y ? vec_rows(y, ldy) : 0};
-    return launch_mode<false>(p, precision, (hipStream_t)stream);
+    return launch<false>(p, precision, (hipStream_t)stream);
 }
 
 extern "C" int plnerf_gemm_h16_wgrad(const float* g, int64_t ldg, const float* y, int64_t ldy, const float* x, int64_t ldx,
                                      int M, int N, int K, int precision, const float* g_absmax, float* dwb, int64_t lddwb,
                                      int k_splits, float* partials, int* status, plnerf_stream_t stream) {
     if (M < 0 || N < 0 || K < 0 || ldg < N || (y && ldy < N) || ldx < K || lddwb < (int64_t)K + 1 || !dwb) return PLNERF_EINVAL;
-    if (!h16_mode(precision)) return PLNERF_EINVAL;
+    if (!is_h16(precision)) return PLNERF_EINVAL;
     if (k_splits > 1 && !partials) return PLNERF_EINVAL;
     if (K == 0x7fffffff) return PLNERF_ERANGE;      // (K + 1 columns)
     if (N == 0) return PLNERF_OK;
@@ -345,7 +253,7 @@ extern "C" int plnerf_gemm_h16_wgrad(const float* g, int64_t ldg, const float* y
     const BwdArgs p{g, ldg, y, ldy, x, ldx, N, K + 1, M, reinterpret_cast<const unsigned*>(g_absmax),
                     splits > 1 ? partials : dwb, splits > 1 ? (long long)K + 1 : (long long)lddwb,
                     reinterpret_cast<unsigned*>(status), 1, 1, splits, 0, 0, 0};
-    const int rc = launch_mode<true>(p, precision, st);
+    const int rc = launch<true>(p, precision, st);
     if (rc != PLNERF_OK || splits == 1) return rc;
     hipLaunchKernelGGL(reduce_splits, dim3((unsigned)reduce_blocks), dim3(THREADS), 0, st, partials, splits, N, K + 1,
                        reinterpret_cast<const unsigned*>(g_absmax), dwb, (long long)lddwb);

@@ -9,16 +9,14 @@
 // made, k ascends in the same 16-deep steps from 0 -- so the results are plnerf_gemm_h16's bit for bit, and the range bit a
 // consumer's loader raised is raised by the producer's epilogue.
 //
-// The layer kernel is linear_h16.hip's (tile shapes, two 32-deep stages, 80-byte plane rows, hi.hi / lo.hi / hi.lo, the same
-// dynamic LDS and nothing static beside it) with three choices per operand: A from fp32 rows (split in the loader, as
-// there) or from packed planes; W from packed planes; C as fp32 rows through ldc (as there) or as packed planes.  A packed
-// operand's loader moves 16 bytes = 8 k-elements per load (a 32-deep stage of a row is four such chunks per plane) where the
-// chunk lies inside K, elements on a ragged tail: nothing between K and the row stride is read.  The packed epilogue: in the
-// accumulator layout a lane owns one output column, so a direct store is 2 bytes per lane; the stages are dead behind the k
-// loop's last barrier and hold a whole hi + lo tile, so the halves are staged there (row stride 2 TN + 16 bytes) and leave as
-// 16-byte row chunks, elements on a ragged edge (measured against the direct stores: faster in every mode, LABNOTES).
-#include <atomic>
-
+// The layer kernel is linear_h16.hip's (linear_h16_dev.h: the same Tile, the same two-stage loop) with three choices per
+// operand: A from fp32 rows (split in the loader, as there) or from packed planes; W from packed
+// planes; C as fp32 rows through ldc (as there) or as packed planes.  A packed operand's loader moves 16 bytes = 8 k-elements
+// per load (a 32-deep stage of a row is four such chunks per plane) where the chunk lies inside K, elements on a ragged tail:
+// nothing between K and the row stride is read.  The packed epilogue: in the accumulator layout a lane owns one output
+// column, so a direct store is 2 bytes per lane; the stages are dead behind the k loop's last barrier and hold a whole hi + lo tile, so the
+// halves are staged there (row stride 2 TN + 16 bytes) and leave as 16-byte row chunks, elements on a ragged edge (measured
+// against the direct stores: faster in every mode, LABNOTES).
 #include "linear_h16_dev.h"
 #include "../../include/experimental/plnerf_hip_generic.h"
 
@@ -61,20 +59,18 @@ struct ChainArgs {
     int a_vec;              // fp32 A: its rows may be read 16 bytes at a time
 };
 
-// WM x WN waves, each BM x BN blocks of 32 x 32; AP: A is packed; CP: C is packed
-template <bool BF, int NS, int WM, int WN, int BM, int BN, bool AP, bool CP>
+// AP: A is packed; CP: C is packed
+template <bool BF, class T, bool AP, bool CP>
 __global__ __launch_bounds__(THREADS) void chain_h16_kernel(const ChainArgs p) {
-    static_assert(WM * WN == 4, "four waves");
+    constexpr int NS = T::NS, WM = T::WM, BM = T::BM, BN = T::BN;
     typedef typename Elem<BF>::v8 v8;
-    constexpr int TM = WM * BM * 32, TN = WN * BN * 32;
-    constexpr int A_PLANE = TM * RS, W_PLANE = TN * RS;
-    constexpr int W_OFF = NS * A_PLANE, STAGE = NS * (A_PLANE + W_PLANE);
+    constexpr int TM = T::TM, TN = T::TN, A_PLANE = T::A_PLANE, W_PLANE = T::B_PLANE, W_OFF = T::B_OFF, STAGE = T::STAGE;
     constexpr int CA = TM * (KS / 4) / THREADS;                                    // fp32 A: four-k chunks per thread and stage
     constexpr int A_CHUNKS = TM * (KS / PACK_CHUNK), W_CHUNKS = TN * (KS / PACK_CHUNK);      // packed: eight-k chunks per plane
     constexpr int PA = (A_CHUNKS + THREADS - 1) / THREADS, PW = (W_CHUNKS + THREADS - 1) / THREADS;
     static_assert(TM * (KS / 4) % THREADS == 0, "whole chunks per thread");
     constexpr int T_ROW = TN * 2 + 16;      // packed C: bytes per row of the output tile staged in LDS (one plane: TM rows)
-    static_assert(NS * TM * T_ROW <= 2 * STAGE && T_ROW % 16 == 0 && TM * (TN / PACK_CHUNK) % THREADS == 0, "the tile fits the stages");
+    static_assert(NS * TM * T_ROW <= T::LDS && T_ROW % 16 == 0 && TM * (TN / PACK_CHUNK) % THREADS == 0, "the tile fits the stages");
     // two stages and nothing else, as in linear_h16.hip: the range flags are gathered in the stages' first dword
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -148,6 +144,7 @@ __global__ __launch_bounds__(THREADS) void chain_h16_kernel(const ChainArgs p) {
             }
     };
 
+    // (run_stages' loop in this kernel's own text: linear_h16_dev.h describes it and says why it is not called here)
     if (n_stages > 0) {
         fetch(0);
         stash(smem);
@@ -253,62 +250,28 @@ __global__ __launch_bounds__(THREADS) void chain_h16_kernel(const ChainArgs p) {
             }
         __syncthreads();      // (the range flags below reuse the first dword)
     }
-    if constexpr (!BF && (!AP || CP)) {      // (uniform: every thread arrives at the barrier)
-        if (p.status) {
-            // (the stages' last readers are behind the barrier that ended the k loop -- or, with K == 0, the one before it)
-            unsigned* wg_range = reinterpret_cast<unsigned*>(smem);
-            const unsigned range = top > __float_as_uint(H16_MAX) ? PLNERF_RANGE_ACTIVATION : 0u;
-            if (tid == 0) *wg_range = 0u;
-            __syncthreads();
-            if (range) atomicOr(wg_range, range);
-            __syncthreads();
-            if (tid == 0 && *wg_range) atomicOr(p.status, *wg_range);
-        }
-    }
-}
-
-template <bool BF, int NS, int WM, int WN, int BM, int BN, bool AP, bool CP>
-int launch(ChainArgs p, hipStream_t st) {
-    constexpr int TM = WM * BM * 32, TN = WN * BN * 32;
-    constexpr size_t lds = 2 * (size_t)NS * (TM + TN) * RS;
-    const long long tiles_m = ((long long)p.M + TM - 1) / TM, tiles_n = ((long long)p.N + TN - 1) / TN;
-    if (tiles_m * tiles_n > 0x7fffffffLL) return PLNERF_ERANGE;
-    p.tiles_n = (int)tiles_n;
-    auto kernel = chain_h16_kernel<BF, NS, WM, WN, BM, BN, AP, CP>;
-    if (lds > 64 * 1024) {      // once per instantiation and device, not per layer and call
-        static std::atomic<unsigned long long> raised{0ull};
-        int device = 0;
-        if (hipGetDevice(&device) != hipSuccess) return PLNERF_ELAUNCH;
-        const unsigned long long bit = 1ull << (device & 63);
-        if (!(raised.load(std::memory_order_relaxed) & bit)) {
-            if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return PLNERF_ELAUNCH;
-            raised.fetch_or(bit, std::memory_order_relaxed);
-        }
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(THREADS), lds, st, p);
-    PLNERF_CHECK_LAUNCH();
-    return PLNERF_OK;
+    if constexpr (!BF && (!AP || CP))
+        raise_range(reinterpret_cast<unsigned*>(smem), p.status, beyond_half(top, PLNERF_RANGE_ACTIVATION), tid);
 }
 
 template <bool BF, int NS, bool AP, bool CP>
-int launch_shape(const ChainArgs& p, hipStream_t st) {
-    return p.N <= 32 ? launch<BF, NS, 4, 1, 1, 1, AP, CP>(p, st) : launch<BF, NS, 2, 2, 2, 2, AP, CP>(p, st);
-}
-
-template <bool BF, int NS>
-int launch_operands(const ChainArgs& p, const bool a_packed, const bool c_packed, hipStream_t st) {
-    if (a_packed) return c_packed ? launch_shape<BF, NS, true, true>(p, st) : launch_shape<BF, NS, true, false>(p, st);
-    return c_packed ? launch_shape<BF, NS, false, true>(p, st) : launch_shape<BF, NS, false, false>(p, st);
+int launch_shape(ChainArgs p, hipStream_t st) {
+    return with_tile<NS, false>(p.M, p.N, [&](auto tile) -> int {
+        typedef decltype(tile) T;
+        const long long tiles_m = ((long long)p.M + T::TM - 1) / T::TM, tiles_n = ((long long)p.N + T::TN - 1) / T::TN;
+        if (tiles_m * tiles_n > 0x7fffffffLL) return PLNERF_ERANGE;
+        p.tiles_n = (int)tiles_n;
+        return launch_tile<chain_h16_kernel<BF, T, AP, CP>, T>(tiles_m * tiles_n, p, st);
+    });
 }
 
 int launch_layer(const ChainArgs& p, const int precision, const bool a_packed, const bool c_packed, hipStream_t st) {
-    switch (precision) {
-        case PLNERF_PREC_BF16X3: return launch_operands<true, 2>(p, a_packed, c_packed, st);
-        case PLNERF_PREC_BF16: return launch_operands<true, 1>(p, a_packed, c_packed, st);
-        case PLNERF_PREC_F16X3: return launch_operands<false, 2>(p, a_packed, c_packed, st);
-        default: return launch_operands<false, 1>(p, a_packed, c_packed, st);
-    }
+    return with_mode(precision, [&](auto bf, auto ns) {
+        constexpr bool BF = decltype(bf)::value;
+        constexpr int NS = decltype(ns)::value;
+        if (a_packed) return c_packed ? launch_shape<BF, NS, true, true>(p, st) : launch_shape<BF, NS, true, false>(p, st);
+        return c_packed ? launch_shape<BF, NS, false, true>(p, st) : launch_shape<BF, NS, false, false>(p, st);
+    });
 }
 
 // ---- plnerf_pack_h16: one thread per eight-column chunk of a row
@@ -348,15 +311,7 @@ __global__ __launch_bounds__(THREADS) void pack_h16_kernel(const float* __restri
                 }
         }
     }
-    if constexpr (!BF) {      // (uniform: every thread arrives at the barriers)
-        if (status) {
-            if (threadIdx.x == 0) wg_range = 0u;
-            __syncthreads();
-            if (top > __float_as_uint(H16_MAX)) atomicOr(&wg_range, range_bit);
-            __syncthreads();
-            if (threadIdx.x == 0 && wg_range) atomicOr(status, wg_range);
-        }
-    }
+    if constexpr (!BF) raise_range(&wg_range, status, beyond_half(top, range_bit), threadIdx.x);
 }
 
 // ---- the encoding columns into a concatenation's fp32 rows: dst[i, 0 .. cols) = src[i, 0 .. cols)
@@ -368,12 +323,6 @@ __global__ __launch_bounds__(THREADS) void copy_cols_kernel(const float* __restr
     if (row < rows) dst[row * ldd + col] = src[row * lds_ + col];
 }
 
-inline bool is_h16(const int precision) {
-    return precision == PLNERF_PREC_BF16X3 || precision == PLNERF_PREC_BF16 || precision == PLNERF_PREC_F16X3 ||
-           precision == PLNERF_PREC_F16;
-}
-inline int planes_of(const int precision) { return precision == PLNERF_PREC_BF16X3 || precision == PLNERF_PREC_F16X3 ? 2 : 1; }
-inline int vec_rows(const float* base, const int64_t ld) { return plnerf::aligned16(base) && ld % 4 == 0 ? 1 : 0; }
 inline size_t round_up(const size_t v, const size_t to) { return (v + to - 1) / to * to; }
 
 int pack_launch(const float* src, const int64_t ld, const int rows, const int K, const int precision, void* dst, unsigned* status,
@@ -383,12 +332,11 @@ int pack_launch(const float* src, const int64_t ld, const int rows, const int K,
     const dim3 grid((unsigned)groups), block(THREADS);
     unsigned short* d = static_cast<unsigned short*>(dst);
     const int vec = vec_rows(src, ld);
-    switch (precision) {
-        case PLNERF_PREC_BF16X3: hipLaunchKernelGGL((pack_h16_kernel<true, 2>), grid, block, 0, st, src, ld, rows, K, vec, d, status, range_bit); break;
-        case PLNERF_PREC_BF16: hipLaunchKernelGGL((pack_h16_kernel<true, 1>), grid, block, 0, st, src, ld, rows, K, vec, d, status, range_bit); break;
-        case PLNERF_PREC_F16X3: hipLaunchKernelGGL((pack_h16_kernel<false, 2>), grid, block, 0, st, src, ld, rows, K, vec, d, status, range_bit); break;
-        default: hipLaunchKernelGGL((pack_h16_kernel<false, 1>), grid, block, 0, st, src, ld, rows, K, vec, d, status, range_bit); break;
-    }
+    with_mode(precision, [&](auto bf, auto ns) {
+        hipLaunchKernelGGL((pack_h16_kernel<decltype(bf)::value, decltype(ns)::value>), grid, block, 0, st, src, ld, rows, K,
+                           vec, d, status, range_bit);
+        return 0;
+    });
     PLNERF_CHECK_LAUNCH();
     return PLNERF_OK;
 }
