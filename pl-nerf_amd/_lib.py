@@ -476,6 +476,26 @@ for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES
                GEMM16_BWD_TABLE_SIGNATURES):
     _disjoint(GENERIC_FWD_TABLE_SIGNATURES, _table)
 
+# ---- an eighth table, for include/experimental/plnerf_hip_generic_train.h: the layer-by-layer route's TRAINING forward and
+# backward as one call each (generic.CHAIN_TRAINING).  Experimental, and a table of its own because the seventh is pinned to
+# its entries; the struct is the seventh's (no mirror of its own).
+GENERIC_TRAIN_SIGNATURES = {
+    "plnerf_generic_train_saved_bytes": (ctypes.c_size_t, [ctypes.POINTER(GenericShape), c_i, c_i]),
+    "plnerf_generic_train_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(GenericShape), c_i, c_i]),
+    "plnerf_generic_train_wgrad_splits": (c_i, [c_i, c_i, c_i]),
+    "plnerf_generic_train_fwd": (c_i, [ctypes.POINTER(GenericShape), ctypes.POINTER(ctypes.c_void_p), c_f, _c_i64, c_i, c_i, c_f,
+                                       ctypes.c_size_t, c_f, _c_i64, c_f, c_s]),
+    "plnerf_generic_train_bwd": (c_i, [ctypes.POINTER(GenericShape), c_f, _c_i64, c_i, c_i, c_f, ctypes.c_size_t, c_f, _c_i64,
+                                       ctypes.POINTER(ctypes.c_void_p), c_f, ctypes.c_size_t, c_f, c_s]),
+}
+GENERIC_TRAIN_HEADERS = (
+    ("experimental/plnerf_hip_generic_train.h", GENERIC_TRAIN_SIGNATURES, {}),
+)
+GENERIC_TRAIN_TABLE_SIGNATURES = _merge(GENERIC_TRAIN_HEADERS)
+for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES, GEMM16_TABLE_SIGNATURES,
+               GEMM16_BWD_TABLE_SIGNATURES, GENERIC_FWD_TABLE_SIGNATURES):
+    _disjoint(GENERIC_TRAIN_TABLE_SIGNATURES, _table)
+
 _lib = None
 
 
@@ -492,7 +512,7 @@ def lib():
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES,
                                   **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES, **GEMM16_BWD_TABLE_SIGNATURES,
-                                  **GENERIC_FWD_TABLE_SIGNATURES}.items():
+                                  **GENERIC_FWD_TABLE_SIGNATURES, **GENERIC_TRAIN_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -17,8 +17,8 @@
 // column, so a direct store is 2 bytes per lane; the stages are dead behind the k loop's last barrier and hold a whole hi + lo tile, so the
 // halves are staged there (row stride 2 TN + 16 bytes) and leave as 16-byte row chunks, elements on a ragged edge (measured
 // against the direct stores: faster in every mode, LABNOTES).
-#include "linear_h16_dev.h"
-#include "../../include/experimental/plnerf_hip_generic.h"
+#include "generic_net.h"
+#include "../../include/experimental/plnerf_hip_generic_train.h"
 
 namespace {
 
@@ -57,10 +57,12 @@ struct ChainArgs {
     unsigned* status;       // or nullptr
     int tiles_n;
     int a_vec;              // fp32 A: its rows may be read 16 bytes at a time
+    unsigned* gate;         // GP: the gate plane, row i at gate + i ldgate words (bit j & 31 of word j >> 5: acc + bias > 0)
+    long long ldgate;
 };
 
-// AP: A is packed; CP: C is packed
-template <bool BF, class T, bool AP, bool CP>
+// AP: A is packed; CP: C is packed; GP: the epilogue also writes the gate plane (the training forward's ReLU layers)
+template <bool BF, class T, bool AP, bool CP, bool GP = false>
 __global__ __launch_bounds__(THREADS) void chain_h16_kernel(const ChainArgs p) {
     constexpr int NS = T::NS, WM = T::WM, BM = T::BM, BN = T::BN;
     typedef typename Elem<BF>::v8 v8;
@@ -194,6 +196,18 @@ __global__ __launch_bounds__(THREADS) void chain_h16_kernel(const ChainArgs p) {
             for (int r = 0; r < 16; r += 2) {      // (rows r and r + 1 of the fragment are adjacent rows of C)
                 const int i = i0 + wi + 32 * bi + plnerf::frag_row(r, lane);
                 float v0 = acc[bi][bj][r] + bias, v1 = acc[bi][bj][r + 1] + bias;
+                if constexpr (GP) {
+                    // The backward's gate is the fp32 sign, which the halves do not keep (a positive value below the
+                    // element's range packs to zeros).  The 32 lanes of a half-wave hold the 32 columns of one row of the
+                    // block (the lanes behind `continue` vote 0; a NaN compares false): one word each, stored by the
+                    // lane of the block's first column, which lies inside N whenever any of its columns does.
+                    const unsigned long long b0 = __builtin_amdgcn_ballot_w64(v0 > 0.0f), b1 = __builtin_amdgcn_ballot_w64(v1 > 0.0f);
+                    if ((lane & 31) == 0) {
+                        unsigned* word = p.gate + (long long)i * p.ldgate + (j >> 5);
+                        if (i < p.M) word[0] = (unsigned)(b0 >> (lane & 32));
+                        if (i + 1 < p.M) word[p.ldgate] = (unsigned)(b1 >> (lane & 32));
+                    }
+                }
                 if (p.relu) {
                     v0 = v0 > 0.0f ? v0 : 0.0f;
                     v1 = v1 > 0.0f ? v1 : 0.0f;
@@ -254,14 +268,14 @@ __global__ __launch_bounds__(THREADS) void chain_h16_kernel(const ChainArgs p) {
         raise_range(reinterpret_cast<unsigned*>(smem), p.status, beyond_half(top, PLNERF_RANGE_ACTIVATION), tid);
 }
 
-template <bool BF, int NS, bool AP, bool CP>
+template <bool BF, int NS, bool AP, bool CP, bool GP = false>
 int launch_shape(ChainArgs p, hipStream_t st) {
     return with_tile<NS, false>(p.M, p.N, [&](auto tile) -> int {
         typedef decltype(tile) T;
         const long long tiles_m = ((long long)p.M + T::TM - 1) / T::TM, tiles_n = ((long long)p.N + T::TN - 1) / T::TN;
         if (tiles_m * tiles_n > 0x7fffffffLL) return PLNERF_ERANGE;
         p.tiles_n = (int)tiles_n;
-        return launch_tile<chain_h16_kernel<BF, T, AP, CP>, T>(tiles_m * tiles_n, p, st);
+        return launch_tile<chain_h16_kernel<BF, T, AP, CP, GP>, T>(tiles_m * tiles_n, p, st);
     });
 }
 
@@ -269,6 +283,10 @@ int launch_layer(const ChainArgs& p, const int precision, const bool a_packed, c
     return with_mode(precision, [&](auto bf, auto ns) {
         constexpr bool BF = decltype(bf)::value;
         constexpr int NS = decltype(ns)::value;
+        if (p.gate) {
+            if (a_packed) return c_packed ? launch_shape<BF, NS, true, true, true>(p, st) : launch_shape<BF, NS, true, false, true>(p, st);
+            return c_packed ? launch_shape<BF, NS, false, true, true>(p, st) : launch_shape<BF, NS, false, false, true>(p, st);
+        }
         if (a_packed) return c_packed ? launch_shape<BF, NS, true, true>(p, st) : launch_shape<BF, NS, true, false>(p, st);
         return c_packed ? launch_shape<BF, NS, false, true>(p, st) : launch_shape<BF, NS, false, false>(p, st);
     });
@@ -323,8 +341,6 @@ __global__ __launch_bounds__(THREADS) void copy_cols_kernel(const float* __restr
     if (row < rows) dst[row * ldd + col] = src[row * lds_ + col];
 }
 
-inline size_t round_up(const size_t v, const size_t to) { return (v + to - 1) / to * to; }
-
 int pack_launch(const float* src, const int64_t ld, const int rows, const int K, const int precision, void* dst, unsigned* status,
                 const unsigned range_bit, hipStream_t st) {
     const long long groups = ((long long)rows * ((K - 1) / PACK_CHUNK + 1) + THREADS - 1) / THREADS;
@@ -341,81 +357,12 @@ int pack_launch(const float* src, const int64_t ld, const int rows, const int K,
     return PLNERF_OK;
 }
 
-// ---- the network: its layers in state_dict order, and where everything lies in the workspace
-constexpr int MAX_DIM = 65536;            // of every size of the shape (keeps the byte counts far inside size_t)
-constexpr size_t WS_ALIGN = 256;          // of every piece inside the workspace
-
-struct Net {
-    const plnerf_generic_shape* s;
-    int views, width_out;                 // view layers that run; columns of the output
-    int n_layers;                         // in state_dict order: D trunk, n_view_layers view, then feature / alpha / rgb or output
-    bool skip(const int i) const {
-        for (int q = 0; q < s->n_skips; ++q)
-            if (s->skips[q] == i) return true;
-        return false;
-    }
-    int feature() const { return s->D + s->n_view_layers; }      // (also output_linear's slot)
-    bool runs(const int l) const { return s->use_viewdirs || l < s->D || l >= feature(); }
-    void dims(const int l, int& N, int& K) const {
-        const int D = s->D, W = s->W;
-        if (l < D) {
-            N = W;
-            K = l == 0 ? s->input_ch : skip(l - 1) ? s->input_ch + W : W;
-        } else if (l < feature()) {
-            N = W / 2;
-            K = l == D ? W + s->view_ch : W / 2;
-        } else if (!s->use_viewdirs) {
-            N = s->output_ch;
-            K = W;
-        } else if (l == feature()) {
-            N = W;
-            K = W;
-        } else if (l == feature() + 1) {
-            N = 1;
-            K = W;
-        } else {
-            N = 3;
-            K = W / 2;
-        }
-    }
-};
-
+// ---- the network (generic_net.h: Net, describe, weight_offset) and where everything lies in the workspace
 struct Layout {
     size_t act[2], cat[2], bytes;      // two packed activation buffers, up to two fp32 concatenation buffers
     long long ld_cat;                  // floats per concatenation row (a multiple of four), 0: none
     int n_cat;
 };
-
-// PLNERF_OK and the network's description, or the refusal
-int describe(const plnerf_generic_shape* s, const int precision, Net& net) {
-    if (!s || !is_h16(precision)) return PLNERF_EINVAL;
-    if (s->D < 1 || s->W < 1 || s->input_ch < 1 || s->view_ch < 0 || s->n_view_layers < 0 || s->n_skips < 0 ||
-        s->n_skips > PLNERF_GENERIC_MAX_SKIPS)
-        return PLNERF_EINVAL;
-    if (s->use_viewdirs ? (s->W < 2 || s->n_view_layers < 1) : s->output_ch < 1) return PLNERF_EINVAL;
-    for (int q = 0; q < s->n_skips; ++q)
-        if (s->skips[q] < 0 || s->skips[q] > s->D - 2) return PLNERF_EINVAL;
-    if (s->D > MAX_DIM || s->W > MAX_DIM || s->input_ch > MAX_DIM || s->view_ch > MAX_DIM || s->n_view_layers > MAX_DIM ||
-        (!s->use_viewdirs && s->output_ch > MAX_DIM))
-        return PLNERF_ERANGE;
-    net.s = s;
-    net.views = s->use_viewdirs ? s->n_view_layers : 0;
-    net.width_out = s->use_viewdirs ? 4 : s->output_ch;
-    net.n_layers = s->D + s->n_view_layers + (s->use_viewdirs ? 3 : 1);
-    return PLNERF_OK;
-}
-
-// byte offset of layer l's packed weights (layers that do not run take no room)
-size_t weight_offset(const Net& net, const int l, const int planes) {
-    size_t off = 0;
-    for (int q = 0; q < l; ++q) {
-        if (!net.runs(q)) continue;
-        int N, K;
-        net.dims(q, N, K);
-        off += round_up(PLNERF_PACK_BYTES(N, K, planes), WS_ALIGN);
-    }
-    return off;
-}
 
 Layout lay_out(const Net& net, const int n, const int planes) {
     const plnerf_generic_shape* s = net.s;
@@ -469,31 +416,33 @@ extern "C" size_t plnerf_generic_fwd_workspace_bytes(const plnerf_generic_shape*
     return lay_out(net, n, planes_of(precision)).bytes;
 }
 
-extern "C" int plnerf_generic_fwd(const plnerf_generic_shape* shape, const float* const* params, const float* rows, int64_t ld_rows,
-                                  int n, int precision, void* workspace, size_t workspace_bytes, float* out, int64_t ld_out,
-                                  int* status, plnerf_stream_t stream) {
-    Net net;
-    const int rc = describe(shape, precision, net);
-    if (rc != PLNERF_OK) return rc;
-    const plnerf_generic_shape* s = shape;
+namespace {
+
+// where a layer's output goes: packed planes [n, N] (ld 0), or the fp32 rows of the concatenation that follows it (ld: their
+// stride in floats); the gate plane of a ReLU layer, or nullptr
+struct Place {
+    void* c;
+    long long ld;
+    unsigned* gate;
+};
+
+// The checks both forwards share, before any launch: PLNERF_OK, or the refusal.
+int check_forward(const Net& net, const float* const* params, const int64_t ld_rows, const int n, const int64_t ld_out) {
+    const plnerf_generic_shape* s = net.s;
     if (n < 0 || !params || ld_rows < (int64_t)s->input_ch + s->view_ch || ld_out < net.width_out) return PLNERF_EINVAL;
     for (int l = 0; l < net.n_layers; ++l)
         if (net.runs(l) && (!params[2 * l] || !params[2 * l + 1])) return PLNERF_EINVAL;
-    if (n == 0) return PLNERF_OK;
-    const int planes = planes_of(precision);
-    const Layout lay = lay_out(net, n, planes);
-    if (!rows || !out || !workspace || ((uintptr_t)workspace % PLNERF_GENERIC_WORKSPACE_ALIGN) != 0 || workspace_bytes < lay.bytes)
-        return PLNERF_EINVAL;
-    // every launch's grid, before the first: the widest layer's tiles, the copies' workgroups
-    const int widest = s->use_viewdirs || s->W > s->output_ch ? s->W : s->output_ch;
-    if ((((long long)n + 127) / 128) * (((long long)widest + 127) / 128) > 0x7fffffffLL) return PLNERF_ERANGE;
-    const int widest_copy = s->input_ch > s->view_ch ? s->input_ch : s->view_ch;
-    if (lay.n_cat && ((long long)n * widest_copy + THREADS - 1) / THREADS > 0x7fffffffLL) return PLNERF_ERANGE;
+    return PLNERF_OK;
+}
 
-    const hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    unsigned* word = reinterpret_cast<unsigned*>(status);
-    const int D = s->D, W = s->W;
+// The weight packs into `weights` (layer l at weight_offset), then every layer: the trunk in order, alpha_linear,
+// feature_linear, the view layers, rgb_linear.  place(l) says where layer l's output goes, asked once per hidden layer and
+// feature_linear in that order: the no-grad forward alternates two buffers, the training forward keeps every one.
+template <class PlaceFn>
+int run_layers(const Net& net, const float* const* params, const float* rows, const int64_t ld_rows, const int n, const int precision,
+               unsigned char* weights, PlaceFn&& place, float* out, const int64_t ld_out, unsigned* word, hipStream_t st) {
+    const plnerf_generic_shape* s = net.s;
+    const int planes = planes_of(precision), D = s->D, W = s->W;
 
     // the weights, once per call
     for (int l = 0; l < net.n_layers; ++l) {
@@ -501,60 +450,129 @@ extern "C" int plnerf_generic_fwd(const plnerf_generic_shape* shape, const float
         int N, K;
         net.dims(l, N, K);
         if (K == 0) continue;
-        const int e = pack_launch(params[2 * l], K, N, K, precision, ws + weight_offset(net, l, planes), word, PLNERF_RANGE_WEIGHT, st);
+        const int e = pack_launch(params[2 * l], K, N, K, precision, weights + weight_offset(net, l, planes), word, PLNERF_RANGE_WEIGHT, st);
         if (e != PLNERF_OK) return e;
     }
 
     // one layer: A from fp32 rows (a_packed false) or packed planes of n rows, C likewise
     auto layer = [&](const int l, const void* a, const long long lda, const bool a_packed, const int relu, void* c,
-                     const long long ldc, const bool c_packed) {
+                     const long long ldc, const bool c_packed, unsigned* gate) {
         int N, K;
         net.dims(l, N, K);
         if (N == 0) return (int)PLNERF_OK;
         const long long ldw = PLNERF_PACK_LD(K);
-        const ChainArgs p{a, lda, (long long)n * lda * 2, reinterpret_cast<const unsigned short*>(ws + weight_offset(net, l, planes)),
+        const ChainArgs p{a, lda, (long long)n * lda * 2, reinterpret_cast<const unsigned short*>(weights + weight_offset(net, l, planes)),
                           ldw, (long long)N * ldw * 2, params[2 * l + 1], n, N, K, relu, c, ldc, (long long)n * ldc * 2, word, 1,
-                          a_packed ? 0 : vec_rows(static_cast<const float*>(a), lda)};
+                          a_packed ? 0 : vec_rows(static_cast<const float*>(a), lda), gate, gate_ld(N)};
         return launch_layer(p, precision, a_packed, c_packed, st);
     };
 
-    int held = 0, cat = 0;                   // the packed buffer that holds the activation; the concatenation buffer in use
     const void* a = rows;                    // the next layer's input ...
     long long lda = ld_rows;
     bool a_packed = false;                   // ... which the first layer reads in place
     for (int l = 0; l < D; ++l) {
+        const Place to = place(l);
         int e;
         if (net.skip(l)) {      // [encoding | this layer] for the next one: fp32, through ldc, beside a copy of the encoding
-            if (!a_packed && a != rows) cat ^= (lay.n_cat - 1);      // (this layer READS a concatenation: write the other buffer)
-            float* rows_cat = reinterpret_cast<float*>(ws + lay.cat[cat]);
-            e = copy_cols(rows, ld_rows, n, s->input_ch, rows_cat, lay.ld_cat, st);
+            float* rows_cat = static_cast<float*>(to.c);
+            e = copy_cols(rows, ld_rows, n, s->input_ch, rows_cat, to.ld, st);
             if (e != PLNERF_OK) return e;
-            e = layer(l, a, lda, a_packed, 1, rows_cat + s->input_ch, lay.ld_cat, false);
-            a = rows_cat, lda = lay.ld_cat, a_packed = false;
+            e = layer(l, a, lda, a_packed, 1, rows_cat + s->input_ch, to.ld, false, to.gate);
+            a = rows_cat, lda = to.ld, a_packed = false;
         } else {
-            const int to = a_packed ? held ^ 1 : held;
-            e = layer(l, a, lda, a_packed, 1, ws + lay.act[to], PLNERF_PACK_LD(W), true);
-            held = to;
-            a = ws + lay.act[to], lda = PLNERF_PACK_LD(W), a_packed = true;
+            e = layer(l, a, lda, a_packed, 1, to.c, PLNERF_PACK_LD(W), true, to.gate);
+            a = to.c, lda = PLNERF_PACK_LD(W), a_packed = true;
         }
         if (e != PLNERF_OK) return e;
     }
     // (D - 1 is no skip: the trunk's activation is packed)
-    if (!s->use_viewdirs) return layer(net.feature(), a, lda, true, 0, out, ld_out, false);
-    int e = layer(net.feature() + 1, a, lda, true, 0, out + 3, ld_out, false);      // alpha_linear -> column 3
+    if (!s->use_viewdirs) return layer(net.feature(), a, lda, true, 0, out, ld_out, false, nullptr);
+    int e = layer(net.feature() + 1, a, lda, true, 0, out + 3, ld_out, false, nullptr);      // alpha_linear -> column 3
     if (e != PLNERF_OK) return e;
-    float* rows_cat = reinterpret_cast<float*>(ws + lay.cat[0]);      // (no trunk layer reads a concatenation any more)
-    e = layer(net.feature(), a, lda, true, 0, rows_cat, lay.ld_cat, false);      // [feature | view columns]
+    const Place cat = place(net.feature());
+    float* rows_cat = static_cast<float*>(cat.c);
+    e = layer(net.feature(), a, lda, true, 0, rows_cat, cat.ld, false, nullptr);      // [feature | view columns]
     if (e != PLNERF_OK) return e;
-    e = copy_cols(rows + s->input_ch, ld_rows, n, s->view_ch, rows_cat + W, lay.ld_cat, st);
+    e = copy_cols(rows + s->input_ch, ld_rows, n, s->view_ch, rows_cat + W, cat.ld, st);
     if (e != PLNERF_OK) return e;
-    a = rows_cat, lda = lay.ld_cat, a_packed = false;
-    for (int v = 0; v < net.views; ++v) {      // (the trunk's buffer is free: feature_linear and alpha_linear are enqueued)
-        const int to = held ^ 1;
-        e = layer(D + v, a, lda, a_packed, 1, ws + lay.act[to], PLNERF_PACK_LD(W / 2), true);
+    a = rows_cat, lda = cat.ld, a_packed = false;
+    for (int v = 0; v < net.views; ++v) {
+        const Place to = place(D + v);
+        e = layer(D + v, a, lda, a_packed, 1, to.c, PLNERF_PACK_LD(W / 2), true, to.gate);
         if (e != PLNERF_OK) return e;
-        held = to;
-        a = ws + lay.act[to], lda = PLNERF_PACK_LD(W / 2), a_packed = true;
+        a = to.c, lda = PLNERF_PACK_LD(W / 2), a_packed = true;
     }
-    return layer(net.feature() + 2, a, lda, true, 0, out, ld_out, false);      // rgb_linear -> columns 0 .. 2
+    return layer(net.feature() + 2, a, lda, true, 0, out, ld_out, false, nullptr);      // rgb_linear -> columns 0 .. 2
+}
+
+}  // namespace
+
+extern "C" int plnerf_generic_fwd(const plnerf_generic_shape* shape, const float* const* params, const float* rows, int64_t ld_rows,
+                                  int n, int precision, void* workspace, size_t workspace_bytes, float* out, int64_t ld_out,
+                                  int* status, plnerf_stream_t stream) {
+    Net net;
+    int rc = describe(shape, precision, net);
+    if (rc == PLNERF_OK) rc = check_forward(net, params, ld_rows, n, ld_out);
+    if (rc != PLNERF_OK) return rc;
+    if (n == 0) return PLNERF_OK;
+    const Layout lay = lay_out(net, n, planes_of(precision));
+    if (!rows || !out || !workspace || ((uintptr_t)workspace % PLNERF_GENERIC_WORKSPACE_ALIGN) != 0 || workspace_bytes < lay.bytes)
+        return PLNERF_EINVAL;
+    rc = check_grids(net, n, lay.n_cat != 0);
+    if (rc != PLNERF_OK) return rc;
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    // two packed buffers and up to two concatenation buffers in turn: a layer never writes the buffer it reads (the view
+    // layers reuse the trunk's: feature_linear and alpha_linear are enqueued by then)
+    int held = 0, cat = 0;
+    auto place = [&](const int l) {
+        const int D = net.s->D;
+        if (l == net.feature()) return Place{ws + lay.cat[0], lay.ld_cat, nullptr};      // (no trunk layer reads a concatenation any more)
+        const bool reads_cat = l > 0 && l < D && net.skip(l - 1);
+        if (l < D && net.skip(l)) {
+            if (reads_cat) cat ^= (lay.n_cat - 1);      // (this layer READS a concatenation: write the other buffer)
+            return Place{ws + lay.cat[cat], lay.ld_cat, nullptr};
+        }
+        if (l >= D || (l > 0 && !reads_cat)) held ^= 1;      // (this layer READS the packed buffer in use: write the other)
+        return Place{ws + lay.act[held], 0, nullptr};
+    };
+    return run_layers(net, params, rows, ld_rows, n, precision, ws, place, out, ld_out, reinterpret_cast<unsigned*>(status),
+                      (hipStream_t)stream);
+}
+
+extern "C" size_t plnerf_generic_train_saved_bytes(const plnerf_generic_shape* shape, int n, int precision) {
+    Net net;
+    if (describe(shape, precision, net) != PLNERF_OK || n < 0) return 0;
+    return lay_out_train(net, n, planes_of(precision)).saved_bytes;
+}
+
+extern "C" size_t plnerf_generic_train_workspace_bytes(const plnerf_generic_shape* shape, int n, int precision) {
+    Net net;
+    if (describe(shape, precision, net) != PLNERF_OK || n < 0) return 0;
+    return lay_out_train(net, n, planes_of(precision)).workspace_bytes;
+}
+
+extern "C" int plnerf_generic_train_wgrad_splits(int N, int K1, int M) { return wgrad_splits(N, K1, M); }
+
+extern "C" int plnerf_generic_train_fwd(const plnerf_generic_shape* shape, const float* const* params, const float* rows,
+                                        int64_t ld_rows, int n, int precision, void* saved, size_t saved_bytes, float* out,
+                                        int64_t ld_out, int* status, plnerf_stream_t stream) {
+    Net net;
+    int rc = describe(shape, precision, net);
+    if (rc == PLNERF_OK) rc = check_forward(net, params, ld_rows, n, ld_out);
+    if (rc != PLNERF_OK) return rc;
+    if (n == 0) return PLNERF_OK;
+    const TrainLayout lay = lay_out_train(net, n, planes_of(precision));
+    if (!rows || !out || !saved || ((uintptr_t)saved % PLNERF_GENERIC_WORKSPACE_ALIGN) != 0 || saved_bytes < lay.saved_bytes)
+        return PLNERF_EINVAL;
+    rc = check_grids(net, n, net.s->n_skips > 0 || net.s->use_viewdirs);
+    if (rc != PLNERF_OK) return rc;
+    unsigned char* sv = static_cast<unsigned char*>(saved);
+    auto place = [&](const int l) {      // every layer's output in a place of its own: the backward reads them all
+        unsigned* gate = lay.gate[l] == TrainLayout::NONE ? nullptr : reinterpret_cast<unsigned*>(sv + lay.gate[l]);
+        if (lay.cat[l] != TrainLayout::NONE)
+            return Place{sv + lay.cat[l], l == net.feature() ? lay.ld_cat_view : lay.ld_cat_trunk, gate};
+        return Place{sv + lay.act[l], 0, gate};
+    };
+    return run_layers(net, params, rows, ld_rows, n, precision, sv, place, out, ld_out, reinterpret_cast<unsigned*>(status),
+                      (hipStream_t)stream);
 }

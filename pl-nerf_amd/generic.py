@@ -41,6 +41,15 @@ _HALF = ("f16x3", "f16")      # IEEE-half elements: the backward entries are han
 # without HONOUR_PRECISION, or in an fp32 network, or whenever autograd records: no effect.  Read at every forward.
 CHAIN_INFERENCE = False
 
+# Opt-in, on top of HONOUR_PRECISION and HONOUR_PRECISION_BACKWARD: a TRAINING forward (grad mode on, a parameter that
+# requires grad, rows that do not) is ONE plnerf_generic_train_fwd call and its backward ONE plnerf_generic_train_bwd call,
+# wrapped in one autograd.Function for the whole network: the forward keeps every layer's output as the 16-bit planes it
+# produces (plus one gate bit per element) in a state allocated per call, and the backward reads those planes instead of
+# splitting fp32 activations again.  Outputs, gradients and status bits are the layered 16-bit route's bit for bit.  Off (the
+# default), or without either of the two switches above, or in an fp32 network, or with rows that require grad (pose or input
+# gradients): no effect -- the layered route runs.  Read at every forward.
+CHAIN_TRAINING = False
+
 
 def honours(net):
     """True when `net`'s forward through this route runs in its own 16-bit precision (and has a range status word)."""
@@ -200,32 +209,60 @@ def chains(net, rows):
         return False
     if torch.is_grad_enabled() and (rows.requires_grad or any(p.requires_grad for p in net.parameters())):
         return False
-    live = _live_skips(net)
-    return len(live) <= L.GENERIC_MAX_SKIPS and net.D - 1 not in live
+    return _describable(net)
+
+
+def chains_training(net, rows):
+    """True when forward(net, rows) takes the one-call training entries: CHAIN_TRAINING on a network that honours its precision
+    in both directions, a forward that autograd records for the parameters alone, and a shape chains() accepts."""
+    if not (CHAIN_TRAINING and HONOUR_PRECISION_BACKWARD and honours(net)):
+        return False
+    if not torch.is_grad_enabled() or rows.requires_grad or not any(p.requires_grad for p in net.parameters()):
+        return False
+    return _describable(net)
 
 
 def _live_skips(net):
     return sorted(set(k for k in net.skips if 0 <= k < net.D))
 
 
-def _chain_forward(net, rows):
-    """One plnerf_generic_fwd call: raw outputs [N, 4 or output_ch]."""
+def _describable(net):
+    """A shape plnerf_generic_shape holds and the one-call entries accept."""
+    live = _live_skips(net)
+    return len(live) <= L.GENERIC_MAX_SKIPS and net.D - 1 not in live
+
+
+def _layers(net):
+    """The modules in the order of the C entries' `params` and `grads` (the class's state_dict order)."""
+    layers = list(net.pts_linears) + list(net.views_linears)
+    return layers + ([net.feature_linear, net.alpha_linear, net.rgb_linear] if net.use_viewdirs else [net.output_linear])
+
+
+def _describe(net, rows):
+    """What the one-call entries are handed: (plnerf_generic_shape, rows as they read them, their pointer and row stride)."""
     if not rows.is_cuda:
         raise RuntimeError(f"plnerf_amd: the generic NeRF route got a tensor on {rows.device}; the HIP path needs a GPU tensor "
                            "(there is no CPU fallback)")
-    width = net.input_ch + net.view_ch
-    rows, rows_ptr, ld_rows = _rows_h16(rows.detach(), width, "rows")
-    n = rows.shape[0]
+    rows, rows_ptr, ld_rows = _rows_h16(rows.detach(), net.input_ch + net.view_ch, "rows")
     live = _live_skips(net)
     shape = L.GenericShape(D=net.D, W=net.W, input_ch=net.input_ch, view_ch=net.view_ch, use_viewdirs=int(bool(net.use_viewdirs)),
                            output_ch=0 if net.use_viewdirs else net.output_linear.out_features,
                            n_view_layers=len(net.views_linears), n_skips=len(live))
     for q, k in enumerate(live):
         shape.skips[q] = k
-    layers = list(net.pts_linears) + list(net.views_linears)
-    layers += [net.feature_linear, net.alpha_linear, net.rgb_linear] if net.use_viewdirs else [net.output_linear]
-    tensors = [t.detach().to(torch.float32).contiguous() for fc in layers for t in (fc.weight, fc.bias)]
-    params = (L.ctypes.c_void_p * len(tensors))(*[L.dptr(t, "parameter").value for t in tensors])
+    return shape, rows, rows_ptr, ld_rows
+
+
+def _param_table(tensors):
+    tensors = [t.detach().to(torch.float32).contiguous() for t in tensors]
+    return tensors, (L.ctypes.c_void_p * len(tensors))(*[L.dptr(t, "parameter").value for t in tensors])
+
+
+def _chain_forward(net, rows):
+    """One plnerf_generic_fwd call: raw outputs [N, 4 or output_ch]."""
+    shape, rows, rows_ptr, ld_rows = _describe(net, rows)
+    n = rows.shape[0]
+    tensors, params = _param_table([t for fc in _layers(net) for t in (fc.weight, fc.bias)])
     out = torch.empty(n, 4 if net.use_viewdirs else shape.output_ch, device=rows.device, dtype=torch.float32)
     if n == 0:
         return out
@@ -242,13 +279,69 @@ def _chain_forward(net, rows):
     return out
 
 
+class ChainTrainFn(torch.autograd.Function):
+    """The whole network as one node: forward = one plnerf_generic_train_fwd call whose saved state (16-bit planes, gate bits,
+    packed weights) is allocated per call and kept on ctx -- run_network calls a network once per netchunk before any backward
+    runs --; backward = one plnerf_generic_train_bwd call into one [N, K + 1] block per layer.  apply(net, shape, rows,
+    rows_ptr, ld_rows, *weights_and_biases)."""
+
+    @staticmethod
+    def forward(ctx, net, shape, rows, rows_ptr, ld_rows, *tensors):
+        n = rows.shape[0]
+        fp32, params = _param_table(tensors)      # (fp32: the tensors the table points at, alive across the call)
+        code = L.PRECISION[net.precision]
+        need = L.lib().plnerf_generic_train_saved_bytes(L.ctypes.byref(shape), n, code)
+        if need == 0 and n > 0:
+            raise RuntimeError("plnerf_amd: plnerf_generic_train_saved_bytes refused this network")
+        saved = torch.empty(max(need, 16), device=rows.device, dtype=torch.uint8)
+        out = torch.empty(n, 4 if shape.use_viewdirs else shape.output_ch, device=rows.device, dtype=torch.float32)
+        status = net.status_word()
+        L.check(L.lib().plnerf_generic_train_fwd(L.ctypes.byref(shape), params, rows_ptr, ld_rows, n, code,
+                                                 L.ctypes.c_void_p(saved.data_ptr()), saved.numel(), L.dptr(out, "out"),
+                                                 max(out.stride(0), out.shape[1]), L.dptr(status, "status", torch.int32),
+                                                 L.stream()), "plnerf_generic_train_fwd")
+        ctx.shape, ctx.rows, ctx.rows_ptr, ctx.ld_rows, ctx.code, ctx.saved, ctx.status = shape, rows, rows_ptr, ld_rows, code, saved, status
+        ctx.dims = [tuple(t.shape) for t in tensors[0::2]]      # (N, K) per layer
+        ctx.runs = [bool(shape.use_viewdirs) or not (shape.D <= q < shape.D + shape.n_view_layers) for q in range(len(ctx.dims))]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        shape, rows, code = ctx.shape, ctx.rows, ctx.code
+        n = rows.shape[0]
+        g, g_ptr, ld_g = _rows_h16(g, g.shape[1], "grad")
+        need = L.lib().plnerf_generic_train_workspace_bytes(L.ctypes.byref(shape), n, code)
+        ws = torch.empty(max(need, 16), device=g.device, dtype=torch.uint8)
+        blocks = [torch.empty(N, K + 1, device=g.device, dtype=torch.float32) if run else None
+                  for (N, K), run in zip(ctx.dims, ctx.runs)]
+        grads = (L.ctypes.c_void_p * len(blocks))(*[None if b is None else b.data_ptr() for b in blocks])
+        L.check(L.lib().plnerf_generic_train_bwd(L.ctypes.byref(shape), ctx.rows_ptr, ctx.ld_rows, n, code,
+                                                 L.ctypes.c_void_p(ctx.saved.data_ptr()), ctx.saved.numel(), g_ptr, ld_g, grads,
+                                                 L.ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                                 L.dptr(ctx.status, "status", torch.int32), L.stream()), "plnerf_generic_train_bwd")
+        out = []
+        for q, ((N, K), block) in enumerate(zip(ctx.dims, blocks)):
+            need_w, need_b = ctx.needs_input_grad[5 + 2 * q], ctx.needs_input_grad[6 + 2 * q]
+            out.append(block[:, :K].contiguous() if block is not None and need_w else None)
+            out.append(block[:, K].contiguous() if block is not None and need_b else None)
+        return (None, None, None, None, None, *out)
+
+
+def _chain_train_forward(net, rows):
+    """One plnerf_generic_train_fwd call under autograd: raw outputs [N, 4 or output_ch]."""
+    shape, rows, rows_ptr, ld_rows = _describe(net, rows)
+    return ChainTrainFn.apply(net, shape, rows, rows_ptr, ld_rows, *[t for fc in _layers(net) for t in (fc.weight, fc.bias)])
+
+
 def forward(net, rows):
     """The module's layers applied to embedded rows [N, input_ch + view_ch], whatever its shape: what NeRF.forward computes
     (run_nerf_helpers.py:105-128; with the camera columns and the softplus density of the depth-supervised variant,
     depth_supervised_exps/model/run_nerf_helpers.py:164-205), every nn.Linear through LinearFn -- or, with CHAIN_INFERENCE and
-    nothing for autograd to record, all of them in one plnerf_generic_fwd call."""
-    if chains(net, rows):
-        out = _chain_forward(net, rows)
+    nothing for autograd to record, all of them in one plnerf_generic_fwd call -- or, with CHAIN_TRAINING and only the
+    parameters to record for, in one plnerf_generic_train_fwd call whose backward is one plnerf_generic_train_bwd call."""
+    if chains(net, rows) or chains_training(net, rows):
+        out = _chain_forward(net, rows) if chains(net, rows) else _chain_train_forward(net, rows)
         return _softplus_density(out, 3) if net.density_activation == "softplus" else out
     # (with HONOUR_PRECISION: the network's 16-bit mode and its range status word, through every layer)
     mode = net.precision if honours(net) else "fp32"
