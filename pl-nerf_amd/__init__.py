@@ -22,6 +22,8 @@ from .render import (batchify, batchify_rays, compute_weights, compute_weights_p
                      sample_pdf_reformulation)
 from .png import read_png, write_png
 from .view import ViewRenderer, render_path_frames
+from . import anyview     # plnerf_render_view_any: frames of any pair of networks create_nerf builds, one library call each
+from .anyview import AnyViewRenderer
 from . import depthview   # plnerf_depth_render_view: the depth-supervised variant's frames, one library call each
 from .depthview import DepthViewRenderer, render_video_frames
 from . import camcode     # test-time optimisation of a held-out view's camera code (plnerf_camcode_sweep / _update)
@@ -44,5 +46,5 @@ __all__ = [
     "set_draw_source", "MeanTracker", "compute_rmse", "image_metrics", "metric_rows", "render_images_with_metrics",
     "sample_error_rows", "DepthViews", "DepthTrainStep", "ViewRenderer", "render_path_frames", "write_png", "read_png",
     "write_images_with_metrics", "write_images_with_metrics_testdist", "depthview", "DepthViewRenderer", "render_video_frames",
-    "camcode", "CameraCodeOptimizer", "optimize_camera_embedding",
+    "camcode", "CameraCodeOptimizer", "optimize_camera_embedding", "anyview", "AnyViewRenderer",
 ]

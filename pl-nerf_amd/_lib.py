@@ -496,6 +496,40 @@ for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES
                GEMM16_BWD_TABLE_SIGNATURES, GENERIC_FWD_TABLE_SIGNATURES):
     _disjoint(GENERIC_TRAIN_TABLE_SIGNATURES, _table)
 
+# ---- a ninth table, for include/experimental/plnerf_hip_anyview.h: one call = one rendered view for any pair of networks
+# create_nerf builds, each slot on the compiled trunk or outside it (plnerf_amd.anyview), and the layer-by-layer route's fp32
+# forward as one call.  Experimental, and a table of its own because the other eight are pinned to their entries.
+ANYVIEW_FUSED, ANYVIEW_CHAIN16, ANYVIEW_LAYERS32 = 0, 1, 2      # PLNERF_ANYVIEW_*: a network slot's route
+
+
+class AnyViewNet(ctypes.Structure):
+    """plnerf_anyview_net."""
+    _fields_ = [("route", c_i), ("fused", ViewNet), ("shape", GenericShape), ("params", c_f), ("precision", c_i), ("status", c_f)]
+
+
+class AnyViewIo(ctypes.Structure):
+    """plnerf_anyview_io."""
+    _fields_ = [("coarse", AnyViewNet), ("fine", AnyViewNet), ("max_net_rows", c_i), ("t_vals", c_f), ("u_vals", c_f)] + \
+               [(name, c_f) for name in VIEW_PLANES] + [("rgb8", c_f), ("depth16", c_f)]
+
+
+ANYVIEW_STRUCTS = {"plnerf_anyview_net": AnyViewNet, "plnerf_anyview_io": AnyViewIo}
+ANYVIEW_SIGNATURES = {
+    "plnerf_generic_fwd_f32_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(GenericShape), c_i]),
+    "plnerf_generic_fwd_f32": (c_i, [ctypes.POINTER(GenericShape), ctypes.POINTER(ctypes.c_void_p), c_f, _c_i64, c_i, c_f,
+                                     ctypes.c_size_t, c_f, _c_i64, c_s]),
+    "plnerf_render_view_any_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(StepConfig), ctypes.POINTER(AnyViewIo)]),
+    "plnerf_render_view_any": (c_i, [ctypes.POINTER(StepConfig), ctypes.POINTER(AnyViewIo), ctypes.POINTER(ViewArgs), c_f,
+                                     ctypes.c_size_t, c_s]),
+}
+ANYVIEW_HEADERS = (
+    ("experimental/plnerf_hip_anyview.h", ANYVIEW_SIGNATURES, ANYVIEW_STRUCTS),
+)
+ANYVIEW_TABLE_SIGNATURES = _merge(ANYVIEW_HEADERS)
+for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES, GEMM16_TABLE_SIGNATURES,
+               GEMM16_BWD_TABLE_SIGNATURES, GENERIC_FWD_TABLE_SIGNATURES, GENERIC_TRAIN_TABLE_SIGNATURES):
+    _disjoint(ANYVIEW_TABLE_SIGNATURES, _table)
+
 _lib = None
 
 
@@ -512,7 +546,8 @@ def lib():
         tools_build = os.environ.get("PLNERF_ALLOW_TOOLS_BUILD") == "1"
         for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES,
                                   **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES, **GEMM16_BWD_TABLE_SIGNATURES,
-                                  **GENERIC_FWD_TABLE_SIGNATURES, **GENERIC_TRAIN_TABLE_SIGNATURES}.items():
+                                  **GENERIC_FWD_TABLE_SIGNATURES, **GENERIC_TRAIN_TABLE_SIGNATURES,
+                                  **ANYVIEW_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -170,12 +170,9 @@ struct Carver {
 
 // ---- the stages ----
 
-// one network over a pass's K samples per ray, then that pass's density noise (counter stream `noise_stream`)
-static inline int network(const Pass& ps, const Rays& r, const void* packed, const Samples& s, int K, uint32_t noise_stream,
-                          plnerf_stream_t stream) {
+// a pass's density noise over its K samples per ray (counter stream `noise_stream`): behind the network, whichever ran
+static inline int density_noise(const Pass& ps, const Samples& s, int K, uint32_t noise_stream, plnerf_stream_t stream) {
     int rc;
-    STEP_OK(plnerf_mlp_fwd(packed, ps.precision, s.pts, r.viewdirs, nullptr, ps.input_ch, ps.input_ch_views, ps.R * K, K,
-                           ps.input_scale, ps.density_beta, s.raw, s.saved, ps.fwd_kernel, stream));
     if (s.noise) {
         STEP_OK(plnerf_normal(ps.seed, noise_stream, ps.step, ps.ray_id0, ps.R, K, s.noise, stream));
         if (ps.raw_noise_std != 1.0f)
@@ -184,17 +181,28 @@ static inline int network(const Pass& ps, const Rays& r, const void* packed, con
     return PLNERF_OK;
 }
 
+// one network of the compiled trunk over a pass's K samples per ray, then that pass's density noise
+static inline int network(const Pass& ps, const Rays& r, const void* packed, const Samples& s, int K, uint32_t noise_stream,
+                          plnerf_stream_t stream) {
+    int rc;
+    STEP_OK(plnerf_mlp_fwd(packed, ps.precision, s.pts, r.viewdirs, nullptr, ps.input_ch, ps.input_ch_views, ps.R * K, K,
+                           ps.input_scale, ps.density_beta, s.raw, s.saved, ps.fwd_kernel, stream));
+    return density_noise(ps, s, K, noise_stream, stream);
+}
+
 // The forward up to the fine network's raw output and noise: coarse samples -> coarse network -> coarse epilogue (the coarse
 // maps, the fine pass's depths and points) -> fine network.  r.o / r.d: the rays the samples lie on (the NDC ones under
-// ndc; r.viewdirs stay the camera-space rays').
-static inline int forward(const Pass& ps, const Rays& r, const void* packed_c, const void* packed_f, const Samples& c,
-                          const Samples& f, const CoarseMaps& m, plnerf_stream_t stream) {
+// ndc; r.viewdirs stay the camera-space rays').  net_c, net_f: the network stage of either pass, (samples, K, noise stream)
+// -> code: network() for the compiled trunk (forward() below), another body for a network outside it.
+template <class NetC, class NetF>
+static inline int forward_with(const Pass& ps, const Rays& r, NetC&& net_c, NetF&& net_f, const Samples& c, const Samples& f,
+                               const CoarseMaps& m, plnerf_stream_t stream) {
     const int R = ps.R, S = ps.S, N = ps.N;
     const float* u = ps.perturb ? nullptr : ps.u_vals;
     int rc;
     STEP_OK(plnerf_coarse_samples(r.o, r.d, r.near, r.far, ps.t_vals, nullptr, ps.seed, ps.step, ps.ray_id0, R, S, ps.lindisp,
                                   ps.perturb, c.z, c.pts, stream));
-    STEP_OK(network(ps, r, packed_c, c, S, NOISE_STREAM, stream));
+    STEP_OK(net_c(c, S, NOISE_STREAM));
     if (ps.mode == PLNERF_MODE_LINEAR)
         STEP_OK(plnerf_coarse_epilogue(c.raw, c.z, r.near, r.far, r.o, r.d, c.noise, u, 0, ps.seed, ps.step, ps.ray_id0, R, S, N,
                                        ps.color_mode, ps.white_bkgd, ps.farcolorfix, ps.zero_tol, ps.epsilon, m.rgb0, m.disp0,
@@ -203,7 +211,18 @@ static inline int forward(const Pass& ps, const Rays& r, const void* packed_c, c
         STEP_OK(plnerf_coarse_epilogue_const(c.raw, c.z, r.near, r.far, r.o, r.d, c.noise, u, 0, ps.seed, ps.step, ps.ray_id0, R, S,
                                              N, ps.white_bkgd, m.rgb0, m.disp0, m.acc0, m.depth0, nullptr, f.z, f.pts, m.z_std,
                                              stream));
-    return network(ps, r, packed_f, f, S + N, NOISE_STREAM + 1, stream);
+    return net_f(f, S + N, NOISE_STREAM + 1);
+}
+
+// ... with both networks on the compiled trunk
+static inline int forward(const Pass& ps, const Rays& r, const void* packed_c, const void* packed_f, const Samples& c,
+                          const Samples& f, const CoarseMaps& m, plnerf_stream_t stream) {
+    const auto trunk = [&](const void* packed) {
+        return [&ps, &r, packed, stream](const Samples& s, int K, uint32_t noise_stream) {
+            return network(ps, r, packed, s, K, noise_stream, stream);
+        };
+    };
+    return forward_with(ps, r, trunk(packed_c), trunk(packed_f), c, f, m, stream);
 }
 
 // The depth variant's last stage: the fine maps, and N depth hypotheses per ray drawn from the final weights with their

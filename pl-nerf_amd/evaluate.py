@@ -258,7 +258,7 @@ def _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpip
 
 def render_images_with_metrics(count, indices, images, depths, valid_depths, poses, H, W, K, lpips_alex, args,
                                render_kwargs_test, embedcam_fn=None, with_test_time_optimization=False, *,
-                               keep_images=True):
+                               keep_images=True, one_call=False):
     """run_plnerf.py:284-363: renders `count` views of `indices` (all of them in order for None, else
     np.random.choice(indices, count, replace=False)) and returns (MeanTracker of img_loss, psnr, ssim[, lpips]
     [, img_loss0, psnr0][, depth_rmse], res).  res holds CPU [count,3,H,W] / [count,1,H,W] tensors as the reference
@@ -268,10 +268,51 @@ def render_images_with_metrics(count, indices, images, depths, valid_depths, pos
     lpips_alex: a callable called as the reference calls it (clamped frame and target, [1,3,H,W], normalize=True), its
     [0][0,0,0] recorded as "lpips"; None leaves "lpips" out.  embedcam_fn and with_test_time_optimization are accepted
     and unused, as in the reference.  keep_images=False (extension) skips res (None is returned for it), and with it
-    every per-frame copy to the host: the metric rows are read back once, after the last frame."""
+    every per-frame copy to the host: the metric rows are read back once, after the last frame.
+    one_call (extension, off by default): each view comes from the one-call renderer that serves the configuration
+    (anyview.frame_renderer: view.ViewRenderer, else anyview.AnyViewRenderer; blocks of args.chunk), built once per call, its
+    planes scored in place -- where one serves it, the kwargs ask for no draws (perturb 0, no density noise: the test-time
+    settings) AND the entries' fp32 focal reciprocals are the ones torch's device kernels use for K (entry_rays_are_renders):
+    then its frames are render()'s bit for bit for device poses, and so are the rows; any other configuration keeps
+    render(), silently.  The renderer's range status words are read once, after the last view."""
     with_depth = args.dataset == "scannet"
-    return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
-                        render_kwargs_test, render, lambda img_idx: K, with_depth, lambda img_idx: None, keep_images)
+    renderer = _frame_renderer(render_kwargs_test, H, W, K, args) if one_call else None
+    if renderer is None:
+        return _score_views(count, indices, images, depths, valid_depths, poses, H, W, lpips_alex, args.chunk,
+                            render_kwargs_test, render, lambda img_idx: K, with_depth, lambda img_idx: None, keep_images)
+    host_poses = torch.as_tensor(poses).detach().to(device="cpu", dtype=torch.float32)      # (the call reads host floats)
+
+    def render_fn(H, W, K, chunk=None, c2w=None, **kwargs):
+        renderer.enqueue(c2w)
+        return renderer._result(False)
+    out = _score_views(count, indices, images, depths, valid_depths, host_poses, H, W, lpips_alex, args.chunk,
+                       render_kwargs_test, render_fn, lambda img_idx: K, with_depth, lambda img_idx: None, keep_images)
+    renderer.check_range()      # (sticky words: read once)
+    return out
+
+
+def entry_rays_are_renders(K):
+    """Are the one-call entries' rays those render() builds on the device for these intrinsics, bit for bit?  rays.get_rays
+    divides by the focal lengths as Python floats, which torch's device kernel turns into a multiply by the fp32 rounding of
+    the DOUBLE reciprocal, float(1.0 / f); the entries hold fx / fy as fp32 and multiply by 1.0f / float(f)
+    (csrc/pixel_select.h).  The two reciprocals are the same fp32 number for many focal lengths (11.3, 9.7, 1111.111) and an
+    ulp apart for others (10.77): there the frames agree to rounding only, and a loop that promises render()'s rows keeps
+    render()."""
+    return all(np.float32(1.0 / float(f)) == np.float32(1.0) / np.float32(float(f)) for f in (K[0][0], K[1][1]))
+
+
+def _frame_renderer(render_kwargs_test, H, W, K, args):
+    """The one-call renderer of an evaluation loop (blocks of args.chunk), or None when the loop stays with render(): a
+    configuration neither entry serves, kwargs that ask for draws -- the renderers' are counter-based and keyed by their
+    own (seed, step), not what render() would draw -- or focal lengths at which the entries' rays are an ulp from render()'s."""
+    from .anyview import frame_renderer
+    kw = {k: v for k, v in render_kwargs_test.items() if k not in ("near", "far", "ndc")}
+    if kw.get("perturb", 0.) > 0. or kw.get("raw_noise_std", 0.) > 0.:
+        return None
+    if not entry_rays_are_renders(K):
+        return None
+    return frame_renderer(kw, H, W, K, min(int(args.chunk), H * W), render_kwargs_test.get("near", 0.),
+                          render_kwargs_test.get("far", 1.), ndc=render_kwargs_test.get("ndc", True))
 
 
 def to8b(x):

@@ -120,21 +120,36 @@ class Renderer:
         """Everything behind a filled config: the workspace, the tables, the frame planes, both packed buffers and the io /
         args structs."""
         self.nets = (kw["network_fn"], kw["network_fine"])
-        dev = self.nets[0].param_list()[0].device
+        dev = next(self.nets[0].parameters()).device
         self.device, self.H, self.W, self.far = dev, int(H), int(W), float(far)
         self.precision = self.nets[0].precision
         self.config = cfg
-        nbytes = getattr(L.lib(), self.ENTRY + "_workspace_bytes")(ctypes.byref(cfg))
+        io = self.io = self.IO()
+        self._bind_networks()      # (ahead of the size query: an entry may size its workspace by what the slots hold)
+        nbytes = self._workspace_bytes()
         if nbytes == 0:
             raise ValueError(f"{type(self).__name__}: {self.ENTRY} refuses this configuration; use {self.FALLBACK}")
         self.workspace, self.workspace_bytes = aligned_workspace(nbytes, dev), nbytes
-        io = self.io = self.IO()
         self.t_vals, self.u_vals = tables(cfg, io, dev)
         n = self.H * self.W
         self.planes = {name: torch.empty((n, 3) if name in ("rgb", "rgb0") else (n,), device=dev) for name in L.VIEW_PLANES}
         self.rgb8 = torch.empty(n, 3, device=dev, dtype=torch.uint8)
         self.depth16 = torch.empty(n, device=dev, dtype=torch.int16)      # (uint16 bit patterns: depth / far)
-        # the renderer's own packed buffers (zeroed once: the kernels only ever OR into the status word)
+        for name in L.VIEW_PLANES:
+            setattr(io, name, self.planes[name].data_ptr())
+        self.args = self.ARGS()
+        self.args.pack_weights = 1
+        self.args.depth16_scale = float(np.float32(1.0) / np.float32(far))
+        self._refs = (ctypes.byref(cfg), ctypes.byref(io), ctypes.byref(self.args), ctypes.c_void_p(self.workspace.data_ptr()))
+
+    def _workspace_bytes(self):
+        """The entry's size query (0: the configuration is refused)."""
+        return getattr(L.lib(), self.ENTRY + "_workspace_bytes")(ctypes.byref(self.config))
+
+    def _bind_networks(self):
+        """Both networks into the io struct: two networks of the compiled trunk, their 24 parameter tensors each and the
+        renderer's own packed buffers (zeroed once: the kernels only ever OR into the status word)."""
+        cfg, io, dev = self.config, self.io, self.device
         packed_bytes = L.lib().plnerf_mlp_packed_bytes(cfg.precision)
         self.packed = tuple(torch.zeros(packed_bytes // 4, device=dev, dtype=torch.float32) for _ in range(2))
         self._status_off = L.lib().plnerf_mlp_status_offset(cfg.precision) // 4
@@ -143,12 +158,6 @@ class Renderer:
             for k, p in enumerate(params):
                 io_net.params[k] = L.dptr(p, f"params[{k}]").value
             io_net.packed = packed.data_ptr()
-        for name in L.VIEW_PLANES:
-            setattr(io, name, self.planes[name].data_ptr())
-        self.args = self.ARGS()
-        self.args.pack_weights = 1
-        self.args.depth16_scale = float(np.float32(1.0) / np.float32(far))
-        self._refs = (ctypes.byref(cfg), ctypes.byref(io), ctypes.byref(self.args), ctypes.c_void_p(self.workspace.data_ptr()))
 
     def current(self):
         """Do the parameter addresses the structs hold still belong to the live networks (a .to() or a precision change
@@ -224,7 +233,8 @@ class Renderer:
                 for key, src in copies:
                     s[key].copy_(src, non_blocking=True)
                 for k, word in enumerate(self.status_words()):
-                    s["status"][k:k + 1].copy_(word, non_blocking=True)
+                    if word is not None:      # (a network without a status word: its entry of the pair stays 0)
+                        s["status"][k:k + 1].copy_(word, non_blocking=True)
                 s["done"].record()
                 if i > 0:
                     done(i - 1)

@@ -9,8 +9,10 @@ call: it packs both networks' weights, walks the view in blocks of `chunk` pixel
 device.  What it computes is what render() computes under functional.DrawSource(seed, 0, step) for the same pose GIVEN AS A
 DEVICE TENSOR, bit for bit: render() builds its rays with rays.get_rays where the pose lives, and the call's rays are the
 device's evaluation of that expression.  (For a host pose render() takes the host's get_rays, whose directions differ from
-the device's by an ulp; the frames then agree to rounding, not bit for bit.)  Configurations outside the call (supported())
-stay with render().
+the device's by an ulp; the frames then agree to rounding, not bit for bit.  The same holds for intrinsics whose focal lengths'
+fp32 reciprocal 1.0f / float(f), which the call's rays multiply by, is not float(1.0 / f), which torch's device kernels multiply
+by when get_rays divides by the Python float: 11.3, 9.7 and 1111.111 are one number either way, 10.77 is an ulp apart.
+evaluate.entry_rays_are_renders(K) says which kind K is.)  Configurations outside the call (supported()) stay with render().
 
 `render_path_frames` is render_path (run_plnerf.py:178-216) on that route, writing '{:03d}.png' per frame when asked to.
 """
@@ -22,7 +24,7 @@ import torch
 from . import _lib as L
 from .onecall import Renderer, fill_pinhole, fill_sampling, refusal_head
 from .png import write_png
-from .render import _fusable
+from .render import MAX_ROWS_PER_LAUNCH, _fusable
 
 
 class ViewRenderer(Renderer):
@@ -83,11 +85,15 @@ def depth16_numpy(depth16):
     return depth16.cpu().numpy().view(np.uint16)
 
 
-def render_path_frames(render_poses, hwf, K, chunk, render_kwargs, savedir=None, render_factor=0, seed=0):
-    """run_plnerf.py:178-216 through plnerf_render_view: one library call per pose; returns (rgbs [n,H,W,3], disps [n,H,W])
+def render_path_frames(render_poses, hwf, K, chunk, render_kwargs, savedir=None, render_factor=0, seed=0,
+                       max_net_rows=MAX_ROWS_PER_LAUNCH):
+    """run_plnerf.py:178-216 through plnerf_render_view -- or, for a pair of networks that entry does not serve (one outside
+    the fused trunk), through plnerf_render_view_any (anyview.AnyViewRenderer; max_net_rows bounds the rows one call of such
+    a network takes, and with them the workspace) --: one library call per pose; returns (rgbs [n,H,W,3], disps [n,H,W])
     as numpy arrays, as render_path does.  Frame i draws under (seed, step = i): it is, bit for bit, what render() gives for
-    that pose as a device tensor under DrawSource(seed, 0, i) (render_path under torch's own generator draws other numbers,
-    and for host poses builds its rays with the host's arithmetic, an ulp away).  With `savedir`, frame i is also written as
+    that pose as a device tensor under DrawSource(seed, 0, i), for focal lengths as the module docstring describes them
+    (render_path under torch's own generator draws other numbers, and for host poses builds its rays with the host's
+    arithmetic, an ulp away).  With `savedir`, frame i is also written as
     '{:03d}.png' of to8b(rgb): quantised on the device and copied to pinned host memory without blocking, two buffers deep,
     so encoding frame i overlaps rendering frame i + 1.  render_kwargs carries near / far / ndc as render() takes them."""
     H, W, focal = hwf
@@ -96,7 +102,10 @@ def render_path_frames(render_poses, hwf, K, chunk, render_kwargs, savedir=None,
     H, W = int(H), int(W)
     kw = dict(render_kwargs)
     near, far, ndc = kw.pop("near", 0.), kw.pop("far", 1.), kw.pop("ndc", True)
-    renderer = ViewRenderer(kw, H, W, K, chunk, near, far, ndc=ndc, seed=seed)
+    from .anyview import frame_renderer      # (imported here: that module stands on this one)
+    renderer = frame_renderer(kw, H, W, K, chunk, near, far, ndc=ndc, seed=seed, max_net_rows=max_net_rows)
+    if renderer is None:      # (neither entry serves it: ViewRenderer's ValueError, as before)
+        renderer = ViewRenderer(kw, H, W, K, chunk, near, far, ndc=ndc, seed=seed)
     n = len(render_poses)
     rgbs, disps = np.empty((n, H, W, 3), dtype=np.float32), np.empty((n, H, W), dtype=np.float32)
     if n == 0:
