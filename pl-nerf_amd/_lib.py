@@ -530,6 +530,33 @@ for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES
                GEMM16_BWD_TABLE_SIGNATURES, GENERIC_FWD_TABLE_SIGNATURES, GENERIC_TRAIN_TABLE_SIGNATURES):
     _disjoint(ANYVIEW_TABLE_SIGNATURES, _table)
 
+# ---- a tenth table, for include/experimental/plnerf_hip_unique.h: the fine pass's MLP forward over the rows it needs (runs of
+# bit-identical rows are evaluated at their two ends), the fold of the upstream gradient onto those rows, the workspace's layout
+# and the host-side predicate.  Experimental, and a table of its own because the other nine are pinned to their entries.
+
+
+class UniqueLayout(ctypes.Structure):
+    """plnerf_unique_layout: byte offsets inside the workspace (n_absmax: a count)."""
+    _fields_ = [(name, ctypes.c_size_t) for name in ("words", "rows_u", "src", "pts_u", "dirs_u", "raw_u", "g_raw_u", "absmax",
+                                                     "n_absmax", "total")]
+
+
+UNIQUE_STRUCTS = {"plnerf_unique_layout": UniqueLayout}
+UNIQUE_SIGNATURES = {
+    "plnerf_mlp_unique_workspace_bytes": (ctypes.c_size_t, [c_i]),
+    "plnerf_mlp_unique_layout": (c_i, [c_i, ctypes.POINTER(UniqueLayout)]),
+    "plnerf_mlp_fwd_unique_served": (c_i, [c_i] * 6),
+    "plnerf_mlp_fwd_unique": (c_i, [c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_fl, c_fl, c_f, c_f, c_i, c_f, c_s]),
+    "plnerf_mlp_unique_fold": (c_i, [c_f, c_i, c_f, c_s]),
+}
+UNIQUE_HEADERS = (
+    ("experimental/plnerf_hip_unique.h", UNIQUE_SIGNATURES, UNIQUE_STRUCTS),
+)
+UNIQUE_TABLE_SIGNATURES = _merge(UNIQUE_HEADERS)
+for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES, GEMM16_TABLE_SIGNATURES,
+               GEMM16_BWD_TABLE_SIGNATURES, GENERIC_FWD_TABLE_SIGNATURES, GENERIC_TRAIN_TABLE_SIGNATURES, ANYVIEW_TABLE_SIGNATURES):
+    _disjoint(UNIQUE_TABLE_SIGNATURES, _table)
+
 _lib = None
 
 
@@ -547,7 +574,7 @@ def lib():
         for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES,
                                   **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES, **GEMM16_BWD_TABLE_SIGNATURES,
                                   **GENERIC_FWD_TABLE_SIGNATURES, **GENERIC_TRAIN_TABLE_SIGNATURES,
-                                  **ANYVIEW_TABLE_SIGNATURES}.items():
+                                  **ANYVIEW_TABLE_SIGNATURES, **UNIQUE_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

@@ -9,6 +9,8 @@
 #include "mlp_fwd_route.h"
 #include "mlp_internal.h"
 #include "mlp_layout.h"
+#include "mlp_unique_plan.h"
+#include "../../include/experimental/plnerf_hip_unique.h"
 
 using namespace plnerf;
 
@@ -226,6 +228,64 @@ extern "C" int plnerf_mlp_input_grad(const float* const* params, int precision, 
     const unsigned* live = impl::bwd_compact(n_rows) ? (const unsigned*)(ws + lo.partials) : nullptr;
     return impl::input_grad(params, n_rows, ws + lo.dz, (const unsigned*)(ws + lo.gmax), true, input_ch, input_ch_views, g_embedded,
                             live, (hipStream_t)stream);
+}
+
+// ---- include/experimental/plnerf_hip_unique.h: the fine pass's forward over the rows it needs (mlp_unique_plan.h) ----
+static_assert(sizeof(plnerf_unique_layout) == 10 * sizeof(size_t), "");
+
+extern "C" size_t plnerf_mlp_unique_workspace_bytes(int n_rows) { return n_rows < 1 ? 0 : uniq::workspace((size_t)n_rows).total; }
+
+extern "C" int plnerf_mlp_unique_layout(int n_rows, plnerf_unique_layout* layout) {
+    if (!layout || n_rows < 1) return PLNERF_EINVAL;
+    const uniq::Workspace w = uniq::workspace((size_t)n_rows);
+    *layout = plnerf_unique_layout{w.words, w.rows_u, w.src, w.pts_u, w.dirs_u, w.raw_u, w.g_raw_u, w.absmax,
+                                   (size_t)uniq::blocks((size_t)n_rows), w.total};
+    return PLNERF_OK;
+}
+
+extern "C" int plnerf_mlp_fwd_unique_served(int precision, int has_embedded, int fwd_kernel, int samples_per_ray, int n_rows,
+                                            int training) {
+    if (!known(precision) || !ns_of(precision) || !kernel_arg_ok(fwd_kernel) || n_rows < 1 || samples_per_ray < 1) return 0;
+    return uniq::served(elem_of(precision), ns_of(precision), training != 0, has_embedded != 0, fwd_kernel, samples_per_ray,
+                        (size_t)n_rows, impl::bwd_compact(n_rows), impl::fwd_unique_enabled()) ? 1 : 0;
+}
+
+extern "C" int plnerf_mlp_fwd_unique(const void* packed, int precision, const float* pts, const float* viewdirs, int input_ch,
+                                     int input_ch_views, int n_rows, int samples_per_ray, float input_scale, float density_beta,
+                                     float* raw_out, void* saved, int fwd_kernel, void* workspace, plnerf_stream_t stream) {
+    if (!known(precision)) return PLNERF_ENOSYS;
+    if (!kernel_arg_ok(fwd_kernel)) return PLNERF_EINVAL;
+    if (n_rows < 0 || !geometry_ok(input_ch, input_ch_views) || !(density_beta >= 0.0f) || !(density_beta < 1e6f)) return PLNERF_EINVAL;
+    if ((input_ch - 3) % 6 != 0 || input_ch < 3 || input_ch > lay::XYZ_CH || (input_ch_views - 3) % 6 != 0 || input_ch_views < 3 ||
+        input_ch_views > lay::DIR_CH || !(input_scale > 0.0f) || !(input_scale < 1e6f))
+        return PLNERF_EINVAL;
+    if (n_rows == 0) return PLNERF_OK;
+    if (!packed || !raw_out || !aligned16(raw_out) || !pts || !viewdirs || samples_per_ray < 1) return PLNERF_EINVAL;
+    if (!workspace || ((uintptr_t)workspace & 255) != 0) return PLNERF_EINVAL;
+    if (!plnerf_mlp_fwd_unique_served(precision, 0, fwd_kernel, samples_per_ray, n_rows, saved != nullptr)) return PLNERF_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const uniq::Workspace lo = uniq::workspace((size_t)n_rows);
+    unsigned char* ws = (unsigned char*)workspace;
+    int rc = impl::unique_list(pts, viewdirs, n_rows, samples_per_ray, workspace, st);
+    if (rc) return rc;
+    // the forward over the compact rows: one direction per row, the grid and the planes' stride from n_rows, the row count
+    // from the device (a workgroup past it returns at once)
+    rc = impl::rr_fwd(elem_of(precision), packed, (const unsigned char*)packed + impl::h16_packed_bytes(ns_of(precision)),
+                      ns_of(precision), (const float*)(ws + lo.pts_u), (const float*)(ws + lo.dirs_u), nullptr, input_ch,
+                      input_ch_views, n_rows, 1, impl::FwdOpt{input_scale, density_beta}, (float*)(ws + lo.raw_u), saved,
+                      status_word(const_cast<void*>(packed), precision), st, (const unsigned*)(ws + lo.words));
+    if (rc) return rc;
+    return impl::unique_expand(n_rows, workspace, raw_out, st);
+}
+
+extern "C" int plnerf_mlp_unique_fold(const float* g_raw, int n_rows, void* workspace, plnerf_stream_t stream) {
+    if (n_rows < 1 || !g_raw || !aligned16(g_raw) || !workspace || ((uintptr_t)workspace & 255) != 0) return PLNERF_EINVAL;
+    return impl::unique_fold(g_raw, n_rows, workspace, (hipStream_t)stream);
+}
+
+bool plnerf::impl::fwd_unique_enabled() {
+    const char* e = getenv("PLNERF_FWD_UNIQUE");
+    return !(e && e[0] == '0' && e[1] == '\0');
 }
 
 // PLNERF_BWD_COMPACT=0: the dense backward (A/B measurements, the tests' dense leg).  Read at every call, so a process may

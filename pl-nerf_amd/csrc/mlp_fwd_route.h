@@ -19,6 +19,15 @@
 #define PLNERF_RR_INSTANCES_bf16(X) \
     X(bf16, 1, 0, 0) X(bf16, 2, 0, 0) X(bf16, 2, 1, 0) X(bf16, 2, 0, 1) X(bf16, 2, 1, 1)
 #define PLNERF_RR_INSTANCES(X) PLNERF_RR_INSTANCES_f16(X) PLNERF_RR_INSTANCES_bf16(X)
+// The COUNTED variants of rows above (a device-side row count, RrFwdArgs::n_dev: the unique-row forward of the split modes,
+// mlp_unique_plan.h), rows of (element, NS, SAVE); EMB is 0.  A list of its own, expanded by mlp_rr.hip and named again by
+// csrc/Makefile's RR_CNT_INST (objects mlp_rr_c_<element>_<NS>_<SAVE>.o from mlp_rr_inst.hip with -DRR_INST_CNT); the plain
+// rows and their objects are what they were.
+#define PLNERF_RR_CNT_INSTANCES_f16(X) X(f16, 2, 0) X(f16, 2, 1)
+#define PLNERF_RR_CNT_INSTANCES_bf16(X) X(bf16, 2, 0) X(bf16, 2, 1)
+#define PLNERF_RR_CNT_INSTANCES(X) PLNERF_RR_CNT_INSTANCES_f16(X) PLNERF_RR_CNT_INSTANCES_bf16(X)
+#define PLNERF_RR_CNT_LAUNCHER_(E, NS, SAVE) rr_launch_cnt_##E##_##NS##_##SAVE
+#define PLNERF_RR_CNT_LAUNCHER(E, NS, SAVE) PLNERF_RR_CNT_LAUNCHER_(E, NS, SAVE)
 // the launcher behind a row: int rr_launch_<element>_<NS>_<SAVE>_<EMB>(const RrFwdArgs&, hipStream_t)
 #define PLNERF_RR_LAUNCHER_(E, NS, SAVE, EMB) rr_launch_##E##_##NS##_##SAVE##_##EMB
 #define PLNERF_RR_LAUNCHER(E, NS, SAVE, EMB) PLNERF_RR_LAUNCHER_(E, NS, SAVE, EMB)

@@ -124,11 +124,23 @@ struct RrFwdArgs {
     int in_ch, view_ch;
     float pe_scale;         // in-kernel encoding: sin / cos(x * pe_scale * 2^k)
     float act_beta;         // > 0: sigma leaves as softplus(beta)(sigma)
+    const unsigned* n_dev;  // counted kernels (mlp_unique.hip's compact rows): the device-side row count -- a workgroup whose first
+                            //   row is at or past it returns at once; n_rows still sizes the grid and the planes.  Else nullptr.
 };
 // elem: route::ELEM_* (mlp_fwd_route.h, which lists the instantiations that exist and decides who is sent here)
 int rr_fwd(int elem, const void* packed, const void* section, int ns, const float* pts, const float* viewdirs,
            const float* embedded, int in_ch, int view_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out,
-           void* saved, unsigned* status, hipStream_t st);
+           void* saved, unsigned* status, hipStream_t st, const unsigned* n_dev = nullptr);
+
+// The fine pass's unique-row forward (mlp_unique.hip; the rule, who is served and the workspace: mlp_unique_plan.h).
+//   unique_list    the evaluated rows' list, src[] and the gathered compact inputs, into the workspace (three launches)
+//   unique_expand  raw_out[row] = raw_u[src[row]]
+//   unique_fold    the upstream gradient folded onto the compact rows, and its per-workgroup maxima
+int unique_list(const float* pts, const float* viewdirs, int n_rows, int spr, void* workspace, hipStream_t st);
+int unique_expand(int n_rows, const void* workspace, float* raw_out, hipStream_t st);
+int unique_fold(const float* g_raw, int n_rows, void* workspace, hipStream_t st);
+// PLNERF_FWD_UNIQUE=0 in the environment switches the route off (read at every call, like PLNERF_BWD_COMPACT)
+bool fwd_unique_enabled();
 
 }  // namespace impl
 }  // namespace plnerf

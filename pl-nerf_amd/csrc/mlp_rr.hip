@@ -13,10 +13,18 @@ namespace impl {
 #define RR_DECLARE(E, NS, SAVE, EMB) int PLNERF_RR_LAUNCHER(E, NS, SAVE, EMB)(const RrFwdArgs& a, hipStream_t st);
 PLNERF_RR_INSTANCES(RR_DECLARE)
 #undef RR_DECLARE
+// ... and the counted variants (PLNERF_RR_CNT_INSTANCES)
+#define RR_DECLARE(E, NS, SAVE) int PLNERF_RR_CNT_LAUNCHER(E, NS, SAVE)(const RrFwdArgs& a, hipStream_t st);
+PLNERF_RR_CNT_INSTANCES(RR_DECLARE)
+#undef RR_DECLARE
 #ifdef RR_SINGLE_TU
 #define RR_DEFINE(E, NS, SAVE, EMB) \
     int PLNERF_RR_LAUNCHER(E, NS, SAVE, EMB)(const RrFwdArgs& a, hipStream_t st) { return RR_NS::launch<NS, bool(SAVE), bool(EMB)>(a, st); }
 PLNERF_RR_PASTE(PLNERF_RR_INSTANCES_, PLNERF_RR_ELEM)(RR_DEFINE)
+#undef RR_DEFINE
+#define RR_DEFINE(E, NS, SAVE) \
+    int PLNERF_RR_CNT_LAUNCHER(E, NS, SAVE)(const RrFwdArgs& a, hipStream_t st) { return RR_NS::launch<NS, bool(SAVE), false, true>(a, st); }
+PLNERF_RR_PASTE(PLNERF_RR_CNT_INSTANCES_, PLNERF_RR_ELEM)(RR_DEFINE)
 #undef RR_DEFINE
 #endif
 
@@ -39,9 +47,17 @@ size_t rr_packed_bytes(int ns) { return (size_t)lay::FWDC_FLOATS * ns * 2; }
 // (elem: route::ELEM_*; a combination that is no row of PLNERF_RR_INSTANCES: PLNERF_EINVAL -- route::fwd_uses_rr sends none)
 int rr_fwd(int elem, const void* packed, const void* section, int ns, const float* pts, const float* viewdirs,
            const float* embedded, int in_ch, int view_ch, int n_rows, int samples_per_ray, FwdOpt opt, float* raw_out,
-           void* saved, unsigned* status, hipStream_t st) {
+           void* saved, unsigned* status, hipStream_t st, const unsigned* n_dev) {
     RrFwdArgs a{packed, section, pts, viewdirs, n_rows, samples_per_ray < 1 ? 1 : samples_per_ray, raw_out, saved,
-                status, embedded, in_ch, view_ch, opt.pe_scale, opt.act_beta};
+                status, embedded, in_ch, view_ch, opt.pe_scale, opt.act_beta, n_dev};
+    if (n_dev) {      // the counted kernels: rows of PLNERF_RR_CNT_INSTANCES, or PLNERF_EINVAL
+        if (embedded) return PLNERF_EINVAL;
+#define RR_DISPATCH(E, NS, SAVE) \
+    if (elem == route::ELEM_##E && ns == NS && (saved != nullptr) == bool(SAVE)) return PLNERF_RR_CNT_LAUNCHER(E, NS, SAVE)(a, st);
+        PLNERF_RR_CNT_INSTANCES(RR_DISPATCH)
+#undef RR_DISPATCH
+        return PLNERF_EINVAL;
+    }
 #define RR_DISPATCH(E, NS, SAVE, EMB) \
     if (elem == route::ELEM_##E && ns == NS && (saved != nullptr) == bool(SAVE) && (embedded != nullptr) == bool(EMB)) \
         return PLNERF_RR_LAUNCHER(E, NS, SAVE, EMB)(a, st);

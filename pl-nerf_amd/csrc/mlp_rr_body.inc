@@ -790,9 +790,12 @@ constexpr int HEAD_PIECES = 16;
 static_assert(HEAD_PIECES * 1024 >= (int)HEAD_BYTES && HEAD_PIECES % 4 == 0, "head block DMA");
 constexpr size_t rr_lds_bytes() { return (size_t)NSLOTS * SLOT_BYTES + (size_t)HEAD_PIECES * 1024; }
 
-template <int NS, bool SAVE, bool EMB>
+// CNT: the counted kernel (the unique-row forward's compact rows, mlp_unique.hip) -- a.n_dev points at the device-side row
+// count; everything else, the grid included, is sized by a.n_rows as in the plain kernel.
+template <int NS, bool SAVE, bool EMB, bool CNT = false>
 __global__ __launch_bounds__(RR_THREADS) void mlp_fwd_rr_kernel(FwdArgs a) {
     constexpr int RT = row_tiles(NS);
+    static_assert(!(CNT && EMB), "the counted kernel encodes pts / viewdirs itself");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef __attribute__((address_space(3))) unsigned char lds_byte;
     const unsigned lds_base = (unsigned)(uintptr_t)(lds_byte*)smem;
@@ -824,6 +827,14 @@ __global__ __launch_bounds__(RR_THREADS) void mlp_fwd_rr_kernel(FwdArgs a) {
     // The rows' six input floats first, as loads the compiler does not track (it would wait for them with vmcnt(0) and
     // drain the DMA queue behind them); then the head block and the first three units' weights, all by DMA.  One
     // counted wait below covers the inputs: they are older than every DMA piece.
+    // (counted kernel: the row count is asked for first, as a scalar load the compiler does not track either, and waited
+    // for only after the input loads are out -- their addresses are valid over the whole buffer whatever the count says.
+    // Like the input loads' registers, the count's SGPR must not be copied or spilled between the load and the wait below:
+    // nothing uses n_dev in between, and the disassembly of the four counted objects (this compiler, gfx950, the
+    // Makefile's flags) shows the loaded register untouched up to the s_waitcnt and compared right behind it -- look
+    // again after a compiler change, as for the in6 loads.)
+    unsigned n_dev = 0u;
+    if constexpr (CNT) asm volatile("s_load_dword %0, %1, 0x0" : "=s"(n_dev) : "s"(a.n_dev) : "memory");
     float in6[RT][6];
     float ev[EMB ? RT : 1][32], eu[EMB ? RT : 1][16];      // caller-embedded input: this lane's slot values
 #pragma unroll
@@ -852,6 +863,12 @@ __global__ __launch_bounds__(RR_THREADS) void mlp_fwd_rr_kernel(FwdArgs a) {
                 asm volatile("global_load_dword %0, %1, off" : "=v"(in6[rt][3 + c]) : "v"(pv + c) : "memory");
             }
         }
+    }
+    if constexpr (CNT) {
+        // a workgroup whose first row is at or past the count has no row: gone before any DMA, LDS use or barrier
+        // (uniform; the end of the program waits for the input loads in flight)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(n_dev) : : "memory");
+        if (row0 >= (int)n_dev) return;
     }
 #pragma unroll
     for (int p = 0; p < HEAD_PIECES / 4; ++p)
@@ -1007,13 +1024,14 @@ __global__ __launch_bounds__(RR_THREADS) void mlp_fwd_rr_kernel(FwdArgs a) {
     }
 }
 
-template <int NS, bool SAVE, bool EMB>
+template <int NS, bool SAVE, bool EMB, bool CNT = false>
 int launch(const FwdArgs& a, hipStream_t st) {
     const size_t lds = rr_lds_bytes();
     constexpr int ROWS = RR_ROWS * row_tiles(NS);
-    (void)hipFuncSetAttribute((const void*)mlp_fwd_rr_kernel<NS, SAVE, EMB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (CNT != (a.n_dev != nullptr)) return PLNERF_EINVAL;
+    (void)hipFuncSetAttribute((const void*)mlp_fwd_rr_kernel<NS, SAVE, EMB, CNT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
-    hipLaunchKernelGGL((mlp_fwd_rr_kernel<NS, SAVE, EMB>), dim3((a.n_rows + ROWS - 1) / ROWS), dim3(RR_THREADS), lds, st, a);
+    hipLaunchKernelGGL((mlp_fwd_rr_kernel<NS, SAVE, EMB, CNT>), dim3((a.n_rows + ROWS - 1) / ROWS), dim3(RR_THREADS), lds, st, a);
     PLNERF_CHECK_LAUNCH();
     return PLNERF_OK;
 }

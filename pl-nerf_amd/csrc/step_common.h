@@ -8,6 +8,7 @@
 #include "common.h"
 #include "../../include/plnerf_hip_step.h"
 #include "../../include/plnerf_hip_view.h"      // (plnerf_view_net; brings plnerf_hip_constepi.h)
+#include "../../include/experimental/plnerf_hip_unique.h"
 
 namespace plnerf_step {
 
@@ -78,7 +79,9 @@ struct FineMaps { float *rgb, *disp, *acc, *depth; };
 // what the depth variant's last stage writes besides the maps: see depth_last_stage
 struct HypPlanes { float *w, *tau, *T, *hyp; int64_t* inds; float *u_used, *z_std; };
 // what the backward of both networks writes and works in
-struct Backward { float *g_raw_c, *g_raw_f; uint32_t *absmax_c, *absmax_f; void *bwd_c, *bwd_f; };
+// (uniq_f: the fine pass's unique-row workspace, include/experimental/plnerf_hip_unique.h; NULL where the entry carves none
+// and, in the Backward an entry hands to backward_nets(), where this step's fine pass took the plain forward)
+struct Backward { float *g_raw_c, *g_raw_f; uint32_t *absmax_c, *absmax_f; void *bwd_c, *bwd_f; void* uniq_f; };
 // a block's planes of a view entry
 struct ViewMaps { FineMaps fine; CoarseMaps coarse; };
 
@@ -155,7 +158,8 @@ struct Carver {
     ViewMaps view_maps(size_t R) { return ViewMaps{FineMaps{nullptr, floats(R), floats(R), floats(R)}, coarse_maps(R)}; }
     // the steps' tail: d loss / d raw of either pass, max |g_raw| per group of rays, then both passes' saved activations
     // and the backward's scratch
-    Backward backward(size_t R, size_t S, size_t F, int precision, Samples* coarse, Samples* fine) {
+    // (unique: the block of the fine pass's unique-row forward behind everything else -- the NVS steps)
+    Backward backward(size_t R, size_t S, size_t F, int precision, Samples* coarse, Samples* fine, bool unique = false) {
         Backward b{};
         b.g_raw_c = floats(4 * R * S); b.g_raw_f = floats(4 * R * F);
         const size_t groups = (R + PLNERF_QUAD_RAYS_PER_GROUP - 1) / PLNERF_QUAD_RAYS_PER_GROUP;
@@ -164,6 +168,7 @@ struct Carver {
         fine->saved = take<void>(plnerf_mlp_saved_bytes((int)(R * F), precision));
         b.bwd_c = take<void>(plnerf_mlp_bwd_workspace_bytes((int)(R * S), precision));
         b.bwd_f = take<void>(plnerf_mlp_bwd_workspace_bytes((int)(R * F), precision));
+        b.uniq_f = unique ? take<void>(plnerf_mlp_unique_workspace_bytes((int)(R * F))) : nullptr;
         return b;
     }
 };
@@ -181,12 +186,28 @@ static inline int density_noise(const Pass& ps, const Samples& s, int K, uint32_
     return PLNERF_OK;
 }
 
+// Does a pass of K samples per ray take the unique-row forward (uniq_ws: its workspace, NULL = the entry has none)?  The
+// library's host-side predicate, and no density activation (the backward would want the activated output in compact order).
+// An entry asks ONCE per step, ahead of the forward, and hands forward() and backward_nets() the answer as the workspace
+// pointer -- given: the route, NULL: the plain forward -- so that the forward and the backward's fold cannot disagree (the
+// predicate reads the environment's switches at every call).
+static inline bool unique_pass(const Pass& ps, int K, bool training, const void* uniq_ws) {
+    return uniq_ws && !(ps.density_beta > 0.0f) &&
+           plnerf_mlp_fwd_unique_served(ps.precision, 0, ps.fwd_kernel, K, ps.R * K, training ? 1 : 0) != 0;
+}
+
 // one network of the compiled trunk over a pass's K samples per ray, then that pass's density noise
+// (uniq_ws: not NULL for a fine pass that takes the unique-row forward, as unique_pass() decided -- runs of bit-identical rows
+// are evaluated at their ends)
 static inline int network(const Pass& ps, const Rays& r, const void* packed, const Samples& s, int K, uint32_t noise_stream,
-                          plnerf_stream_t stream) {
+                          plnerf_stream_t stream, void* uniq_ws = nullptr) {
     int rc;
-    STEP_OK(plnerf_mlp_fwd(packed, ps.precision, s.pts, r.viewdirs, nullptr, ps.input_ch, ps.input_ch_views, ps.R * K, K,
-                           ps.input_scale, ps.density_beta, s.raw, s.saved, ps.fwd_kernel, stream));
+    if (uniq_ws)
+        STEP_OK(plnerf_mlp_fwd_unique(packed, ps.precision, s.pts, r.viewdirs, ps.input_ch, ps.input_ch_views, ps.R * K, K,
+                                      ps.input_scale, ps.density_beta, s.raw, s.saved, ps.fwd_kernel, uniq_ws, stream));
+    else
+        STEP_OK(plnerf_mlp_fwd(packed, ps.precision, s.pts, r.viewdirs, nullptr, ps.input_ch, ps.input_ch_views, ps.R * K, K,
+                               ps.input_scale, ps.density_beta, s.raw, s.saved, ps.fwd_kernel, stream));
     return density_noise(ps, s, K, noise_stream, stream);
 }
 
@@ -215,14 +236,16 @@ static inline int forward_with(const Pass& ps, const Rays& r, NetC&& net_c, NetF
 }
 
 // ... with both networks on the compiled trunk
+// (uniq_f: the fine pass's unique-row workspace where unique_pass() said yes, else NULL; the coarse pass's jittered depths
+// never repeat)
 static inline int forward(const Pass& ps, const Rays& r, const void* packed_c, const void* packed_f, const Samples& c,
-                          const Samples& f, const CoarseMaps& m, plnerf_stream_t stream) {
-    const auto trunk = [&](const void* packed) {
-        return [&ps, &r, packed, stream](const Samples& s, int K, uint32_t noise_stream) {
-            return network(ps, r, packed, s, K, noise_stream, stream);
+                          const Samples& f, const CoarseMaps& m, plnerf_stream_t stream, void* uniq_f = nullptr) {
+    const auto trunk = [&](const void* packed, void* uniq_ws) {
+        return [&ps, &r, packed, stream, uniq_ws](const Samples& s, int K, uint32_t noise_stream) {
+            return network(ps, r, packed, s, K, noise_stream, stream, uniq_ws);
         };
     };
-    return forward_with(ps, r, trunk(packed_c), trunk(packed_f), c, f, m, stream);
+    return forward_with(ps, r, trunk(packed_c, nullptr), trunk(packed_f, uniq_f), c, f, m, stream);
 }
 
 // The depth variant's last stage: the fine maps, and N depth hypotheses per ray drawn from the final weights with their
@@ -264,7 +287,19 @@ static inline int backward_nets(const Pass& ps, const Rays& r, const Samples& c,
     const void* packed[2] = {coarse->packed, fine->packed};
     const float* g_raw[2] = {b.g_raw_c, b.g_raw_f};
     const uint32_t* absmax[2] = {by_product ? b.absmax_c : nullptr, by_product ? b.absmax_f : nullptr};
-    const int n_absmax[2] = {by_product ? groups : 0, by_product ? groups : 0};
+    int n_absmax[2] = {by_product ? groups : 0, by_product ? groups : 0};
+    if (b.uniq_f) {
+        // the fine forward ran over its needed rows (the entry's one unique_pass() decision: b.uniq_f is what forward() was
+        // given): its saved planes are in compact order, and so must the gradient be -- folded, with the launch scale's
+        // candidates taken from the FOLDED gradient in place of the quadrature's (unique_pass() admits no density
+        // activation, so by_product holds here)
+        plnerf_unique_layout lo;
+        STEP_OK(plnerf_mlp_unique_layout(R * F, &lo));
+        STEP_OK(plnerf_mlp_unique_fold(b.g_raw_f, R * F, b.uniq_f, stream));
+        g_raw[1] = (const float*)((const unsigned char*)b.uniq_f + lo.g_raw_u);
+        absmax[1] = (const uint32_t*)((const unsigned char*)b.uniq_f + lo.absmax);
+        n_absmax[1] = (int)lo.n_absmax;
+    }
     const int n_rows[2] = {R * S, R * F};
     const void* saved[2] = {c.saved, f.saved};
     const int layouts[2] = {layout, layout};

@@ -49,7 +49,7 @@ Plan carve(const plnerf_step_config* c, void* workspace) {
     p.fine = w.samples(R, F, noise);
     p.maps = w.fine_maps(R);
     p.g_rgb = w.floats(3 * R); p.g_rgb0 = w.floats(3 * R);
-    p.bwd = w.backward(R, S, F, c->precision, &p.coarse, &p.fine);
+    p.bwd = w.backward(R, S, F, c->precision, &p.coarse, &p.fine, true);
     p.bytes = w.off;
     return p;
 }
@@ -154,7 +154,10 @@ int train_step_grads(const plnerf_step_config* c, const plnerf_step_io* io, cons
     // ---- both passes up to the fine network's raw output, then the last stage ----
     STEP_OK(plnerf_mlp_pack_weights(io->coarse.params, ps.precision, ps.input_ch, ps.input_ch_views, io->coarse.packed, stream));
     STEP_OK(plnerf_mlp_pack_weights(io->fine.params, ps.precision, ps.input_ch, ps.input_ch_views, io->fine.packed, stream));
-    STEP_OK(forward(ps, r, io->coarse.packed, io->fine.packed, p.coarse, p.fine, p.maps0, stream));
+    // (the fine pass's route, decided once for the forward and the backward's fold)
+    Backward bwd = p.bwd;
+    if (!unique_pass(ps, F, true, bwd.uniq_f)) bwd.uniq_f = nullptr;
+    STEP_OK(forward(ps, r, io->coarse.packed, io->fine.packed, p.coarse, p.fine, p.maps0, stream, bwd.uniq_f));
     STEP_OK(plnerf_quad_fwd(p.fine.raw, p.fine.z, r.near, r.far, r.d, p.fine.noise, R, F, mode, ps.color_mode, ps.white_bkgd,
                             ps.farcolorfix, p.maps.rgb, p.maps.disp, p.maps.acc, p.maps.depth, nullptr, nullptr, nullptr, stream));
 
@@ -166,7 +169,7 @@ int train_step_grads(const plnerf_step_config* c, const plnerf_step_io* io, cons
     STEP_OK(plnerf_quad_bwd(p.fine.raw, p.fine.z, r.near, r.far, r.d, p.fine.noise, R, F, mode, ps.color_mode, ps.white_bkgd,
                             ps.farcolorfix, p.g_rgb, nullptr, nullptr, nullptr, nullptr, nullptr, p.bwd.g_raw_f, p.bwd.absmax_f,
                             stream));
-    return backward_nets(ps, r, p.coarse, p.fine, p.g_rgb0, p.bwd, layout, &io->coarse, &io->fine, stream);
+    return backward_nets(ps, r, p.coarse, p.fine, p.g_rgb0, bwd, layout, &io->coarse, &io->fine, stream);
 }
 
 int train_step(const plnerf_step_config* c, const plnerf_step_io* io, const plnerf_step_args* a, void* workspace,

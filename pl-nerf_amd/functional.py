@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, streams, the autograd tape); every oper
 the path itself runs in libplnerf_hip.so.
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -49,6 +50,14 @@ class KernelTimer:
 
 
 KERNEL_TIMER = None
+
+# The fine pass's forward over the rows it needs (include/experimental/plnerf_hip_unique.h): after importance sampling a
+# ray's fine pass holds runs of bit-identical rows, and plnerf_mlp_fwd_unique evaluates each run at its two ends only.
+# FWD_UNIQUE mirrors PLNERF_FWD_UNIQUE (0: off; A/B runs -- a test flips the attribute).  FINE_QUERY is set by
+# render.render_rays around the FINE network query, in the style of MLP_TAPE: the coarse pass's jittered depths never
+# repeat and do not pay for a list.
+FWD_UNIQUE = os.environ.get("PLNERF_FWD_UNIQUE") != "0"
+FINE_QUERY = False
 
 
 GRAD_TAIL = 4      # floats behind a network's flat gradient (16 bytes: [0] = range status, the rest unused)
@@ -500,14 +509,26 @@ def _mlp_backward_launch(ctxs, g_raws, absmax_log=None):
     offs = [sum(sizes[:j]) for j in range(n)]
     for j, (c, g_raw) in enumerate(zip(ctxs, g_raws)):
         g = _f32c(g_raw)
-        gs.append(g)
         # (the producer's by-product: the word of the plnerf_quad_bwd launch that wrote exactly this buffer -- and nothing has
         # written to it since: if `raw` ever gets a second consumer, autograd accumulates the second gradient INTO the first
         # one's buffer (same pointer, version counter bumped), and the maximum of the first alone would understate the scale
         # of the sum; the absmax pass then runs instead.  ADVICE r05)
         am = next((v for t, ver, v in (absmax_log or ())
                    if t.data_ptr() == g.data_ptr() and t.numel() == g.numel() and t._version == ver), None)
-        absmax.append(am if (am is not None and c.beta == 0.0 and g.numel() == 4 * c.n_rows) else None)
+        am = am if (am is not None and c.beta == 0.0 and g.numel() == 4 * c.n_rows) else None
+        uws = getattr(c, "unique_ws", None)
+        if uws is not None:
+            # a unique-row forward (MlpFn.forward): the gradient folded onto the evaluated rows, in the compact order of the
+            # saved planes.  Where the quadrature left its by-product, the launch scale's candidates are the fold's own
+            # maxima -- of the FOLDED gradient -- in its place; where it did not, the backward's own pass runs, as ever
+            _expect(g.numel() == 4 * c.n_rows, "the upstream gradient of a unique-row forward covers every row")
+            lo = L.UniqueLayout()
+            L.check(L.lib().plnerf_mlp_unique_layout(c.n_rows, ctypes.byref(lo)), "plnerf_mlp_unique_layout")
+            L.check(L.lib().plnerf_mlp_unique_fold(L.dptr(g, "g_raw"), c.n_rows, L.dptr(uws), L.stream()), "plnerf_mlp_unique_fold")
+            g = uws[lo.g_raw_u // 4:lo.g_raw_u // 4 + 4 * c.n_rows]
+            am = None if am is None else uws.view(torch.int32)[lo.absmax // 4:lo.absmax // 4 + lo.n_absmax]
+        gs.append(g)
+        absmax.append(am)
         wss.append(torch.empty(L.lib().plnerf_mlp_bwd_workspace_bytes(c.n_rows, c.prec) // 4, device=dev, dtype=torch.float32))
         grads, full = _grad_buffer(c, dev, block=None if block is None else block[offs[j]:offs[j] + sizes[j]])
         grads_all.append(grads)
@@ -562,7 +583,7 @@ def mlp_backward_multi(outs, g_raws, absmax_log=None):
     if timer is not None:
         ev[1].record()
     for c in ctxs:
-        c.saved_acts = None
+        c.saved_acts = c.unique_ws = None
     return grads_all
 
 
@@ -609,13 +630,27 @@ class MlpFn(torch.autograd.Function):
         if timer is not None:
             ev = timer.bracket(f"mlp_fwd[{n_rows}]")
             ev[0].record()
-        L.check(L.lib().plnerf_mlp_fwd(
-            L.dptr(packed, "packed"), prec, L.dptr(pts_c, "pts"), L.dptr(vd_c, "viewdirs"),
-            L.dptr(emb_c, "embedded"), int(net.input_ch), int(net.hip_view_ch), n_rows, int(spr), pe_scale, beta,
-            L.dptr(raw), L.dptr(saved), L.FWD_KERNEL, L.stream()), "plnerf_mlp_fwd")
+        # the fine query over its needed rows: the marked call, the kernel's own encoding, no input or camera gradient, and
+        # the library's predicate (route, rows per ray, the backward over live rows) -- else the plain forward
+        unique_ws = None
+        if (FINE_QUERY and FWD_UNIQUE and emb_c is None and not in_grad and cam is None and beta == 0.0 and n_rows > 0 and
+                L.lib().plnerf_mlp_fwd_unique_served(prec, 0, L.FWD_KERNEL, int(spr), n_rows, int(saved is not None))):
+            unique_ws = torch.empty(L.lib().plnerf_mlp_unique_workspace_bytes(n_rows) // 4, device=dev, dtype=torch.float32)
+            L.check(L.lib().plnerf_mlp_fwd_unique(
+                L.dptr(packed, "packed"), prec, L.dptr(pts_c, "pts"), L.dptr(vd_c, "viewdirs"), int(net.input_ch),
+                int(net.hip_view_ch), n_rows, int(spr), pe_scale, beta, L.dptr(raw), L.dptr(saved), L.FWD_KERNEL,
+                L.dptr(unique_ws), L.stream()), "plnerf_mlp_fwd_unique")
+        else:
+            L.check(L.lib().plnerf_mlp_fwd(
+                L.dptr(packed, "packed"), prec, L.dptr(pts_c, "pts"), L.dptr(vd_c, "viewdirs"),
+                L.dptr(emb_c, "embedded"), int(net.input_ch), int(net.hip_view_ch), n_rows, int(spr), pe_scale, beta,
+                L.dptr(raw), L.dptr(saved), L.FWD_KERNEL, L.stream()), "plnerf_mlp_fwd")
         if timer is not None:
             ev[1].record()
         ctx.net, ctx.prec, ctx.n_rows = net, prec, n_rows
+        # (a unique-row forward: `saved` holds the evaluated rows' planes in compact order, and the backward folds the
+        # upstream gradient onto them first -- _mlp_backward_launch)
+        ctx.unique_ws = unique_ws if saved is not None else None
         ctx.saved_layout = L.lib().plnerf_mlp_saved_layout(prec, int(emb_c is not None), L.FWD_KERNEL)
         ctx.saved_acts = saved
         ctx.packed = packed
@@ -678,7 +713,7 @@ class MlpFn(torch.autograd.Function):
                     g_dir = g_rows[:, xyz_ch:].reshape(-1, ctx.in_spr, dir_ch).sum(1)
                     g_vd = encoding_vjp(ctx.in_vd, g_dir, ctx.in_scale)
             ctx.in_params = ctx.in_pts = ctx.in_vd = None
-        ctx.saved_acts = None
+        ctx.saved_acts = ctx.unique_ws = None
         return (g_pts, g_vd, g_embedded, g_cam) + (None,) * 3 + tuple(grads)
 
 

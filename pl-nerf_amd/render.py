@@ -319,7 +319,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, mode, color_
 
     if N_importance > 0:
         run_fn = network_fn if network_fine is None else network_fine
-        raw = network_query_fn(pts, viewdirs, run_fn)
+        # (the fine query: after the merge sort its rows hold runs of equal depths -- functional.FINE_QUERY lets MlpFn take
+        # the unique-row forward where the library serves it)
+        Fn.FINE_QUERY = True
+        try:
+            raw = network_query_fn(pts, viewdirs, run_fn)
+        finally:
+            Fn.FINE_QUERY = False
         rgb_map, disp_map, acc_map, weights, depth_map, tau, T = raw2outputs(
             raw, z_vals, near, far, rays_d, mode, color_mode, raw_noise_std, pytest=pytest,
             white_bkgd=white_bkgd, farcolorfix=farcolorfix)
