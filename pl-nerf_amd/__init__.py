@@ -28,6 +28,8 @@ from . import depthview   # plnerf_depth_render_view: the depth-supervised varia
 from .depthview import DepthViewRenderer, render_video_frames
 from . import camcode     # test-time optimisation of a held-out view's camera code (plnerf_camcode_sweep / _update)
 from .camcode import CameraCodeOptimizer, optimize_camera_embedding
+from . import mesh        # mesh extraction: plnerf_density_grid (one call = extract_fields) and marching cubes on the device
+from .mesh import (extract_fields, extract_geometry, extract_iso_level, keep_components, marching_cubes, read_ply, write_ply)
 
 
 def library_path():
@@ -47,4 +49,5 @@ __all__ = [
     "sample_error_rows", "DepthViews", "DepthTrainStep", "ViewRenderer", "render_path_frames", "write_png", "read_png",
     "write_images_with_metrics", "write_images_with_metrics_testdist", "depthview", "DepthViewRenderer", "render_video_frames",
     "camcode", "CameraCodeOptimizer", "optimize_camera_embedding", "anyview", "AnyViewRenderer",
+    "mesh", "extract_fields", "extract_geometry", "extract_iso_level", "marching_cubes", "keep_components", "write_ply", "read_ply",
 ]

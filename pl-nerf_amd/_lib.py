@@ -557,6 +557,29 @@ for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES
                GEMM16_BWD_TABLE_SIGNATURES, GENERIC_FWD_TABLE_SIGNATURES, GENERIC_TRAIN_TABLE_SIGNATURES, ANYVIEW_TABLE_SIGNATURES):
     _disjoint(UNIQUE_TABLE_SIGNATURES, _table)
 
+# ---- an eleventh table, for include/experimental/plnerf_hip_mesh.h: mesh extraction (plnerf_amd.mesh) -- one network's density on
+# a lattice in one call (on the ninth table's slot struct) and indexed marching cubes of a device field.  Experimental, and a
+# table of its own because the other ten are pinned to their entries.
+GRID_STATS = 4                             # PLNERF_GRID_STATS: fp64 values of a stats row, columns PLNERF_GRID_*
+GRID_MIN, GRID_MAX, GRID_SUM, GRID_SUMSQ = range(GRID_STATS)
+MC_MAX_POINTS = 1 << 30                    # lattice points of either entry
+MC_COUNT_SATURATED = 0xFFFFFFFF            # a count of plnerf_mc_count that does not fit its word
+MESH_SIGNATURES = {
+    "plnerf_density_grid_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(AnyViewNet)] + [c_i] * 5),
+    "plnerf_density_grid": (c_i, [ctypes.POINTER(AnyViewNet)] + [c_i] * 4 + [c_f] * 3 + [c_i, c_i, c_f, c_f, c_f, ctypes.c_size_t, c_s]),
+    "plnerf_mc_workspace_bytes": (ctypes.c_size_t, [c_i] * 3),
+    "plnerf_mc_count": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_double, c_f, ctypes.c_size_t, c_f, c_s]),
+    "plnerf_mc_emit": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_double, c_f, ctypes.c_size_t, c_f, _c_i64, c_f, _c_i64, c_s]),
+}
+MESH_HEADERS = (
+    ("experimental/plnerf_hip_mesh.h", MESH_SIGNATURES, {}),
+)
+MESH_TABLE_SIGNATURES = _merge(MESH_HEADERS)
+for _table in (ALL_SIGNATURES, EXPERIMENTAL_SIGNATURES, CAMCODE_TABLE_SIGNATURES, DPSTEP_TABLE_SIGNATURES, GEMM16_TABLE_SIGNATURES,
+               GEMM16_BWD_TABLE_SIGNATURES, GENERIC_FWD_TABLE_SIGNATURES, GENERIC_TRAIN_TABLE_SIGNATURES, ANYVIEW_TABLE_SIGNATURES,
+               UNIQUE_TABLE_SIGNATURES):
+    _disjoint(MESH_TABLE_SIGNATURES, _table)
+
 _lib = None
 
 
@@ -574,7 +597,7 @@ def lib():
         for name, (res, args) in {**ALL_SIGNATURES, **EXPERIMENTAL_SIGNATURES, **CAMCODE_TABLE_SIGNATURES,
                                   **DPSTEP_TABLE_SIGNATURES, **GEMM16_TABLE_SIGNATURES, **GEMM16_BWD_TABLE_SIGNATURES,
                                   **GENERIC_FWD_TABLE_SIGNATURES, **GENERIC_TRAIN_TABLE_SIGNATURES,
-                                  **ANYVIEW_TABLE_SIGNATURES, **UNIQUE_TABLE_SIGNATURES}.items():
+                                  **ANYVIEW_TABLE_SIGNATURES, **UNIQUE_TABLE_SIGNATURES, **MESH_TABLE_SIGNATURES}.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if tools_build:      # (tools/ab.sh against a library of an earlier commit: entry points it lacks stay unbound)

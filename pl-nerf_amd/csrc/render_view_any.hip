@@ -5,19 +5,11 @@
 // plnerf_generic_fwd_f32), into the pass's raw outputs; the pass's density noise follows either.  Rows are independent in
 // both routes, so where a pass is cut does not show in the frame.  No kernel of the path is written here.
 #include "step_common.h"
-#include "generic_net.h"
-#include "../../include/experimental/plnerf_hip_anyview.h"
+#include "anyview_slot.h"
 
 namespace {
 
 using namespace plnerf_step;
-
-constexpr int MAX_FREQS = 16;      // plnerf_embed_rows' limit on either encoding
-
-// a slot's encoding: frequency bands of the positions and of the directions, columns of an embedded row
-struct Encoding { int L, M, cols; };
-
-bool generic(const plnerf_anyview_net& n) { return n.route == PLNERF_ANYVIEW_CHAIN16 || n.route == PLNERF_ANYVIEW_LAYERS32; }
 
 // The workspace: plnerf_render_view's blocks in its order (so that two FUSED slots need exactly its bytes), then the embedded
 // rows and the network workspace of one sub-block.
@@ -32,12 +24,6 @@ struct Plan {
     int net_rows;
     size_t bytes;
 };
-
-size_t net_workspace_bytes(const plnerf_anyview_net& n, int rows) {
-    if (n.route == PLNERF_ANYVIEW_CHAIN16) return plnerf_generic_fwd_workspace_bytes(&n.shape, rows, n.precision);
-    if (n.route == PLNERF_ANYVIEW_LAYERS32) return plnerf_generic_fwd_f32_workspace_bytes(&n.shape, rows);
-    return 0;
-}
 
 Plan carve(const plnerf_step_config* c, const plnerf_anyview_io* io, int cols, void* workspace) {
     const size_t R = (size_t)c->max_rays, S = (size_t)c->n_samples, F = S + (size_t)c->n_importance;
@@ -63,31 +49,6 @@ Plan carve(const plnerf_step_config* c, const plnerf_anyview_io* io, int cols, v
 
 Pass pass_of(const plnerf_step_config* c, int R, int ray_id0, uint32_t step, const float* t_vals, const float* u_vals) {
     return make_pass(*c, c->mode, c->farcolorfix, 1.0f, 0.0f, R, ray_id0, step, t_vals, u_vals);
-}
-
-// a generic slot's shape as far as it can be judged without its pointers: PLNERF_OK and its encoding, or the refusal
-int check_shape(const plnerf_anyview_net& n, int net_rows, Encoding& e) {
-    const plnerf_generic_shape& s = n.shape;
-    if (!s.use_viewdirs) return PLNERF_EINVAL;
-    if (s.input_ch < 3 || (s.input_ch - 3) % 6 != 0 || s.view_ch < 3 || (s.view_ch - 3) % 6 != 0) return PLNERF_EINVAL;
-    e = Encoding{(s.input_ch - 3) / 6, (s.view_ch - 3) / 6, s.input_ch + s.view_ch};
-    if (e.L > MAX_FREQS || e.M > MAX_FREQS) return PLNERF_EINVAL;
-    // the shape's (and the precision's) own refusals, in the order the entry looks: describe() (generic_net.h; the fp32 loop
-    // describes under a two-plane precision, which changes nothing about a shape), then whatever else the size query refuses
-    // -- an empty call of the entry, which launches nothing, says with which code
-    Net net;
-    int rc = describe(&s, n.route == PLNERF_ANYVIEW_CHAIN16 ? n.precision : PLNERF_PREC_BF16X3, net);
-    if (rc) return rc;
-    if (net_workspace_bytes(n, 1) == 0) {
-        rc = n.route == PLNERF_ANYVIEW_CHAIN16
-                 ? plnerf_generic_fwd(&s, nullptr, nullptr, e.cols, 0, n.precision, nullptr, 0, nullptr, 4, nullptr, nullptr)
-                 : plnerf_generic_fwd_f32(&s, nullptr, nullptr, e.cols, 0, nullptr, 0, nullptr, 4, nullptr);
-        return rc ? rc : PLNERF_EINVAL;      // (a size of 0 is a refusal whatever the empty call says)
-    }
-    // every launch's grid, before the first: plnerf_generic_fwd_f32's row limit, plnerf_generic_fwd's tiles and copies
-    // (check_grids, as that entry calls it for a network with a concatenation: one with view directions has one)
-    if (net_workspace_bytes(n, net_rows) == 0) return PLNERF_ERANGE;
-    return n.route == PLNERF_ANYVIEW_CHAIN16 ? check_grids(net, net_rows, true) : PLNERF_OK;
 }
 
 // Behind plnerf_render_view's checks of the configuration: the routes, max_net_rows, and that both slots read rows of the
@@ -122,14 +83,6 @@ int check_config(const plnerf_step_config* c, const plnerf_anyview_io* io, Encod
         first = false;
     }
     return PLNERF_OK;
-}
-
-int check_slot(const plnerf_anyview_net& n, int cols) {
-    if (n.route == PLNERF_ANYVIEW_FUSED) return check_net(&n.fused);
-    // (an empty call: the entry's own checks of the table, no launch)
-    return n.route == PLNERF_ANYVIEW_CHAIN16
-               ? plnerf_generic_fwd(&n.shape, n.params, nullptr, cols, 0, n.precision, nullptr, 0, nullptr, 4, nullptr, nullptr)
-               : plnerf_generic_fwd_f32(&n.shape, n.params, nullptr, cols, 0, nullptr, 0, nullptr, 4, nullptr);
 }
 
 // One network outside the trunk over a pass's K samples per ray, in sub-blocks of at most p.net_rows rows, then that pass's
